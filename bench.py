@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- training images/sec of the LRCN step (VGG-16 -> fc7 forward + 2-layer LSTM fwd/bwd + Adam) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -254,6 +254,36 @@ PRESETS = {  # BASELINE.json configs[k] -> flags (SURVEY.md 8d "Config -> shapes
 }
 
 
+DUMP_MAX_ELEMS = 1 << 20   # --dump-outputs: at most 4 MB of float32 per array, so the nine parameters stay under 64 MB in all
+DUMP_SEED = 20240607
+
+
+def output_sample(t, key, cap=DUMP_MAX_ELEMS):
+    """--dump-outputs: a tensor -> float32 numpy.  At most `cap` elements: the whole tensor in its logical shape.  More: `cap` of them,
+    flattened in logical row-major order, at sorted positions drawn from (DUMP_SEED, key) -- the same positions on every run."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    n = t.numel()
+    if n <= cap:
+        return t.float().cpu().numpy()
+    idx = np.sort(np.random.default_rng([DUMP_SEED, key]).choice(n, cap, replace=False))
+    return t.reshape(-1).index_select(0, torch.as_tensor(idx, device=t.device)).float().cpu().numpy()
+
+
+def write_outputs(d, arrays):
+    """arrays: list of (name, float32 / float64 numpy array) -> d/<name>.npy; returns {name: shape written}."""
+    import numpy as np
+    total = sum(v.nbytes for _, v in arrays)
+    if total > 64 << 20:
+        raise SystemExit("--dump-outputs: %d bytes is more than the 64 MB allowed" % total)
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays:
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(d, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in arrays}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -299,7 +329,16 @@ def parse_args(argv=None):
                          "2 s 6.75 6.99 7.00 7.02 7.09 ms -- what differs between leases is the box: profiles/r06b_*, r06d_*).  0 = off")
     ap.add_argument("--watchdog-s", type=float, default=float(os.environ.get("LRCN_BENCH_WATCHDOG_S", "900")),
                     help="self-launched jobs: kill the ranks and fail if they have not finished after this many seconds")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step handed its caller to DIR/<name>.npy: loss.npy (float64) "
+                         "and the nine updated parameters (float32; a tensor of more than %d elements as a fixed, seeded sample of that many, "
+                         "flattened in logical row-major order).  Training configurations only.  With --emulate-world N and the sharded update the "
+                         "other ranks' shards of the parameters are never updated: they are dumped as they are" % DUMP_MAX_ELEMS)
     a = ap.parse_args(argv)
+    if a.dump_outputs is not None:
+        if a.config == "c5":
+            ap.error("--dump-outputs: the training configurations only (c2, c3, c4)")
+        a.dump_outputs = os.path.abspath(a.dump_outputs)   # ranks started by the launcher see the same directory
     if a.config in PRESETS:
         for k, v in PRESETS[a.config].items():
             if getattr(a, k) is None:
@@ -500,6 +539,14 @@ def rank_main(a, world, rank, local_rank):
         m_chunk //= 2
     Bv = m_chunk * B
     ctx = L.Context(E, H, H, V, max_B=B, max_T=T, lstm_dtype=dt, vgg_dtype=dt, max_images=Bv, n_layers=a.layers)
+    # Every sum on the lossgradient route in a fixed order (no float atomics): the same arguments give the same bits, run after run
+    # (--dump-outputs).  The ordered embedding sum takes at most 8192 rows per call ((T+1) x rows per GPU): above that, and with
+    # LRCN_DETERMINISTIC=0 (development A/B), the float-atomic sums run instead and the line says so (config.deterministic).
+    det_rows = (T + 1) * B
+    deterministic = os.environ.get("LRCN_DETERMINISTIC", "1")[:1] != "0" and det_rows <= 8192
+    det_note = None if deterministic else ("LRCN_DETERMINISTIC=0" if det_rows <= 8192 else
+                                           "float-atomic sums: %d rows per step exceed the ordered sum's 8192" % det_rows)
+    ctx.set_option(lrcn_amd._lib.LRCN_OPT_DETERMINISTIC, 1 if deterministic else 0)
     vgg_w = L.synthetic_vgg_weights(seed=1)
     L.vgg_load(ctx, *vgg_w)
     param = L.initweights(ctx, seed=42)          # identical on every rank (same seed)
@@ -622,6 +669,11 @@ def rank_main(a, world, rank, local_rank):
     _lib.check(ctx._h, _lib.lib().lrcn_profile_get(ctx._h, C.byref(conv_ms), C.byref(conv_n)))
     _lib.check(ctx._h, _lib.lib().lrcn_profile(ctx._h, 0))
     loss = trainer.loss_value()
+    # --dump-outputs: what the last timed step handed its caller, taken before the untimed sub-report pass below trains further
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = [("loss", np.array([loss], dtype=np.float64))] + [
+            (n, output_sample(p, k)) for k, (n, p) in enumerate(zip(L.PARAM_NAMES, param))]
     if getattr(trainer, "_tail_events", None):   # LRCN_DP_DEBUG_TAIL=1 (development)
         tails = [a_.elapsed_time(b_) for a_, b_ in trainer._tail_events[-a.steps:]]
         print("update chain past the end of the backward pass, ms per step: median %.3f min %.3f max %.3f  first16 %s" % (
@@ -673,7 +725,7 @@ def rank_main(a, world, rank, local_rank):
                        "global_batch": Bg, "per_gpu_batch": B, "seq_len": T + 1, "parallelism": "dp%d" % world,
                        "vgg_forward": ("one forward per step (%d images)" % B) if m_chunk == 1 else
                                       ("one forward per %d steps (%d images: the crops of the next %d batches of this rank; one feature block per step)" % (m_chunk, Bv, m_chunk)),
-                       "last_loss": loss,
+                       "last_loss": loss, "deterministic": deterministic, **({"deterministic_note": det_note} if det_note else {}),
                        "inputs": ("pinned host, H2D per step on a copy stream (%.1f MB per step, uploaded one step ahead of the forward that reads it)"
                                   % (B * 224 * 224 * 3 / 1e6)) if a.inputs == "host" else "resident in HBM",
                        "setup_spinup": "%d untimed VGG forwards (%.0f ms) before the warm-up steps; not training steps" % (spun, a.spinup_ms)},
@@ -701,6 +753,9 @@ def rank_main(a, world, rank, local_rank):
                       (L.from_jl(vgg_w[2][0]), vgg_w[2][1].cpu().numpy()), (L.from_jl(vgg_w[3][0]), vgg_w[3][1].cpu().numpy()))
             out["cpu_baseline"], sample = cpu_baseline(host_w, E, H, V, T, np.random.default_rng(3), a.layers)
             out["parity"] = parity_spot_check(ctx, L, sample, imgs_dev[0], a.dtype)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": a.dump_outputs, "shapes": write_outputs(a.dump_outputs, dumped),
+                                   "sampled_above_elements": DUMP_MAX_ELEMS, "sample_seed": DUMP_SEED}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

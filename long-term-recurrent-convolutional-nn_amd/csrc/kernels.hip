@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void embed_scatter_rm_kernel(const float *dxem
 // Sparse exchange of the embedding gradient (data parallelism): a rank's contribution to d Wembed is its (T+1) B rows of d(x_lstm) (dropout
 // multiplier applied) with their token ids -- 1.5 MB at 32 rows against the 42.6 MB dense V x E gradient.  This kernel writes those rows
 // E-contiguous into the caller's buffer; the ranks all-gather rows + ids and every rank sums ALL of them in one fixed order
-// (sort_token_rows_kernel + embed_segsum_kernel below: bit-identical results on every rank, as an all-reduce would give).
+// (rank_token_rows_kernel + embed_segsum_kernel below: bit-identical results on every rank, as an all-reduce would give).
 __global__ __launch_bounds__(256) void embed_rows_export_kernel(const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out) {
     const int m = blockIdx.x;
     const int s = m / B, b = m - s * B;
@@ -108,48 +108,85 @@ __global__ __launch_bounds__(256) void embed_rows_export_kernel(const float *dxe
     float *dst = out + (int64_t)m * E;
     for (int e = threadIdx.x; e < E; e += blockDim.x) dst[e] = src[e] * drop_mult(d, s, b, e, B, E);
 }
-// LRCN_OPT_DETERMINISTIC: keys (token, row) sorted by ONE workgroup (bitonic network in LDS, n <= 8192 padded to a power of two), so
-// that the rows of a token are consecutive and in row order ...
-__global__ __launch_bounds__(1024) void sort_token_rows_kernel(const int32_t *tok_in, int M, int P2, unsigned long long *keys_out) {
-    extern __shared__ unsigned long long sk[];
-    for (int i = threadIdx.x; i < P2; i += blockDim.x)
-        sk[i] = i < M ? (((unsigned long long)(unsigned)tok_in[i] << 32) | (unsigned)i) : ~0ull;
+// LRCN_OPT_DETERMINISTIC: the rows grouped by token, each token's rows in row order -- a stable counting sort, integer arithmetic only.  Row m
+// goes to position #{rows with a smaller token} + #{earlier rows with its token}; each block ranks 64 rows against all M tokens (in LDS,
+// its 4 waves a quarter of them each).  Key = token << 32 | segment length << 16 | row, the length (the token's row count) only at the
+// token's first position and 0 elsewhere.  M <= 8192.
+__global__ __launch_bounds__(256) void rank_token_rows_kernel(const int32_t *tok_in, int M, unsigned long long *keys_out) {
+    extern __shared__ unsigned stok[];
+    __shared__ int part[3][4][64];
+    for (int i = threadIdx.x; i < M; i += blockDim.x) stok[i] = (unsigned)tok_in[i];
     __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P2; i += blockDim.x) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const unsigned long long a = sk[i], b = sk[l];
-                    const bool up = (i & k) == 0;
-                    if ((a > b) == up) { sk[i] = b; sk[l] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = threadIdx.x; i < M; i += blockDim.x) keys_out[i] = sk[i];
-}
-// ... and one wave per (segment head, 256-column slice) adds the segment's rows in that order: plain stores, a fixed summation order.
-__global__ __launch_bounds__(64) void embed_segsum_kernel(const float *dxemb, int64_t ld_dx, const unsigned long long *keys, int M, int B, int E,
-                                                          DropSpec d, float *stage, int64_t ld_s) {
-    const int i = blockIdx.x;
-    const unsigned tok = (unsigned)(keys[i] >> 32);
-    if (i > 0 && (unsigned)(keys[i - 1] >> 32) == tok) return;  // not the first row of its token
-    const int e0 = blockIdx.y * 256 + threadIdx.x * 4;
-    if (e0 >= E) return;
-    float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int j = i; j < M && (unsigned)(keys[j] >> 32) == tok; ++j) {
-        const int m = (int)(unsigned)keys[j];
-        const int s = m / B, b = m - s * B;
-        const float *src = dxemb + (int64_t)m * ld_dx;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (e0 + k < E) acc[k] += src[e0 + k] * drop_mult(d, s, b, e0 + k, B, E);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int m = blockIdx.x * 64 + lane;
+    const unsigned t = m < M ? stok[m] : 0u;
+    const int q = (M + 3) / 4, j0 = w * q, j1 = min(M, j0 + q);
+    int less = 0, eq_before = 0, eq = 0;
+#pragma unroll 8
+    for (int j = j0; j < j1; ++j) {
+        const unsigned u = stok[j];
+        less += u < t;
+        eq += u == t;
+        eq_before += (u == t) & (j < m);
     }
-    float *dst = stage + (int64_t)tok * ld_s;
+    part[0][w][lane] = less;
+    part[1][w][lane] = eq_before;
+    part[2][w][lane] = eq;
+    __syncthreads();
+    if (w == 0 && m < M) {
+        for (int k = 1; k < 4; ++k) {
+            less += part[0][k][lane];
+            eq_before += part[1][k][lane];
+            eq += part[2][k][lane];
+        }
+        keys_out[less + eq_before] = ((unsigned long long)t << 32) | ((unsigned long long)(eq_before == 0 ? eq : 0) << 16) | (unsigned)m;
+    }
+}
+// ... and one workgroup per (token, 256-column slice) adds the token's rows: their row ids go to LDS 512 at a time, wave w takes rows w, w + 8,
+// ... of the segment in order, and the eight partial sums are added in wave order -- a fixed summation order, plain stores.  (A segment can
+// hold a tenth of all rows: Zipf tokens.)
+__global__ __launch_bounds__(512) void embed_segsum_kernel(const float *dxemb, int64_t ld_dx, const unsigned long long *keys, int M, int B, int E,
+                                                          DropSpec d, float *stage, int64_t ld_s) {
+    __shared__ float part[8][256];
+    __shared__ int rows[512];
+    const int i = blockIdx.x;
+    const unsigned long long head = keys[i];
+    const int n = (int)((head >> 16) & 0xFFFF);
+    if (n == 0) return;  // not the first row of its token (uniform over the block)
+    const unsigned tok = (unsigned)(head >> 32);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int e0 = blockIdx.y * 256 + lane * 4;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int c0 = 0; c0 < n; c0 += 512) {  // n is uniform over the block: so are the barriers
+        const int cn = min(512, n - c0);
+        __syncthreads();  // the previous chunk's ids have been read
+        if ((int)threadIdx.x < cn) rows[threadIdx.x] = (int)(keys[i + c0 + threadIdx.x] & 0xFFFF);
+        __syncthreads();
+        if (e0 < E) {
+#pragma unroll 4
+            for (int j = w; j < cn; j += 8) {
+                const int m = rows[j];
+                const int s = m / B, b = m - s * B;
+                const float *src = dxemb + (int64_t)m * ld_dx;
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (e0 + k < E) dst[e0 + k] = acc[k];
+                for (int k = 0; k < 4; ++k)
+                    if (e0 + k < E) acc[k] += src[e0 + k] * drop_mult(d, s, b, e0 + k, B, E);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) part[w][lane * 4 + k] = acc[k];
+    __syncthreads();
+    if (w == 0 && e0 < E) {
+        float *dst = stage + (int64_t)tok * ld_s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float t = part[0][lane * 4 + k];
+#pragma unroll
+            for (int r = 1; r < 8; ++r) t += part[r][lane * 4 + k];
+            if (e0 + k < E) dst[e0 + k] = t;
+        }
+    }
 }
 // stage[V][ld_s] (row-major, f32) -> dwembed (V x E column-major: [E][V]); every element of dwembed is written; non-zero staging
 // values are replaced by zeros, so the staging array is all-zero again when the kernel ends.  64 x 64 tiles through LDS.
@@ -602,10 +639,10 @@ __global__ void uncast_rows_kernel(const T *in, int64_t ld_in, int R, int C, flo
         out[(int64_t)r * ld_out + c] = to_f32(in[(int64_t)r * ld_in + c]);
 }
 
-template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const T *z, int64_t ld, int M, int N, int rows_per_slab, float *out) {
-    // block = 64 columns (16 lanes x 4 elements, one 8/16-byte load each) x 16 row groups over one slab of rows (blockIdx.y).
+template <typename T, int RG> __global__ __launch_bounds__(16 * RG) void colsum_kernel(const T *z, int64_t ld, int M, int N, int rows_per_slab, float *out) {
+    // block = 64 columns (16 lanes x 4 elements, one 8/16-byte load each) x RG row groups over one slab of rows (blockIdx.y).
     // One slab: plain store (no zeroing, deterministic).  Several slabs: f32 atomics into an output the host zeroed.
-    __shared__ float sh[16][65];
+    __shared__ float sh[RG][65];
     const int q = threadIdx.x & 15, rg = threadIdx.x >> 4;
     const int c = blockIdx.x * 64 + 4 * q;
     const int m0 = blockIdx.y * rows_per_slab, m1 = min(M, m0 + rows_per_slab);
@@ -613,7 +650,7 @@ template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
     if (c < N) {  // ld % 4 == 0 and N <= ld: the whole quad is inside the row
 #pragma unroll 4
-        for (int m = m0 + rg; m < m1; m += 16) {
+        for (int m = m0 + rg; m < m1; m += RG) {
             const V4 v = *reinterpret_cast<const V4 *>(z + (int64_t)m * ld + c);
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[k] += to_f32(v.e[k]);
@@ -626,7 +663,7 @@ template <typename T> __global__ __launch_bounds__(256) void colsum_kernel(const
         const int cc = blockIdx.x * 64 + threadIdx.x;
         float t = 0.0f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) t += sh[r][threadIdx.x];
+        for (int r = 0; r < RG; ++r) t += sh[r][threadIdx.x];
         if (cc < N) {
             if (gridDim.y == 1) out[cc] = t;
             else atomicAdd(out + cc, t);
@@ -1404,11 +1441,9 @@ bool k_embed_scatter_rm(hipStream_t st, const float *dxemb, int64_t ld_dx, const
                         float *stage, int64_t ld_s, float *dwembed, unsigned long long *sort_keys) {
     const int M = S * B;
     if (sort_keys) {  // ordered sums
-        int P2 = 1;
-        while (P2 < M) P2 <<= 1;
-        if (P2 > 8192) return false;
-        hipLaunchKernelGGL(sort_token_rows_kernel, dim3(1), dim3(1024), sizeof(unsigned long long) * (size_t)P2, st, tok_in, M, P2, sort_keys);
-        hipLaunchKernelGGL(embed_segsum_kernel, dim3(M, cdiv(E, 256)), dim3(64), 0, st, dxemb, ld_dx, sort_keys, M, B, E, d, stage, ld_s);
+        if (M > 8192) return false;
+        hipLaunchKernelGGL(rank_token_rows_kernel, dim3(cdiv(M, 64)), dim3(256), sizeof(unsigned) * (size_t)M, st, tok_in, M, sort_keys);
+        hipLaunchKernelGGL(embed_segsum_kernel, dim3(M, cdiv(E, 256)), dim3(512), 0, st, dxemb, ld_dx, sort_keys, M, B, E, d, stage, ld_s);
     } else {
         hipLaunchKernelGGL(embed_scatter_rm_kernel, dim3(M), dim3(256), 0, st, dxemb, ld_dx, tok_in, S, B, E, d, stage, ld_s);
     }
@@ -1522,7 +1557,10 @@ void k_colsum(hipStream_t st, int dtype, const void *z, int64_t ld, int M, int N
     const int rows = cdiv(cdiv(M, slabs), 16) * 16;
     slabs = cdiv(M, rows);
     if (slabs > 1) (void)hipMemsetAsync(out, 0, sizeof(float) * (size_t)N, st);
-    DISPATCH_T(dtype, hipLaunchKernelGGL(colsum_kernel<T>, dim3(cb, slabs), dim3(256), 0, st, (const T *)z, ld, M, N, rows, out));
+    if (slabs == 1 && deterministic && M > 512)  // the ordered form keeps one slab: 64 row groups per block instead of 16, summed in order
+        DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T, 64>), dim3(cb, 1), dim3(1024), 0, st, (const T *)z, ld, M, N, rows, out));
+    else
+        DISPATCH_T(dtype, hipLaunchKernelGGL((colsum_kernel<T, 16>), dim3(cb, slabs), dim3(256), 0, st, (const T *)z, ld, M, N, rows, out));
 }
 void k_transpose_multi(hipStream_t st, int dtype, TrPlan &plan) {
     int tiles = 0;

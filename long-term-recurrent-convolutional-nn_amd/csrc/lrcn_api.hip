@@ -1763,7 +1763,7 @@ int lrcn_set_embed_rows_buffer(lrcn_ctx *c, float *rows, int32_t *tok, int capac
 int lrcn_embed_grad_from_rows(lrcn_ctx *c, const float *rows, const int32_t *tok, int n_rows, float *grad_wembed, void *stream) {
     DeviceGuard dg(c);
     if (!c || !rows || !tok || !grad_wembed) return LRCN_EINVAL;
-    if (n_rows < 1 || n_rows > 8192) FAIL(c, LRCN_EINVAL, "n_rows=%d outside [1, 8192] (the ordered sum sorts its keys in one workgroup)", n_rows);
+    if (n_rows < 1 || n_rows > 8192) FAIL(c, LRCN_EINVAL, "n_rows=%d outside [1, 8192] (the ordered sum ranks at most 8192 keys)", n_rows);
     if (!c->dWe_rm) DALLOC(c, c->dWe_rm, sizeof(float) * (size_t)c->V * c->ldE);
     if (!c->imp_keys) DALLOC(c, c->imp_keys, sizeof(unsigned long long) * 8192);
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : c->stream;

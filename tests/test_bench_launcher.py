@@ -342,3 +342,31 @@ def test_hw_sampler_without_the_sysfs_nodes_is_not_an_error(tmp_path):
     assert r["available"] and r["sclk_mhz"]["median"] == 2150.0 and r["socket_power_w"]["median"] == 1300.0 and r["power_cap_w"] == 1400.0
     assert r["sclk_mhz"]["n"] >= 5
 
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs (bench.output_sample / bench.write_outputs): a small tensor is written whole in its logical shape, a large one as the
+    same seeded sample on every call (so two builds compare output for output), and the files are float32 / float64 .npy under 64 MB."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(12, dtype=torch.float32).reshape(3, 4)
+    np.testing.assert_array_equal(bench.output_sample(small, 0), small.numpy())
+    big = torch.randn(5000, 300).t()   # a transposed (column-major-like) view, as the library's parameters are
+    s1, s2 = bench.output_sample(big, 3, cap=4096), bench.output_sample(big.contiguous(), 3, cap=4096)
+    assert s1.shape == (4096,) and s1.dtype == np.float32
+    np.testing.assert_array_equal(s1, s2)   # positions depend on (seed, key) and the logical order only
+    assert not np.array_equal(s1, bench.output_sample(big, 4, cap=4096))
+    flat = big.reshape(-1).numpy()
+    assert np.isin(s1, flat).all()
+    shapes = bench.write_outputs(str(tmp_path / "out"), [("loss", np.array([1.5])), ("W", s1)])
+    assert shapes == {"loss": [1], "W": [4096]}
+    assert np.load(tmp_path / "out" / "loss.npy").dtype == np.float64
+    np.testing.assert_array_equal(np.load(tmp_path / "out" / "W.npy"), s1)
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), [("x", np.zeros(17 << 20, np.float32))])
+    a = bench.parse_args(["--dump-outputs", "rel_dir"])
+    assert a.dump_outputs == os.path.abspath("rel_dir")
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--config", "c5", "--dump-outputs", "d"])

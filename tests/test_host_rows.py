@@ -1,5 +1,6 @@
 """CPU: the host-side "next" rows of SURVEY.md 8(f): BLEU port against the reference script's outputs, tokenizer /
 vocabulary / equal-length minibatcher properties, checkpoint and feature formats, crop geometry, CLI flag surface."""
+import gzip
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ from lrcn_amd import bleu, captions as cap, formats as fmt
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BLEU_DIR = os.path.join(HERE, "golden", "bleu")
-REF_EVAL = "/root/reference/eval"
+BLEU_FULL = os.path.join(BLEU_DIR, "full")
 
 
 def lines(path):
@@ -28,13 +29,20 @@ def test_bleu_matches_reference_script_on_committed_fixture():
     assert got == lines(os.path.join(BLEU_DIR, "expected200.txt"))[0]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_EVAL), reason="full known-answer files live in the reference tree (build container only)")
-def test_bleu_four_known_answers_of_the_survey():
+def test_bleu_four_known_answers_of_the_survey(tmp_path):
+    # the reference's committed candidates and reference captions, stored gzip-compressed under golden/bleu/full and unpacked here
+    for dirpath, _, files in os.walk(BLEU_FULL):
+        for name in files:
+            rel = os.path.relpath(os.path.join(dirpath, name), BLEU_FULL)[:-len(".gz")]
+            os.makedirs(os.path.dirname(os.path.join(tmp_path, rel)), exist_ok=True)
+            with gzip.open(os.path.join(dirpath, name), "rb") as src, open(os.path.join(tmp_path, rel), "wb") as dst:
+                dst.write(src.read())
+    ref_eval = str(tmp_path)
     exp = lines(os.path.join(BLEU_DIR, "expected_full.txt"))
     cases = [("candidates.txt", "coco_refs/ref"), ("caps_flickr_bm3", "flickr_refs/f_ref"), ("caps_flickr_bm5", "flickr_refs/f_ref"),
              ("caps_flickr_bm10", "flickr_refs/f_ref")]
     for (hyp, stem), want in zip(cases, exp):
-        got = bleu.format_bleu(bleu.multi_bleu(lines(os.path.join(REF_EVAL, hyp)), bleu.read_refs(os.path.join(REF_EVAL, stem))))
+        got = bleu.format_bleu(bleu.multi_bleu(lines(os.path.join(ref_eval, hyp)), bleu.read_refs(os.path.join(ref_eval, stem))))
         assert got == want
     assert exp[0].startswith("BLEU = 68.2/47.1/33.0/23.5") and exp[2].startswith("BLEU = 60.9/39.4/26.0/17.6")
 
