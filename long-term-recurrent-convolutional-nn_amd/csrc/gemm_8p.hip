@@ -23,6 +23,7 @@
 
 #include "common.h"
 #include "gemm.h"
+#include "philox.h"
 
 namespace {
 
@@ -542,8 +543,9 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
         return false;
     }
     // ---------------------------------------------------------------- softmax / top-K partials (gemm.h SmaxEpi): the logits stay on chip
-    if constexpr (EPI == GEMM_OUT_SMAX_TOPK) {
+    if constexpr (EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL) {
         static_assert(BM == 256 && BN == 256 && SWAP && !F8, "built for the 256 x 256 tile");
+        constexpr bool GUM = EPI == GEMM_OUT_SMAX_GUMBEL;
         // Two phases, one per 128-column half h of the tile: the waves that own those columns (wc >> 1 == h) stage accumulator + bias as f32
         // (256 rows x 512 bytes = the whole ring; 16-byte chunk c of row r at chunk c ^ (r & 31)), columns past N as -inf; then thread t scans
         // 64 of them for row t >> 1 (part t & 1: columns [0, 32) + [64, 96) resp. [32, 64) + [96, 128) of the half) and carries {max, sum exp,
@@ -561,6 +563,9 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
             tv[k] = -INFINITY;
             ti[k] = 0x7FFFFFFF;
         }
+        // GUMBEL: the record's winner {score, column, z}
+        float gs = -INFINITY, gz = -INFINITY;
+        int gc = 0x7FFFFFFF;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if ((wc >> 1) == h) {
@@ -609,7 +614,30 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
                     const f32x4v x = *reinterpret_cast<const f32x4v *>(rowp + ((cid(c) ^ sw) << 4));
 #pragma unroll
                     for (int k = 0; k < 4; ++k) s4[k] += __expf(x[k] - m_run);
-                    if (fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])) > tv[SMAX_KC - 1]) {   // one test per chunk: most chunks offer nothing
+                    if constexpr (GUM) {
+                        // m_run only grows, so the pruning bound against it is exact for the row's final max too.  Greedy (T = 0): the
+                        // largest z, lower column first (columns ascend within the thread's scan)
+                        const float thr = e.temp > 0.0f ? m_run - GUMBEL_PRUNE * e.temp : m_run;
+                        if (fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])) >= thr) {
+                            const int cbase = n0 + h * 128 + 4 * cid(c);
+                            if (e.temp > 0.0f) {
+                                // the row's counter words (s, i) are recomputed here rather than held beside the other half's accumulators
+                                const int grow = m0 + srow, gii = grow / e.S;
+                                const Philox4 rnd = philox4x32_10((uint32_t)(cbase >> 2), (uint32_t)e.current, (uint32_t)(grow - gii * e.S), (uint32_t)gii,
+                                                                  e.key0, e.key1);
+#pragma unroll
+                                for (int k = 0; k < 4; ++k)
+                                    if (x[k] >= thr) {
+                                        const float sc = x[k] / e.temp + gumbel_of(rnd.x[k]);
+                                        if (sc > gs) { gs = sc; gc = cbase + k; gz = x[k]; }
+                                    }
+                            } else {
+#pragma unroll
+                                for (int k = 0; k < 4; ++k)
+                                    if (x[k] > gs) { gs = x[k]; gc = cbase + k; gz = x[k]; }
+                            }
+                        }
+                    } else if (fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])) > tv[SMAX_KC - 1]) {   // one test per chunk: most chunks offer nothing
                         const int cbase = n0 + h * 128 + 4 * cid(c);
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
@@ -637,7 +665,11 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
             __syncthreads();   // the ring is overwritten by the next phase / the next tile's DMA
         }
         const int row = m0 + srow;
-        if (row < M) {
+        if (GUM && row < M) {
+            float *rec = e.part + ((int64_t)row * e.nrec + (2 * (n0 >> 8) + part)) * SMAX_REC;
+            *reinterpret_cast<f32x4v *>(rec) = f32x4v{m_run, s_run, gs, __int_as_float(gc)};
+            rec[4] = gz;
+        } else if (row < M) {
             float *rec = e.part + ((int64_t)row * e.nrec + (2 * (n0 >> 8) + part)) * SMAX_REC;
             *reinterpret_cast<f32x4v *>(rec) = f32x4v{m_run, s_run, tv[0], tv[1]};
             *reinterpret_cast<f32x4v *>(rec + 4) = f32x4v{tv[2], tv[3], tv[4], tv[5]};
@@ -1014,7 +1046,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmArgs g) {
 
 template <int WM, int WN, int MT, int NT, int AMODE, bool SWAP, bool F8 = false, int EPI = 0> hipError_t launch_one(hipStream_t s, const GemmArgs &g, int splitk) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    constexpr int ring = 2 * (BM + BN) * 128, ctile = EPI == GEMM_OUT_SMAX_TOPK ? BM * 512 : BM * BN * (EPI ? 4 : 2);  // the LSTM epilogues stage the f32 tile, SMAX a 128-column half
+    constexpr int ring = 2 * (BM + BN) * 128, ctile = EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL ? BM * 512 : BM * BN * (EPI ? 4 : 2);  // the LSTM epilogues stage the f32 tile, SMAX a 128-column half
     constexpr int lds = ring > ctile ? ring : ctile;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static LdsAttrMask attr_done{0};
@@ -1210,7 +1242,7 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         g.out_mode = GEMM_OUT_PLAIN;  // tile menu and operand checks are those of a plain contraction; the kernel template carries the mode
         g.cfg_pref = 2;
     }
-    if (epi == GEMM_OUT_SMAX_TOPK) {  // 256 x 256 tiles, the logits reduced to per-row records in the epilogue: C is never written
+    if (epi == GEMM_OUT_SMAX_TOPK || epi == GEMM_OUT_SMAX_GUMBEL) {  // 256 x 256 tiles, the logits reduced to per-row records in the epilogue: C is never written
         static_assert(SMAX_KC == 6 && SMAX_REC == 16, "record layout of the epilogue's four 16-byte stores");
         g.out_mode = GEMM_OUT_PLAIN;
         g.c_f32 = 1;
@@ -1223,6 +1255,10 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         g.dbg = dbg5 ? atoi(dbg5) : 0;
         g.inv_w2 = g.inv_h2 = 0;
         gemm_debug_note_route(nullptr, 0);
+        if (epi == GEMM_OUT_SMAX_GUMBEL) {
+            if (g.smax.S < 1 || !(g.smax.temp >= 0.0f)) return hipErrorInvalidValue;
+            return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_GUMBEL>(stream, g, 1);
+        }
         return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_TOPK>(stream, g, 1);
     }
     static const char *dbg = getenv("LRCN_DBG");  // kernel-development ablation flags (gemm.h)

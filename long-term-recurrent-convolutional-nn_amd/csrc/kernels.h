@@ -214,6 +214,21 @@ void k_row_div(hipStream_t st, int32_t *out, int R, int K);
 void k_gather_state(hipStream_t st, int dtype, const float *const in[4], float *const out[4], void *const hT[4], const int64_t ldT[4],
                     const int C[4], const int32_t *parent, int R);
 
+// ---- sample.hip: the per-step draw of the sampled decode (lrcn_sample_batch) ----
+// Device state of R independent rows: histories seq [R][L] (bos first), next input last[R], log-likelihood logp[R], done[R] / len[R],
+// ndone = number of finished rows.  A row stops after eos or at current > nword.
+struct SampleState {
+    int32_t *seq, *last, *done, *len, *ndone;
+    float *logp;
+    int L, current, nword, eos;
+};
+void k_sample_init(hipStream_t st, const SampleState &s, int R, int bos);
+// from f32 logits [R][ld]: one workgroup per row (any V; top_k 0 = all columns, else <= 32; temp 0 = greedy)
+void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
+// from GEMM_OUT_SMAX_GUMBEL records (top_k = 0) resp. GEMM_OUT_SMAX_TOPK records (1 <= top_k < SMAX_KC); false = not applicable
+bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s);
+bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
+
 // ---- fp8.hip: OCP e4m3 plumbing of the VGG convolution stack ----
 void k_quant_conv_w_fp8(hipStream_t st, const float *w, int Cin, int Cout, void *out, float *sw);
 void k_amax(hipStream_t st, int in_f32, const void *x, int64_t n, float *out);  // atomic max of |x| into *out (caller zeroes)

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/lrcn.h"
+#include "../../include/lrcn_sample.h"
 #include "comm.h"
 #include "common.h"
 #include "gemm.h"
@@ -117,6 +118,10 @@ struct lrcn_ctx {
     int32_t *bs_seq[2] = {nullptr, nullptr}, *bs_last = nullptr, *bs_done = nullptr, *bs_ndone = nullptr, *bs_res_tok = nullptr,
             *bs_res_len = nullptr;
     float *bs_p = nullptr, *bs_res_p = nullptr;
+    // lrcn_sample_batch (reuses the beam buffers above): what decode_logits_smax leaves for the sampler's own merge kernel --
+    // 0 = the beam's top-K merge, 1 = GEMM_OUT_SMAX_TOPK records only, 2 = GEMM_OUT_SMAX_GUMBEL records (draw parameters in dec_gumbel)
+    int dec_draw = 0;
+    SmaxEpi dec_gumbel{};
     // VGG
     int vgg_wg_cap = 0;  // > 0: cap on the convolution grids (lrcn_vgg_set_wg_cap)
     bool vgg_loaded = false;
@@ -1064,8 +1069,14 @@ int decode_logits_smax(lrcn_ctx *c, const void *hT, int64_t ldh, const float *bi
     g.out_mode = GEMM_OUT_SMAX_TOPK;
     g.zero_page = c->zero_page;
     g.smax.part = c->smax_part; g.smax.nrec = nrec;
+    if (c->dec_draw == 2) {   // the sampled decode: each record keeps its Gumbel-max winner instead of a top-K list
+        g.out_mode = GEMM_OUT_SMAX_GUMBEL;
+        g.smax.temp = c->dec_gumbel.temp; g.smax.key0 = c->dec_gumbel.key0; g.smax.key1 = c->dec_gumbel.key1;
+        g.smax.current = c->dec_gumbel.current; g.smax.S = c->dec_gumbel.S;
+    }
     hipError_t e = launch_gemm_8p(c->stream, g);
     if (e != hipSuccess) FAIL(c, LRCN_EHIP, "decode step (logits GEMM + softmax / top-K epilogue): %s", hipGetErrorString(e));
+    if (c->dec_draw) return LRCN_OK;   // lrcn_sample_batch merges the records itself
     if (!k_softmax_topk_merge(c->stream, c->smax_part, nrec, B, K, c->st_topi, c->st_topv)) FAIL(c, LRCN_EINVAL, "softmax / top-K merge: K = %d, %d records", K, nrec);
     return LRCN_OK;
 }
@@ -1174,6 +1185,18 @@ int step_decode(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2,
     k_lstm_fwd(st, dt, c->st_g, 4 * H2, c->st_f32[3], B, H2, c->st_a, c->ld4H2, c->st_f32[3], h2T, c->ldXH2, c->st_f32[2]);
     GEMM(c, dt, h2T, c->ldXH2, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
     KCHK(c, "step_decode");
+    return LRCN_OK;
+}
+
+// the context's pinned host staging buffer, grown to at least `need` bytes (decode results: see lrcn_beam_search_batch)
+int pin_reserve(lrcn_ctx *c, size_t need) {
+    if (need > c->pin_bytes) {
+        if (c->pin) (void)hipHostFree(c->pin);
+        c->pin = nullptr;
+        c->pin_bytes = 0;
+        if (hipHostMalloc(&c->pin, need, hipHostMallocDefault) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipHostMalloc(%zu) failed", need);
+        c->pin_bytes = need;
+    }
     return LRCN_OK;
 }
 
@@ -2055,14 +2078,7 @@ int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *fe
     // results through a PINNED staging buffer of the context: a device -> pageable-host copy above 64 KB takes HIP's pin-on-the-fly
     // path (measured: +16 ms per decode from 512 images, whose token block is 67 KB -- more than the 12.9 ms of kernels)
     const size_t nb_tok = sizeof(int32_t) * (size_t)N * Lh, nb_n = sizeof(int32_t) * (size_t)N;
-    const size_t need = nb_tok + 2 * nb_n;
-    if (need > c->pin_bytes) {
-        if (c->pin) (void)hipHostFree(c->pin);
-        c->pin = nullptr;
-        c->pin_bytes = 0;
-        if (hipHostMalloc(&c->pin, need, hipHostMallocDefault) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipHostMalloc(%zu) failed", need);
-        c->pin_bytes = need;
-    }
+    if ((r = pin_reserve(c, nb_tok + 2 * nb_n))) return r;
     unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
     HIPCHK(c, hipMemcpyAsync(pin, c->bs_res_tok, nb_tok, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(pin + nb_tok, c->bs_res_len, nb_n, hipMemcpyDeviceToHost, st));
@@ -2071,6 +2087,110 @@ int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *fe
     memcpy(out_tokens, pin, nb_tok);
     memcpy(out_len, pin + nb_tok, nb_n);
     if (out_prob) memcpy(out_prob, pin + nb_tok + nb_n, nb_n);
+    return LRCN_OK;
+}
+
+// Sampled generation (include/lrcn_sample.h; the sample() path of lrcn.jl:613-621, 680-687): the batched decode of lrcn_beam_search_batch
+// -- the same tables, cell epilogues and step forms, selected under the same conditions -- with R = N*S independent rows instead of
+// N*K beams: the parent index is the identity, and the per-step choice is a Gumbel-max draw per row (sample.hip) instead of top-K and
+// a beam reorder.  Where the beam's logits GEMM reduces to top-K records (decode_smax_on), top_k = 0 reduces to Gumbel records instead
+// (GEMM_OUT_SMAX_GUMBEL) and 1 <= top_k < SMAX_KC draws among the top-K records' best columns; otherwise the logits reach st_logits and
+// one workgroup per row draws (LRCN_DECODE_SMAX=0 forces that form).
+int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k,
+                      uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp) {
+    DeviceGuard dg(c);
+    if (!c || !p || !feats || !out_tokens || !out_len) return LRCN_EINVAL;
+    if (N < 1 || S < 1 || (int64_t)N * S > c->maxB) FAIL(c, LRCN_EINVAL, "N*S = %d*%d must be in [1, max_B = %d]", N, S, c->maxB);
+    if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
+    if (top_k < 0 || top_k > 32 || top_k > c->V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, min(32, V=%d)]", top_k, c->V);
+    if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
+    const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
+    const int R = N * S, Lh = nword + 2;
+    hipStream_t st = c->stream;
+    const bool epi = decode_epi_on(c, R);
+    const bool smax = epi && decode_smax_on(c, R, top_k);   // top_k < SMAX_KC
+    const bool tables = epi && decode_tables_on(c, R);
+    struct DrawReset {   // the beam decode never sees a sampler's draw mode, whichever way this call ends
+        lrcn_ctx *c;
+        ~DrawReset() { c->dec_draw = 0; }
+    } reset{c};
+    c->dec_draw = smax ? (top_k == 0 ? 2 : 1) : 0;
+    c->dec_gumbel = SmaxEpi{};
+    c->dec_gumbel.temp = temperature;
+    c->dec_gumbel.key0 = (uint32_t)seed;
+    c->dec_gumbel.key1 = (uint32_t)(seed >> 32);
+    c->dec_gumbel.S = S;
+    int r = tables ? decode_tables_alloc(c) : LRCN_OK;
+    if (r) return r;
+    r = prepare_weights(c, p, false, !tables, false, epi, tables);
+    if (r) return r;
+    // input = input * param[end-3] per image (lrcn.jl:611), each row repeated for the image's S samples
+    k_transpose(st, dt, 1, feats, N, LRCN_CNNOUT, N, c->F, LRCN_CNNOUT, 0);
+    GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, N, h, LRCN_CNNOUT, nullptr, true);
+    k_repeat_rows(st, GEMM_T_F32, c->dxcnn, c->ldh, N, S, h, c->xcnn);
+    const int Hs[4] = {H1, H1, H2, H2};
+    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemsetAsync(c->st_f32[i], 0, sizeof(float) * (size_t)R * Hs[i], st));
+    HIPCHK(c, hipMemsetAsync(c->st_xh1, 0, c->esz * (size_t)R * c->ldXH1, st));  // zero initial h1 / h2 (T copies) and K padding
+    HIPCHK(c, hipMemsetAsync(c->st_xh2, 0, c->esz * (size_t)R * c->ldXH2, st));
+    if (c->nl == 1) {  // LRCN-1f: the x_cnn columns of [emb | x_cnn | h1] are constant over the decode
+        DropSpec nd{};
+        k_concat_x2(st, dt, c->st_xh1, c->ldXH1, c->xcnn, c->ldh, 1, R, E, h, nd);
+    }
+    HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
+    SampleState ss{c->bs_seq[0], c->bs_last, c->bs_done, c->bs_res_len, c->bs_ndone, c->bs_p, Lh, 0, nword, LRCN_EOS};
+    k_sample_init(st, ss, R, LRCN_BOS);   // histories = [bos], log-likelihoods 0, next input = bos
+    k_row_div(st, c->st_parent, R, 1);    // every row continues its own state
+    DropSpec none{};
+    if (tables && (r = decode_tables_build(c, p, N, S))) return r;
+    const int nrec = 2 * ((V + 255) / 256);
+    for (int current = 1; current <= nword + 1; ++current) {
+        ss.current = current;
+        c->dec_gumbel.current = current;
+        if (tables) {
+            r = step_decode_tables(c, p, R, current > 1 ? c->st_parent : nullptr, current == 1, smax ? SMAX_KC - 1 : 0);
+            if (r) return r;
+            std::swap(c->st_f32[1], c->st2_f32[1]);
+            std::swap(c->st_f32[3], c->st2_f32[3]);
+        } else if (epi) {
+            const bool two = c->nl == 2;
+            k_decode_prep(st, c->WeT, c->ldE, c->bs_last, current > 1 ? c->st_parent : nullptr, R, E, c->st_h1, c->ldH1, H1, two ? c->st_h2 : nullptr,
+                          c->ldH2, H2, c->st_xh1, c->ldXH1, c->ldX1, two ? c->st_xh2 : nullptr, c->ldXH2, c->ldH2);
+            r = step_decode(c, p, R, none, true, current > 1 ? c->st_parent : nullptr, current == 1, smax ? SMAX_KC - 1 : 0);
+            if (r) return r;
+            std::swap(c->st_f32[1], c->st2_f32[1]);
+            if (two) std::swap(c->st_f32[3], c->st2_f32[3]);
+        } else {
+            // the plain step updates the states in place (k_lstm_fwd), which is where an identity parent leaves them
+            k_embed_gather(st, dt, c->WeT, c->ldE, c->bs_last, 1, R, E, none, c->st_xh1, c->ldXH1);  // lrcn.jl:650
+            r = step_decode(c, p, R, none, false);
+            if (r) return r;
+        }
+        if (smax && top_k == 0) {
+            if (!k_sample_gumbel_merge(st, c->smax_part, nrec, R, ss)) FAIL(c, LRCN_EINVAL, "sample merge: %d records per row", nrec);
+        } else if (smax) {
+            if (!k_sample_topk_merge(st, c->smax_part, nrec, R, top_k, temperature, seed, S, ss)) FAIL(c, LRCN_EINVAL, "sample top-k merge: top_k = %d, %d records", top_k, nrec);
+        } else {
+            k_sample_rows(st, c->st_logits, c->ldV, R, V, top_k, temperature, seed, S, ss);
+        }
+        if ((current & 3) == 0 && current <= nword) {  // every row finished early?
+            int32_t nd = 0;
+            HIPCHK(c, hipMemcpyAsync(&nd, c->bs_ndone, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            if (nd >= R) break;
+        }
+    }
+    KCHK(c, "sample_batch");
+    // results through the pinned staging buffer (see lrcn_beam_search_batch)
+    const size_t nb_tok = sizeof(int32_t) * (size_t)R * Lh, nb_n = sizeof(int32_t) * (size_t)R;
+    if ((r = pin_reserve(c, nb_tok + 2 * nb_n))) return r;
+    unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
+    HIPCHK(c, hipMemcpyAsync(pin, c->bs_seq[0], nb_tok, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(pin + nb_tok, c->bs_res_len, nb_n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(pin + nb_tok + nb_n, c->bs_p, nb_n, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(out_tokens, pin, nb_tok);
+    memcpy(out_len, pin + nb_tok, nb_n);
+    if (out_logp) memcpy(out_logp, pin + nb_tok + nb_n, nb_n);
     return LRCN_OK;
 }
 

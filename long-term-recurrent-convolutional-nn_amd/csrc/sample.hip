@@ -1,0 +1,281 @@
+// sample.hip -- the per-step choice of the sampled decode (lrcn_sample_batch, include/lrcn_sample.h; the sample() path of lrcn.jl:613-621,
+// 680-687).  Every row r = i * S + s of the batched step is its own hypothesis: it draws tok = argmax_j (z_j / T + g_j) over the whole
+// vocabulary or its top_k largest logits (Gumbel-max: the draw has the distribution softmax(z / T)), appends it to its history and adds
+// log softmax(z)[tok] (temperature 1) to its log-likelihood.  g_j comes from philox.h.  Three forms, one per route of the step:
+//   sample_rows_kernel          -- from the f32 logits of a plain logits GEMM (any T, top_k <= 32, f32 contexts, LRCN_DECODE_SMAX=0)
+//   sample_topk_merge_kernel    -- from the GEMM_OUT_SMAX_TOPK records (top_k < SMAX_KC): the row's top_k columns, noise for those only
+//   sample_gumbel_merge_kernel  -- from the GEMM_OUT_SMAX_GUMBEL records (top_k = 0): the records already hold each 128 columns' winner
+#include "kernels.h"
+
+#include "common.h"
+#include "gemm.h"
+#include "philox.h"
+
+namespace {
+
+// row r takes token tok (log-probability lp) at step `current`; a finished row is frozen
+__device__ __forceinline__ void sample_commit(const SampleState &s, int r, int tok, float lp) {
+    if (s.done[r]) return;
+    s.seq[(int64_t)r * s.L + s.current] = tok;
+    s.last[r] = tok;
+    s.logp[r] += lp;
+    if (tok == s.eos || s.current > s.nword) {
+        s.done[r] = 1;
+        s.len[r] = s.current + 1;
+        atomicAdd(s.ndone, 1);
+    }
+}
+
+// (score, column) pairs: larger score first, lower column in a tie
+__device__ __forceinline__ bool beats(float a, int ai, float b, int bi) { return a > b || (a == b && ai < bi); }
+__device__ __forceinline__ void wave_best(float &v, int &i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(v, o);
+        const int oi = __shfl_xor(i, o);
+        if (beats(ov, oi, v, i)) { v = ov; i = oi; }
+    }
+}
+// block-wide best pair (256 threads); every thread gets the result
+__device__ __forceinline__ void block_best(float &v, int &i, float *shv, int *shi) {
+    wave_best(v, i);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) { shv[w] = v; shi[w] = i; }
+    __syncthreads();
+    v = shv[0]; i = shi[0];
+    for (int q = 1; q < 4; ++q)
+        if (beats(shv[q], shi[q], v, i)) { v = shv[q]; i = shi[q]; }
+}
+__device__ __forceinline__ float block_reduce(float v, float *sh, bool is_max) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = is_max ? fmaxf(v, __shfl_xor(v, o)) : v + __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return is_max ? fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) : (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+__global__ void sample_init_kernel(SampleState s, int R, int bos) {
+    const int64_t n = (int64_t)R * s.L;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x) {
+        s.seq[e] = (e % s.L) == 0 ? bos : 0;
+        if (e < R) {
+            s.last[e] = bos;
+            s.logp[e] = 0.0f;
+            s.done[e] = 0;
+            s.len[e] = 0;
+        }
+    }
+}
+
+// One 256-thread workgroup per row of logits [R][ld]: max and sum exp in one pass over the row (staged in LDS up to V = 15360), the top_k
+// boundary by top_k rounds of a block-wide argmax below the previous winner, then the Gumbel argmax over the admitted columns, four
+// columns (one Philox call) per thread and round.
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float *logits, int64_t ld, int V, int top_k, float temp, uint32_t k0,
+                                                          uint32_t k1, int S, int stage, SampleState s) {
+    extern __shared__ float srow[];
+    __shared__ float shf[4];
+    __shared__ float shv[4];
+    __shared__ int shi[4];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (s.done[r]) return;   // block-uniform
+    const float *g = logits + (int64_t)r * ld;
+    const float *z = stage ? srow : g;
+    float m = -INFINITY;
+    for (int j = tid; j < V; j += 256) {
+        const float x = g[j];
+        if (stage) srow[j] = x;
+        m = fmaxf(m, x);
+    }
+    m = block_reduce(m, shf, true);   // (its barriers also publish srow)
+    float se = 0.0f;
+    for (int j = tid; j < V; j += 256) se += __expf(z[j] - m);
+    se = block_reduce(se, shf, false);
+    const float lse = m + logf(se);
+    // top_k boundary (tv, tc): column j is admitted iff (z_j, j) ranks no lower than it (larger z first, lower column in a tie)
+    float tv = INFINITY;
+    int tc = -1;
+    for (int k = 0; k < top_k; ++k) {
+        float bv = -INFINITY;
+        int bi = 0x7FFFFFFF;
+        for (int j = tid; j < V; j += 256) {
+            const float x = z[j];
+            if ((x < tv || (x == tv && j > tc)) && beats(x, j, bv, bi)) { bv = x; bi = j; }
+        }
+        block_best(bv, bi, shv, shi);
+        tv = bv;
+        tc = bi;
+    }
+    const float thr = temp > 0.0f ? m - GUMBEL_PRUNE * temp : m;
+    const uint32_t si = (uint32_t)(r % S), ii = (uint32_t)(r / S);
+    float bs = -INFINITY, bz = -INFINITY;
+    int bc = 0x7FFFFFFF;
+    for (int q = tid; 4 * q < V; q += 256) {
+        float x[4];
+        bool ok[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = 4 * q + k;
+            x[k] = j < V ? z[j] : -INFINITY;
+            ok[k] = j < V && x[k] >= thr && (top_k == 0 || x[k] > tv || (x[k] == tv && j <= tc));
+            any |= ok[k];
+        }
+        if (!any) continue;
+        if (temp > 0.0f) {
+            const Philox4 rnd = philox4x32_10((uint32_t)q, (uint32_t)s.current, si, ii, k0, k1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k]) {
+                    const float sc = x[k] / temp + gumbel_of(rnd.x[k]);
+                    if (beats(sc, 4 * q + k, bs, bc)) { bs = sc; bc = 4 * q + k; bz = x[k]; }
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k] && beats(x[k], 4 * q + k, bs, bc)) { bs = x[k]; bc = 4 * q + k; bz = x[k]; }
+        }
+    }
+    float wv = bs;
+    int wc = bc;
+    block_best(wv, wc, shv, shi);
+    if (bc == wc && bs == wv) sample_commit(s, r, wc, bz - lse);   // exactly one thread holds the winning column
+}
+
+// Records of GEMM_OUT_SMAX_GUMBEL, one wave per row (4 rows per workgroup): lane l owns records l, l + 64, ...
+template <int NR>
+__global__ __launch_bounds__(256) void sample_gumbel_merge_kernel(const float *part, int nrec, int R, SampleState s) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R || s.done[row]) return;   // wave-uniform
+    const float *rp = part + (int64_t)row * nrec * SMAX_REC;
+    float m[NR], sx[NR];
+    float bs = -INFINITY, bz = -INFINITY, gm = -INFINITY;
+    int bc = 0x7FFFFFFF;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+        const int rec = lane + 64 * q;
+        m[q] = -INFINITY;
+        sx[q] = 0.0f;
+        if (rec < nrec) {
+            const float4 a = *reinterpret_cast<const float4 *>(rp + (int64_t)rec * SMAX_REC);
+            m[q] = a.x; sx[q] = a.y;
+            const int c = __float_as_int(a.w);
+            if (beats(a.z, c, bs, bc)) { bs = a.z; bc = c; bz = rp[(int64_t)rec * SMAX_REC + 4]; }
+        }
+        gm = fmaxf(gm, m[q]);
+    }
+    float se = 0.0f;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o));
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+        if (m[q] != -INFINITY) se += sx[q] * __expf(m[q] - gm);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+    float wv = bs;
+    int wc = bc;
+    wave_best(wv, wc);
+    const unsigned long long owner = __ballot(bc == wc && bs == wv);
+    const float zt = __shfl(bz, (int)__ffsll((long long)owner) - 1);
+    if (lane == 0) sample_commit(s, row, wc, zt - (gm + logf(se)));
+}
+
+// Records of GEMM_OUT_SMAX_TOPK (1 <= top_k < SMAX_KC), one wave per row: the row's top_k largest logits (ties by lower column) are the
+// top_k best heads of the records' sorted lists -- exact, as a record keeps SMAX_KC > top_k of its columns -- and the draw is among them.
+template <int NR>
+__global__ __launch_bounds__(256) void sample_topk_merge_kernel(const float *part, int nrec, int R, int top_k, float temp, uint32_t k0, uint32_t k1,
+                                                                int S, SampleState s) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= R || s.done[row]) return;   // wave-uniform
+    const float *rp = part + (int64_t)row * nrec * SMAX_REC;
+    float m[NR], sx[NR], v[NR][SMAX_KC];
+    int ix[NR][SMAX_KC];
+    float gm = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+        const int rec = lane + 64 * q;
+        m[q] = -INFINITY;
+        sx[q] = 0.0f;
+#pragma unroll
+        for (int j = 0; j < SMAX_KC; ++j) {
+            v[q][j] = -INFINITY;
+            ix[q][j] = 0x7FFFFFFF;
+        }
+        if (rec < nrec) {
+            const float *p = rp + (int64_t)rec * SMAX_REC;
+            m[q] = p[0]; sx[q] = p[1];
+#pragma unroll
+            for (int j = 0; j < SMAX_KC; ++j) {
+                v[q][j] = p[2 + j];
+                ix[q][j] = __float_as_int(p[8 + j]);
+            }
+        }
+        gm = fmaxf(gm, m[q]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) gm = fmaxf(gm, __shfl_xor(gm, o));
+    float se = 0.0f;
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+        if (m[q] != -INFINITY) se += sx[q] * __expf(m[q] - gm);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) se += __shfl_xor(se, o);
+    const float lse = gm + logf(se);
+    const uint32_t si = (uint32_t)(row % S), ii = (uint32_t)(row / S);
+    float bs = -INFINITY, bz = -INFINITY;
+    int bc = 0x7FFFFFFF;
+    for (int k = 0; k < top_k; ++k) {
+        float lv = -INFINITY;
+        int li = 0x7FFFFFFF;
+#pragma unroll
+        for (int q = 0; q < NR; ++q)
+            if (beats(v[q][0], ix[q][0], lv, li)) { lv = v[q][0]; li = ix[q][0]; }
+        float cv = lv;
+        int ci = li;
+        wave_best(cv, ci);   // the k-th largest logit of the row and its column (wave-uniform)
+#pragma unroll
+        for (int q = 0; q < NR; ++q)
+            if (ix[q][0] == ci && v[q][0] == cv) {   // the owner retires it: shift the list (static indices only)
+#pragma unroll
+                for (int j = 0; j + 1 < SMAX_KC; ++j) {
+                    v[q][j] = v[q][j + 1];
+                    ix[q][j] = ix[q][j + 1];
+                }
+                v[q][SMAX_KC - 1] = -INFINITY;
+                ix[q][SMAX_KC - 1] = 0x7FFFFFFF;
+            }
+        const float sc = temp > 0.0f ? cv / temp + gumbel_of(philox4x32_10((uint32_t)(ci >> 2), (uint32_t)s.current, si, ii, k0, k1).x[ci & 3]) : cv;
+        if (beats(sc, ci, bs, bc)) { bs = sc; bc = ci; bz = cv; }
+    }
+    if (lane == 0) sample_commit(s, row, bc, bz - lse);
+}
+
+}  // namespace
+
+void k_sample_init(hipStream_t st, const SampleState &s, int R, int bos) {
+    const int64_t n = (int64_t)R * s.L;
+    hipLaunchKernelGGL(sample_init_kernel, dim3((unsigned)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, st, s, R, bos);
+}
+void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int top_k, float temp, uint64_t seed, int S, const SampleState &s) {
+    const int stage = V <= 15360;   // 60 KB of LDS (+ the static few bytes: under the default 64 KB limit)
+    hipLaunchKernelGGL(sample_rows_kernel, dim3(R), dim3(256), stage ? sizeof(float) * V : 0, st, logits, ld, V, top_k, temp, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), S, stage, s);
+}
+bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s) {
+    const dim3 grid((R + 3) / 4);
+    if (nrec <= 64) hipLaunchKernelGGL(sample_gumbel_merge_kernel<1>, grid, dim3(256), 0, st, part, nrec, R, s);
+    else if (nrec <= 128) hipLaunchKernelGGL(sample_gumbel_merge_kernel<2>, grid, dim3(256), 0, st, part, nrec, R, s);
+    else if (nrec <= 256) hipLaunchKernelGGL(sample_gumbel_merge_kernel<4>, grid, dim3(256), 0, st, part, nrec, R, s);
+    else return false;
+    return true;
+}
+bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s) {
+    if (top_k < 1 || top_k >= SMAX_KC) return false;
+    const dim3 grid((R + 3) / 4);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    if (nrec <= 64) hipLaunchKernelGGL(sample_topk_merge_kernel<1>, grid, dim3(256), 0, st, part, nrec, R, top_k, temp, k0, k1, S, s);
+    else if (nrec <= 128) hipLaunchKernelGGL(sample_topk_merge_kernel<2>, grid, dim3(256), 0, st, part, nrec, R, top_k, temp, k0, k1, S, s);
+    else if (nrec <= 256) hipLaunchKernelGGL(sample_topk_merge_kernel<4>, grid, dim3(256), 0, st, part, nrec, R, top_k, temp, k0, k1, S, s);
+    else return false;
+    return true;
+}

@@ -442,17 +442,45 @@ def beam_search_batch(ctx, param, feats, beam_width, nword):
     return [(list(out[i * L:i * L + n[i]]), p[i]) for i in range(N)]
 
 
-def generate(ctx, param, feat, index_to_word, nword, beam_width, normalize=False):
-    """generate (lrcn.jl:585-642): caption text "w1 w2 ... ." -- words after bos up to the first eos (:634-640)."""
-    if normalize:
-        feat = to_jl(from_jl(feat) / from_jl(feat).sum())  # input/sum(input) (lrcn.jl:597)
-    seq, _ = beam_search(ctx, param, feat, beam_width, nword)
+def sample_batch(ctx, param, feats, nsamples, nword, temperature=1.0, top_k=0, seed=0):
+    """Sampled generation for N images in one device-resident decode (lrcn_sample_batch, include/lrcn_sample.h; the sample() path of
+    lrcn.jl:613-621, 680-687): feats N x 4096 -> per image nsamples x (token ids incl. bos, log-likelihood); N * nsamples <= max_B.
+    temperature 0 = greedy (beam width 1); top_k 0 = the whole vocabulary.  The draws of image i depend only on (seed, i, sample, step)."""
+    N, S, L = feats.shape[0], nsamples, nword + 2
+    out = (C.c_int32 * (N * S * L))()
+    n = (C.c_int * (N * S))()
+    lp = (C.c_float * (N * S))()
+    ctx._call("lrcn_sample_batch", _p9(param), _ptr(feats), N, S, nword, float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, out, n, lp)
+    return [[(list(out[r * L:r * L + n[r]]), lp[r]) for r in range(i * S, (i + 1) * S)] for i in range(N)]
+
+
+def _caption(seq, index_to_word):
     words = []
     for t in seq[1:]:
         if t == EOS:
             break
         words.append(index_to_word[t])
     return " ".join(words + ["."])
+
+
+def sample_captions(ctx, param, feats, index_to_word, nsamples, nword, temperature=1.0, top_k=0, seed=0, normalize=False):
+    """sample_batch as caption text (as generate): per image the nsamples captions, highest log-likelihood first (ties: sample order)."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    res = []
+    for samples in sample_batch(ctx, param, feats, nsamples, nword, temperature, top_k, seed):
+        order = sorted(range(len(samples)), key=lambda s: -samples[s][1])
+        res.append([_caption(samples[s][0], index_to_word) for s in order])
+    return res
+
+
+def generate(ctx, param, feat, index_to_word, nword, beam_width, normalize=False):
+    """generate (lrcn.jl:585-642): caption text "w1 w2 ... ." -- words after bos up to the first eos (:634-640)."""
+    if normalize:
+        feat = to_jl(from_jl(feat) / from_jl(feat).sum())  # input/sum(input) (lrcn.jl:597)
+    seq, _ = beam_search(ctx, param, feat, beam_width, nword)
+    return _caption(seq, index_to_word)
 
 
 # ------------------------------------------------------------------------------------------------ VGG

@@ -56,6 +56,9 @@ def build_parser():
     p.add_argument("--flickr", action="store_true")
     p.add_argument("--coco", action="store_true")
     p.add_argument("--beam_width", type=int, default=3)
+    p.add_argument("--sample", type=int, default=0, help="--generate: draw this many captions per image instead of beam search (0 = beam search)")
+    p.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature (0 = greedy)")
+    p.add_argument("--topk", type=int, default=0, help="--sample: draw among the k most probable words only (0 = all)")
     p.add_argument("--dropout", type=float, default=0.4, help="pdrop of train! (lrcn.jl:227)")
     p.add_argument("--features", nargs="+", default=[], help=".npz feature dictionaries: train [val] (formats.save_features)")
     p.add_argument("--imagedir", default=".", help="directory of the images for --extfeatures")
@@ -151,7 +154,7 @@ def main(argv=None):
         raise SystemExit("--hidden takes two sizes, the second even (LRCN-2f, lrcn.jl:496-504)")
     H1, H2 = o.hidden
     gen_chunk = 256  # images decoded together by the batched beam search (1280 hypothesis rows at beam 5: the decode GEMMs fill the chip)
-    ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, o.beam_width * (gen_chunk if o.generate > 0 else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
+    ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, (o.sample or o.beam_width) * (gen_chunk if o.generate > 0 else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
                     max_images=max(o.batchsize, 256 if o.train else 1) if o.cnn else 0)   # training: room for the crops of several batches per forward
     param = L.initweights(ctx, seed=o.seed if o.seed > 0 else 42) if host_model is None else L.model_from_arrays(host_model)
     say("LSTM is initialized")
@@ -198,11 +201,16 @@ def main(argv=None):
 
     # ---------------------------------------------------------------- generate (lrcn.jl:127-160)
     if o.generate > 0:
+        sample_seed = o.seed if o.seed > 0 else 0
         if o.cnn:
             crop = load_crops([o.image])
             if vdt == lrcn_amd.LRCN_FP8:
                 L.vgg_calibrate(ctx, crop, mean=mean)
             f = L.convnet_u8(ctx, crop, mean=mean, normalize=True)  # input = input / sum(input)  (lrcn.jl:595-597)
+            if o.sample > 0:  # the S draws, highest log-likelihood first
+                for line in L.sample_captions(ctx, param, f, idx2word, o.sample, o.generate, o.temperature, o.topk, sample_seed)[0]:
+                    print(line)
+                return 0
             toks, _ = L.beam_search(ctx, param, f, o.beam_width, o.generate)
             print(cap.caption_text(toks, idx2word))
             return 0
@@ -220,12 +228,27 @@ def main(argv=None):
         import gc  # tools/beam_bench.py: keep full cyclic-GC passes (tens of ms with torch's objects) out of the decode loop
         gc.collect()
         gc.freeze()
+        smp = open(os.path.join(o.out, "samples" + suffix), "w") if o.sample > 0 else None
         with open(os.path.join(o.out, "candidates" + suffix), "w") as out, open(os.path.join(o.out, "candidate_ids" + suffix), "w") as ido:
             for s0 in range(0, len(ids), gen_chunk):  # the reference decodes image by image; here gen_chunk images x beam_width rows per step
                 chunk = ids[s0:s0 + gen_chunk]
+                if o.sample > 0:
+                    # candidates / ids keep one line per image (the best log-likelihood of the S draws); `samples` holds all of them:
+                    # "id<TAB>log-likelihood<TAB>caption", the image's draws in sample order.  The draws of an image depend on its index in the
+                    # call, so every chunk takes its own seed
+                    drawn = L.sample_batch(ctx, param, feature_rows(table, chunk), o.sample, o.generate, o.temperature, o.topk, sample_seed + s0)
+                    for i, rows in zip(chunk, drawn):
+                        best = max(range(len(rows)), key=lambda s: (rows[s][1], -s))
+                        ido.write("%d\n" % i)
+                        out.write(cap.caption_text(rows[best][0], idx2word) + "\n")
+                        for toks, lp in rows:
+                            smp.write("%d\t%.6f\t%s\n" % (i, lp, cap.caption_text(toks, idx2word)))
+                    continue
                 for i, (toks, _) in zip(chunk, L.beam_search_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.generate)):
                     ido.write("%d\n" % i)
                     out.write(cap.caption_text(toks, idx2word) + "\n")
+        if smp is not None:
+            smp.close()
         return 0
 
     # ---------------------------------------------------------------- extract features (lrcn.jl:162-172, 190-221)
