@@ -6,7 +6,7 @@
 
 enum { GEMM_A_PLAIN = 0, GEMM_A_CONV3 = 1 };
 enum { GEMM_OUT_PLAIN = 0, GEMM_OUT_CONV = 1, GEMM_OUT_POOL = 2, GEMM_OUT_LSTM_FWD = 3, GEMM_OUT_LSTM_BWD = 4, GEMM_OUT_SMAX_TOPK = 5,
-       GEMM_OUT_SMAX_GUMBEL = 6 };
+       GEMM_OUT_SMAX_GUMBEL = 6, GEMM_OUT_SMAX_PICK = 7 };
 
 // GEMM_OUT_SMAX_TOPK (gemm_8p.hip, bf16, 256 x 256 tiles; round 6): the logits GEMM of a batched beam-decode step whose C never reaches HBM.
 // softmax + sortperm of lrcn.jl:652-656 need, per row, max / sum-exp over all V columns and the K best columns; each tile reduces ITS 256
@@ -17,12 +17,15 @@ enum { SMAX_KC = 6, SMAX_REC = 16 };
 // GEMM_OUT_SMAX_GUMBEL (the sampled decode, lrcn_sample_batch): the same tiles and records, but instead of the top-K list a record carries the
 // Gumbel-max winner of its 128 columns: [0] max, [1] sum exp(x - max), [2] best z / T + g (T = 0: best z), [3] its column (int bits), [4] its z.
 // Row r = i * S + s draws with philox.h's counter (col >> 2, current, s, i); columns below max - GUMBEL_PRUNE * T get no noise.
+// GEMM_OUT_SMAX_PICK (caption scoring, lrcn_score_matrix / lrcn_score_pairs): the same tiles and records, but a record carries the logit of the
+// row's TARGET column instead of a top-K list: [0] max, [1] sum exp(x - max), [2] z[tgt[row]] if that column is among the record's 128, else -inf.
 struct SmaxEpi {
     float *part;   // [M][nrec][SMAX_REC]
     int nrec;      // records per row = 2 * ceil(N / 256)
     float temp;    // GUMBEL: temperature (0 = greedy)
     uint32_t key0, key1;
     int current, S;
+    const int32_t *tgt;   // PICK: [M] target column of every row
 };
 
 // Epilogue operands of the two LSTM out-modes of gemm_8p.hip (bf16 only): the recurrent GEMM of a timestep with the cell update
@@ -71,7 +74,7 @@ struct GemmArgs {
     unsigned inv_w2, inv_h2;  // gemm_8p.hip: reciprocals of W / 2 and H / 2 for decode_pixel_fast (set by launch_gemm_8p; 0 = divide)
     int wg_cap;             // > 0: at most this many workgroups (gemm_8p.hip / conv64.hip walk the tiles persistently)
     LstmEpi lstm;           // out_mode GEMM_OUT_LSTM_FWD / _BWD only
-    SmaxEpi smax;           // out_mode GEMM_OUT_SMAX_TOPK / _GUMBEL only (bias = the logits' bias row; C unused)
+    SmaxEpi smax;           // out_mode GEMM_OUT_SMAX_TOPK / _GUMBEL / _PICK only (bias = the logits' bias row; C unused)
     int cfg_pref;           // gemm_8p.hip: 0 = the dispatcher's tile menu, 2 = prefer the 256 x 128 tile (set by the bg_cus route)
     int free_cus;           // > 0 (rows per GPU below the bg_cus route's threshold): this many CUs are free beside the capped convolution grids --
                             // the split-K planner cuts K so that tiles x slices fit them in ONE round (round 5)

@@ -543,9 +543,9 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
         return false;
     }
     // ---------------------------------------------------------------- softmax / top-K partials (gemm.h SmaxEpi): the logits stay on chip
-    if constexpr (EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL) {
+    if constexpr (EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL || EPI == GEMM_OUT_SMAX_PICK) {
         static_assert(BM == 256 && BN == 256 && SWAP && !F8, "built for the 256 x 256 tile");
-        constexpr bool GUM = EPI == GEMM_OUT_SMAX_GUMBEL;
+        constexpr bool GUM = EPI == GEMM_OUT_SMAX_GUMBEL, PICK = EPI == GEMM_OUT_SMAX_PICK;
         // Two phases, one per 128-column half h of the tile: the waves that own those columns (wc >> 1 == h) stage accumulator + bias as f32
         // (256 rows x 512 bytes = the whole ring; 16-byte chunk c of row r at chunk c ^ (r & 31)), columns past N as -inf; then thread t scans
         // 64 of them for row t >> 1 (part t & 1: columns [0, 32) + [64, 96) resp. [32, 64) + [96, 128) of the half) and carries {max, sum exp,
@@ -566,6 +566,10 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
         // GUMBEL: the record's winner {score, column, z}
         float gs = -INFINITY, gz = -INFINITY;
         int gc = 0x7FFFFFFF;
+        // PICK: the row's target column (read once) and its logit, if this thread's columns hold it
+        [[maybe_unused]] int tcol = -1;
+        [[maybe_unused]] float zt = -INFINITY;
+        if constexpr (PICK) tcol = m0 + srow < M ? e.tgt[m0 + srow] : -1;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             if ((wc >> 1) == h) {
@@ -637,6 +641,9 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
                                     if (x[k] > gs) { gs = x[k]; gc = cbase + k; gz = x[k]; }
                             }
                         }
+                    } else if constexpr (PICK) {
+                        const int d = tcol - (n0 + h * 128 + 4 * cid(c));
+                        if ((unsigned)d < 4u) zt = d == 0 ? x[0] : d == 1 ? x[1] : d == 2 ? x[2] : x[3];
                     } else if (fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])) > tv[SMAX_KC - 1]) {   // one test per chunk: most chunks offer nothing
                         const int cbase = n0 + h * 128 + 4 * cid(c);
 #pragma unroll
@@ -665,7 +672,10 @@ __device__ __forceinline__ bool gemm8p_tile(const GemmArgs &g, unsigned char *sm
             __syncthreads();   // the ring is overwritten by the next phase / the next tile's DMA
         }
         const int row = m0 + srow;
-        if (GUM && row < M) {
+        if (PICK && row < M) {
+            float *rec = e.part + ((int64_t)row * e.nrec + (2 * (n0 >> 8) + part)) * SMAX_REC;
+            *reinterpret_cast<f32x4v *>(rec) = f32x4v{m_run, s_run, zt, 0.0f};
+        } else if (GUM && row < M) {
             float *rec = e.part + ((int64_t)row * e.nrec + (2 * (n0 >> 8) + part)) * SMAX_REC;
             *reinterpret_cast<f32x4v *>(rec) = f32x4v{m_run, s_run, gs, __int_as_float(gc)};
             rec[4] = gz;
@@ -1046,7 +1056,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmArgs g) {
 
 template <int WM, int WN, int MT, int NT, int AMODE, bool SWAP, bool F8 = false, int EPI = 0> hipError_t launch_one(hipStream_t s, const GemmArgs &g, int splitk) {
     constexpr int BM = WM * MT * 32, BN = WN * NT * 32;
-    constexpr int ring = 2 * (BM + BN) * 128, ctile = EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL ? BM * 512 : BM * BN * (EPI ? 4 : 2);  // the LSTM epilogues stage the f32 tile, SMAX a 128-column half
+    constexpr int ring = 2 * (BM + BN) * 128, ctile = EPI == GEMM_OUT_SMAX_TOPK || EPI == GEMM_OUT_SMAX_GUMBEL || EPI == GEMM_OUT_SMAX_PICK ? BM * 512 : BM * BN * (EPI ? 4 : 2);  // the LSTM epilogues stage the f32 tile, SMAX a 128-column half
     constexpr int lds = ring > ctile ? ring : ctile;
     static_assert(lds <= 160 * 1024, "LDS budget");
     static LdsAttrMask attr_done{0};
@@ -1242,7 +1252,7 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         g.out_mode = GEMM_OUT_PLAIN;  // tile menu and operand checks are those of a plain contraction; the kernel template carries the mode
         g.cfg_pref = 2;
     }
-    if (epi == GEMM_OUT_SMAX_TOPK || epi == GEMM_OUT_SMAX_GUMBEL) {  // 256 x 256 tiles, the logits reduced to per-row records in the epilogue: C is never written
+    if (epi == GEMM_OUT_SMAX_TOPK || epi == GEMM_OUT_SMAX_GUMBEL || epi == GEMM_OUT_SMAX_PICK) {  // 256 x 256 tiles, the logits reduced to per-row records in the epilogue: C is never written
         static_assert(SMAX_KC == 6 && SMAX_REC == 16, "record layout of the epilogue's four 16-byte stores");
         g.out_mode = GEMM_OUT_PLAIN;
         g.c_f32 = 1;
@@ -1258,6 +1268,10 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         if (epi == GEMM_OUT_SMAX_GUMBEL) {
             if (g.smax.S < 1 || !(g.smax.temp >= 0.0f)) return hipErrorInvalidValue;
             return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_GUMBEL>(stream, g, 1);
+        }
+        if (epi == GEMM_OUT_SMAX_PICK) {
+            if (!g.smax.tgt) return hipErrorInvalidValue;
+            return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_PICK>(stream, g, 1);
         }
         return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_TOPK>(stream, g, 1);
     }

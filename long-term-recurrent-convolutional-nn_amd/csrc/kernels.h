@@ -229,6 +229,20 @@ void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V
 bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s);
 bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
 
+// ---- score.hip: the per-pair steps of caption scoring (lrcn_score_matrix / lrcn_score_pairs) ----
+// A2 (T) row r < R: columns [0, h) = P row row_cap[r] (P: this step's [caption][ldP] block of h1 Wproj), columns [h2_off, h2_off + zero_h2) = 0
+// (the first step's zero h2); tgt_row[r] = tgt_cap[row_cap[r]]
+void k_score_prep(hipStream_t st, int dtype, void *A2, int64_t ldA2, const void *P, int64_t ldP, const int32_t *row_cap, int R, int h, int zero_h2,
+                  int64_t h2_off, const int32_t *tgt_cap, int32_t *tgt_row);
+// dst f32 [R][C] = table rows idx[r] (C % 4 == 0)
+void k_score_gather_rows(hipStream_t st, const float *table, int C, const int32_t *idx, int R, float *dst);
+// acc[r] += z[tgt] - max - log(sum exp) from the row's GEMM_OUT_SMAX_PICK records; false = too many records
+bool k_score_pick_merge(hipStream_t st, const float *part, int nrec, int R, double *acc);
+void k_score_acc(hipStream_t st, const double *terms, int R, double *acc);                        // acc[r] += terms[r]
+// rows r0 .. r0+R of the N x M matrix, caption-major over the sorted captions ord[]: image r % N, sorted caption r / N, slot n + ord[j] * N
+void k_score_matrix_rows(hipStream_t st, int64_t r0, int R, int N, const int32_t *ord, int32_t *img, int32_t *cap, int32_t *out);
+void k_score_scatter(hipStream_t st, const double *acc, const int32_t *out_idx, int R, float *scores);  // scores[out_idx[r]] = acc[r]
+
 // ---- fp8.hip: OCP e4m3 plumbing of the VGG convolution stack ----
 void k_quant_conv_w_fp8(hipStream_t st, const float *w, int Cin, int Cout, void *out, float *sw);
 void k_amax(hipStream_t st, int in_f32, const void *x, int64_t n, float *out);  // atomic max of |x| into *out (caller zeroes)

@@ -23,6 +23,7 @@
 
 #include "../../include/lrcn.h"
 #include "../../include/lrcn_sample.h"
+#include "../../include/lrcn_score.h"
 #include "comm.h"
 #include "common.h"
 #include "gemm.h"
@@ -122,6 +123,9 @@ struct lrcn_ctx {
     // 0 = the beam's top-K merge, 1 = GEMM_OUT_SMAX_TOPK records only, 2 = GEMM_OUT_SMAX_GUMBEL records (draw parameters in dec_gumbel)
     int dec_draw = 0;
     SmaxEpi dec_gumbel{};
+    // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
+    void *sc_arena = nullptr;
+    size_t sc_bytes = 0;
     // VGG
     int vgg_wg_cap = 0;  // > 0: cap on the convolution grids (lrcn_vgg_set_wg_cap)
     bool vgg_loaded = false;
@@ -1203,6 +1207,213 @@ int pin_reserve(lrcn_ctx *c, size_t need) {
 // element counts of the context's 9 tensors (0 for the slots its model does not have)
 void ctx_sizes(const lrcn_ctx *c, int64_t sz[9]) { lrcn_param_sizes_n(c->nl, c->E, c->H1, c->H2, c->V, sz); }
 
+// ------------------------------------------------------------------------------------------- caption scoring (include/lrcn_score.h)
+// LRCN_SCORE_FUSED=0: the logits GEMM writes f32 logits and k_softmax_xent reduces them, at every row count
+bool score_fused_on(const lrcn_ctx *c, int R) {
+    const char *k = getenv("LRCN_SCORE_FUSED");  // read per call (the tests switch it inside one process)
+    return !(k && k[0] == '0') && c->dt == GEMM_T_BF16 && R >= 256 && c->V >= 256 && !(c->V & 3) && c->H2 > 64;
+}
+
+// pair_img == NULL: the N x M matrix; else the P pairs.  See lrcn_score.h for the plan; the routes below are chosen once per piece.
+int score_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, const int32_t *tokens, const int *lens, int M, int Tmax,
+               const int32_t *pair_img, const int32_t *pair_cap, int P, float *scores) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    const bool pairs = pair_cap != nullptr || pair_img != nullptr;
+    if (!p || !feats || !tokens || !lens || !scores || (pairs && (!pair_img || !pair_cap))) FAIL(c, LRCN_EINVAL, "null argument");
+    if (c->nl != 2) FAIL(c, LRCN_EINVAL, "caption scoring needs the two-layer model (LRCN-2f)");
+    if (N < 1 || M < 1 || (pairs && P < 1)) FAIL(c, LRCN_EINVAL, "N=%d, M=%d%s must be >= 1", N, M, pairs ? ", P" : "");
+    if (!pairs && (int64_t)N * M > INT32_MAX) FAIL(c, LRCN_EINVAL, "N*M = %lld pairs: at most 2^31 - 1", (long long)N * M);
+    if (Tmax < 1) FAIL(c, LRCN_EINVAL, "Tmax=%d must be >= 1", Tmax);
+    const int V = c->V;
+    for (int m = 0; m < M; ++m) {
+        if (lens[m] < 1 || lens[m] > LRCN_MAX_T || lens[m] > Tmax) FAIL(c, LRCN_EINVAL, "lens[%d]=%d outside [1, min(Tmax=%d, %d)]", m, lens[m], Tmax, LRCN_MAX_T);
+        for (int t = 0; t < lens[m]; ++t)
+            if ((unsigned)tokens[(int64_t)t * M + m] >= (unsigned)V) FAIL(c, LRCN_EINVAL, "token (t=%d, m=%d) = %d outside [0, V=%d)", t, m, tokens[(int64_t)t * M + m], V);
+    }
+    if (pairs)
+        for (int q = 0; q < P; ++q)
+            if ((unsigned)pair_img[q] >= (unsigned)N || (unsigned)pair_cap[q] >= (unsigned)M)
+                FAIL(c, LRCN_EINVAL, "pair %d = (%d, %d) outside N=%d x M=%d", q, pair_img[q], pair_cap[q], N, M);
+    const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, maxB = c->maxB;
+    const size_t es = c->esz;
+    hipStream_t st = c->stream;
+    struct DetScope {   // every GEMM of the call in its ordered form (no float-atomic split-K): a call's scores repeat bit for bit
+        lrcn_ctx *c;
+        bool prev;
+        ~DetScope() { c->opt_det = prev; }
+    } det{c, c->opt_det};
+    c->opt_det = true;
+
+    // ---- host plan: captions sorted by length (descending, stable); caption step t holds the Ma(t) longest, at rows off[t] .. off[t] + Ma(t)
+    std::vector<int> ord(M), rank(M);
+    for (int m = 0; m < M; ++m) ord[m] = m;
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return lens[a] > lens[b]; });
+    for (int j = 0; j < M; ++j) rank[ord[j]] = j;
+    const int Smax = lens[ord[0]] + 1;
+    std::vector<int64_t> off(Smax + 1, 0);
+    std::vector<int> Ma(Smax);
+    for (int t = 0, j = M; t < Smax; ++t) {
+        while (j > 0 && lens[ord[j - 1]] + 1 <= t) --j;
+        Ma[t] = j;
+        off[t + 1] = off[t] + j;
+    }
+    const int64_t Ptot = off[Smax];
+    const int64_t Rtot = pairs ? P : (int64_t)N * M;
+    // ints: caption-step inputs and targets (each padded by max_B entries: the cell epilogue's GEMM reads up to 256 rows of indices), the
+    // sorted order, and for pairs their rows' image, sorted caption and output slot.  A matrix row r is image r % N of sorted caption r / N:
+    // its maps are made per piece on the device (k_score_matrix_rows)
+    const int64_t n_in = Ptot + maxB, n_int = 2 * n_in + M + (pairs ? 3 * (int64_t)P : 0);
+    std::vector<int32_t> hi((size_t)n_int, 0);
+    int32_t *h_in = hi.data(), *h_tg = h_in + n_in, *h_ord = h_tg + n_in, *h_img = h_ord + M, *h_cap = h_img + (pairs ? P : 0),
+            *h_out = h_cap + (pairs ? P : 0);
+    for (int t = 0; t < Smax; ++t)
+        for (int j = 0; j < Ma[t]; ++j) {
+            const int m = ord[j];
+            h_in[off[t] + j] = t == 0 ? LRCN_BOS : tokens[(int64_t)(t - 1) * M + m];
+            h_tg[off[t] + j] = t < lens[m] ? tokens[(int64_t)t * M + m] : LRCN_EOS;
+        }
+    for (int j = 0; j < M; ++j) h_ord[j] = ord[j];
+    if (pairs) {
+        std::vector<int> q(P);
+        for (int i = 0; i < P; ++i) q[i] = i;
+        std::stable_sort(q.begin(), q.end(), [&](int a, int b) { return rank[pair_cap[a]] < rank[pair_cap[b]]; });
+        for (int i = 0; i < P; ++i) {
+            h_img[i] = pair_img[q[i]];
+            h_cap[i] = rank[pair_cap[q[i]]];
+            h_out[i] = q[i];
+        }
+    }
+    auto steps_of = [&](int64_t row) { return lens[ord[pairs ? h_cap[row] : (int)(row / N)]] + 1; };
+    // ---- device arena: the regions of fixed size first, at fixed offsets (A2's K padding must hold zeros; the ride-along rows of the
+    // epilogue routes read stale target ids, which must be valid), then the regions whose size depends on the call
+    const int64_t ldA2 = c->ldh + c->ldH2;
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t b_A2 = al(es * (size_t)maxB * ldA2), b_i32 = al(sizeof(int32_t) * maxB), b_acc = al(sizeof(double) * maxB),
+                 b_terms = al(sizeof(double) * (maxB + 1)), b_int = al(sizeof(int32_t) * n_int), b_P = al(es * Ptot * c->ldh),
+                 b_U2 = al(sizeof(float) * (size_t)N * 4 * H2);
+    const size_t fixed = 2 * b_A2 + 4 * b_i32 + b_acc + b_terms, need = fixed + b_int + b_P + b_U2;
+    HIPCHK(c, hipStreamSynchronize(st));   // a previous score call may still read the arena
+    if (need > c->sc_bytes) {
+        if (c->sc_arena) (void)hipFree(c->sc_arena);
+        c->sc_arena = nullptr;
+        c->sc_bytes = 0;
+        if (hipMalloc(&c->sc_arena, need) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipMalloc(%zu) for caption scoring failed", need);
+        c->sc_bytes = need;
+    }
+    char *ap = reinterpret_cast<char *>(c->sc_arena);
+    void *A2buf[2] = {ap, ap + b_A2}; ap += 2 * b_A2;
+    int32_t *tgt_row = reinterpret_cast<int32_t *>(ap); ap += b_i32;
+    int32_t *m_img = reinterpret_cast<int32_t *>(ap), *m_cap = m_img + b_i32 / 4, *m_out = m_cap + b_i32 / 4; ap += 3 * b_i32;
+    double *acc = reinterpret_cast<double *>(ap); ap += b_acc;
+    double *terms = reinterpret_cast<double *>(ap); ap += b_terms;
+    int32_t *d_in = reinterpret_cast<int32_t *>(ap), *d_tg = d_in + n_in, *d_ord = d_tg + n_in, *d_img = d_ord + M,
+            *d_cap = d_img + (pairs ? P : 0), *d_out = d_cap + (pairs ? P : 0);
+    ap += b_int;
+    void *Pst = ap; ap += b_P;
+    float *U2 = reinterpret_cast<float *>(ap);
+    // every call: zero operands (K padding, first-step h2) and target ids
+    HIPCHK(c, hipMemsetAsync(c->sc_arena, 0, 2 * b_A2 + b_i32, st));
+    HIPCHK(c, hipMemcpyAsync(d_in, hi.data(), sizeof(int32_t) * n_int, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the host arrays are read before they go out of scope
+
+    int r = decode_tables_alloc(c);
+    if (r) return r;
+    if ((r = prepare_weights(c, p, false, false, false, false, true))) return r;   // + the interleaved recurrent copies and dec_W2c
+    // ---- caption side: T1, then LSTM-1 and P_t = h1_t Wproj over blocks of max_B sorted captions
+    GEMM(c, dt, c->WeT, c->ldE, c->W1x, c->ldX1, c->dec_T1, 4 * H1, V, 4 * H1, E, p[1], true);
+    for (int j0 = 0; j0 < M; j0 += maxB) {
+        const int Bc = std::min(maxB, M - j0);
+        const bool epi = decode_tables_on(c, Bc);
+        void *h1c = c->st_h1, *h1n = c->dec_A1;
+        float *c1c = c->st_f32[1], *c1n = c->st2_f32[1];
+        HIPCHK(c, hipMemsetAsync(h1c, 0, es * (size_t)Bc * c->ldH1, st));
+        for (int t = 0; t < Smax && Ma[t] > j0; ++t) {
+            const int Ba = std::min(Bc, Ma[t] - j0);
+            const int32_t *tok = d_in + off[t] + j0;
+            if (epi) {
+                if ((r = decode_gates_epi(c, h1c, c->ldH1, c->W1h_gi, H1, c->dec_T1, std::max(Ba, 256), H1, t ? c1c : nullptr, nullptr, c1n, h1n,
+                                          c->ldH1, tok)))
+                    return r;
+            } else {
+                k_score_gather_rows(st, c->dec_T1, 4 * H1, tok, Ba, c->st_g);
+                if (t) GEMM(c, dt, h1c, c->ldH1, c->W1h, c->ldH1, c->st_g, 4 * H1, Ba, 4 * H1, H1, nullptr, true, true);
+                k_lstm_fwd(st, dt, c->st_g, 4 * H1, t ? c1c : nullptr, Ba, H1, c->st_a, c->ld4H1, c1n, h1n, c->ldH1, nullptr);
+            }
+            GEMM(c, dt, h1n, c->ldH1, c->Wpd, c->ldH1, boff(Pst, (off[t] + j0) * c->ldh, es), c->ldh, Ba, h, H1, nullptr, false);   // lrcn.jl:544
+            std::swap(h1c, h1n);
+            std::swap(c1c, c1n);
+        }
+    }
+    // ---- image side: U2 = [0 | x_cnn] W2x + b2 per image (x_cnn = feats Wcnn, lrcn.jl:558), in blocks of max_B images
+    for (int n0 = 0; n0 < N; n0 += maxB) {
+        const int nc = std::min(maxB, N - n0);
+        k_transpose(st, dt, 1, feats + n0, N, LRCN_CNNOUT, nc, c->F, LRCN_CNNOUT, 0);
+        GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, nc, h, LRCN_CNNOUT, nullptr, true);
+        HIPCHK(c, hipMemsetAsync(c->dec_Aimg, 0, es * (size_t)nc * c->ldH2, st));
+        DropSpec none{};
+        k_concat_x2(st, dt, c->dec_Aimg, c->ldH2, c->dxcnn, c->ldh, 1, nc, h, h, none);
+        GEMM(c, dt, c->dec_Aimg, c->ldH2, c->W2x, c->ldH2, U2 + (int64_t)n0 * 4 * H2, 4 * H2, nc, 4 * H2, H2, p[3], true);
+    }
+    // ---- pair side: pieces of at most max_B caption-major rows
+    const int nrec = 2 * ((V + 255) / 256);
+    if (!c->smax_part) DALLOC(c, c->smax_part, sizeof(float) * (size_t)maxB * nrec * SMAX_REC);
+    for (int64_t r0 = 0; r0 < Rtot; r0 += maxB) {
+        const int R = (int)std::min<int64_t>(maxB, Rtot - r0);
+        const bool epi = decode_tables_on(c, R), fused = score_fused_on(c, R);
+        const int Sp = steps_of(r0);
+        void *A2c = A2buf[0], *A2n = A2buf[1];
+        float *c2c = c->st_f32[3], *c2n = c->st2_f32[3];
+        const int32_t *img = d_img + r0, *cap = d_cap + r0, *outi = d_out + r0;
+        if (!pairs) {
+            k_score_matrix_rows(st, r0, R, N, d_ord, m_img, m_cap, m_out);
+            img = m_img; cap = m_cap; outi = m_out;
+        }
+        HIPCHK(c, hipMemsetAsync(acc, 0, sizeof(double) * R, st));
+        int Rt = R;
+        for (int t = 0; t < Sp; ++t) {
+            while (Rt > 0 && steps_of(r0 + Rt - 1) <= t) --Rt;
+            // rows past Rt (inactive for good) ride along up to 256 in the epilogue routes: their operands are finite, their results unread
+            const int Mg = epi ? std::max(Rt, 256) : Rt, Ml = fused ? std::max(Rt, 256) : Rt;
+            k_score_prep(st, dt, A2c, ldA2, boff(Pst, off[t] * c->ldh, es), c->ldh, cap, Rt, h, t == 0 ? H2 : 0, c->ldh, d_tg + off[t], tgt_row);
+            void *h2n = boff(A2n, c->ldh, es);
+            if (epi) {
+                if ((r = decode_gates_epi(c, A2c, ldA2, c->dec_W2c, (int)ldA2, U2, Mg, H2, t ? c2c : nullptr, nullptr, c2n, h2n, ldA2, img))) return r;
+            } else {
+                k_score_gather_rows(st, U2, 4 * H2, img, Rt, c->st_g);
+                GEMM(c, dt, A2c, ldA2, c->W2x, c->ldH2, c->st_g, 4 * H2, Rt, 4 * H2, h, nullptr, true, true);   // P_t: the left h columns of W2x
+                if (t) GEMM(c, dt, boff(A2c, c->ldh, es), ldA2, c->W2h, c->ldH2, c->st_g, 4 * H2, Rt, 4 * H2, H2, nullptr, true, true);
+                k_lstm_fwd(st, dt, c->st_g, 4 * H2, t ? c2c : nullptr, Rt, H2, c->st_a, c->ld4H2, c2n, h2n, ldA2, nullptr);
+            }
+            if (fused) {
+                GemmArgs g{};
+                g.dtype = dt;
+                g.A = h2n; g.lda = ldA2;
+                g.B = c->Wod; g.ldb = c->ldH2;
+                g.M = Ml; g.N = V;
+                g.K = (int)round_up64(H2, 64);
+                g.bias = p[8];
+                g.a_mode = GEMM_A_PLAIN;
+                g.out_mode = GEMM_OUT_SMAX_PICK;
+                g.zero_page = c->zero_page;
+                g.smax.part = c->smax_part; g.smax.nrec = nrec; g.smax.tgt = tgt_row;
+                hipError_t e = launch_gemm_8p(st, g);
+                if (e != hipSuccess) FAIL(c, LRCN_EHIP, "score step (logits GEMM + log-softmax pick epilogue): %s", hipGetErrorString(e));
+                if (!k_score_pick_merge(st, c->smax_part, nrec, Rt, acc)) FAIL(c, LRCN_EINVAL, "score merge: %d records per row", nrec);
+            } else {
+                GEMM(c, dt, h2n, ldA2, c->Wod, c->ldH2, c->st_logits, c->ldV, Rt, V, H2, p[8], true);   // lrcn.jl:550
+                k_softmax_xent(st, dt, c->st_logits, c->ldV, tgt_row, Rt, V, 1.0f, terms + maxB, nullptr, 0, terms);
+                k_score_acc(st, terms, Rt, acc);
+            }
+            std::swap(A2c, A2n);
+            std::swap(c2c, c2n);
+        }
+        k_score_scatter(st, acc, outi, R, scores);
+    }
+    KCHK(c, "score");
+    return LRCN_OK;
+}
+
 }  // namespace
 
 // =====================================================================================================
@@ -1280,6 +1491,7 @@ void lrcn_destroy(lrcn_ctx *c) {
     DeviceGuard dg(c);
     (void)hipDeviceSynchronize();
     for (void *p : c->allocs) (void)hipFree(p);
+    if (c->sc_arena) (void)hipFree(c->sc_arena);
     for (auto &e : c->grad_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->wg_fork)
@@ -2192,6 +2404,20 @@ int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, 
     memcpy(out_len, pin + nb_tok, nb_n);
     if (out_logp) memcpy(out_logp, pin + nb_tok + nb_n, nb_n);
     return LRCN_OK;
+}
+
+// Caption scoring (include/lrcn_score.h; paper section 5.1 / Table 2 -- not in lrcn.jl): see score_impl
+int lrcn_score_matrix(lrcn_ctx *c, const float *const p[9], const float *feats, int N, const int32_t *tokens, const int *lens, int M, int Tmax,
+                      float *scores) {
+    return score_impl(c, p, feats, N, tokens, lens, M, Tmax, nullptr, nullptr, 0, scores);
+}
+int lrcn_score_pairs(lrcn_ctx *c, const float *const p[9], const float *feats, int N, const int32_t *tokens, const int *lens, int M, int Tmax,
+                     const int32_t *pair_img, const int32_t *pair_cap, int P, float *scores) {
+    if (!pair_img || !pair_cap) {
+        if (c) c->err = "null argument";
+        return LRCN_EINVAL;
+    }
+    return score_impl(c, p, feats, N, tokens, lens, M, Tmax, pair_img, pair_cap, P, scores);
 }
 
 // ------------------------------------------------------------------------------------------- VGG

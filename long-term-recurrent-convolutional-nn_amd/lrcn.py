@@ -475,6 +475,47 @@ def sample_captions(ctx, param, feats, index_to_word, nsamples, nword, temperatu
     return res
 
 
+def _score_args(feats, captions, normalize):
+    """captions (lists of 0-based ids, no bos / eos) -> host tokens [Tmax][M], lens [M]; feats normalised per image if asked (lrcn.jl:597)."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))
+    M = len(captions)
+    lens = np.array([len(c) for c in captions], np.int32)
+    Tmax = max(1, int(lens.max())) if M else 1
+    tok = np.zeros((Tmax, max(M, 1)), np.int32)
+    for m, cap in enumerate(captions):
+        tok[:len(cap), m] = cap
+    return feats, np.ascontiguousarray(tok), lens, Tmax
+
+
+def score_matrix(ctx, param, feats, captions, normalize=False):
+    """s(n, m) = log p(caption m | image n) summed over its words and eos (lrcn_score_matrix, include/lrcn_score.h; paper section 5.1):
+    feats N x 4096, captions M lists of 0-based token ids without bos / eos -> numpy float32 N x M."""
+    feats, tok, lens, Tmax = _score_args(feats, captions, normalize)
+    N, M = feats.shape[0], len(captions)
+    out = torch.empty(N * max(M, 1), dtype=torch.float32, device=feats.device)
+    ctx._call("lrcn_score_matrix", _p9(param), _ptr(feats), N, tok.ctypes.data_as(C.POINTER(C.c_int32)),
+              lens.ctypes.data_as(C.POINTER(C.c_int)), M, Tmax, C.c_void_p(out.data_ptr()))
+    ctx.sync()
+    return out.cpu().numpy().reshape(M, N).T.copy()
+
+
+def score_pairs(ctx, param, feats, captions, pair_img, pair_cap, normalize=False):
+    """score_matrix at the P given (image, caption) pairs only (lrcn_score_pairs) -> numpy float32 [P]."""
+    feats, tok, lens, Tmax = _score_args(feats, captions, normalize)
+    pi = np.ascontiguousarray(pair_img, dtype=np.int32)
+    pc = np.ascontiguousarray(pair_cap, dtype=np.int32)
+    if pi.shape != pc.shape or pi.ndim != 1:
+        raise LrcnError("pair_img and pair_cap must be 1-D and of one length")
+    out = torch.empty(max(len(pi), 1), dtype=torch.float32, device=feats.device)
+    ctx._call("lrcn_score_pairs", _p9(param), _ptr(feats), feats.shape[0], tok.ctypes.data_as(C.POINTER(C.c_int32)),
+              lens.ctypes.data_as(C.POINTER(C.c_int)), len(captions), Tmax, pi.ctypes.data_as(C.POINTER(C.c_int32)),
+              pc.ctypes.data_as(C.POINTER(C.c_int32)), len(pi), C.c_void_p(out.data_ptr()))
+    ctx.sync()
+    return out.cpu().numpy()[:len(pi)].copy()
+
+
 def generate(ctx, param, feat, index_to_word, nword, beam_width, normalize=False):
     """generate (lrcn.jl:585-642): caption text "w1 w2 ... ." -- words after bos up to the first eos (:634-640)."""
     if normalize:

@@ -6,6 +6,7 @@
         --features train_feats.npz val_feats.npz --savefile m.npz
     python tools/lrcn.py --coco --loadfile m.npz --generate 30 --beam_width 5 --datafiles ... --features ...
     python tools/lrcn.py --cnn --model imagenet-vgg-verydeep-16.mat --loadfile m.npz --generate 30 photo.jpg
+    python tools/lrcn.py --flickr --loadfile m.npz --retrieval --capnumber 1000 --datafiles results_20130124.token --features ...
     python tools/lrcn.py --cnn --model vgg.mat --extfeatures --imagedir train2014 --prefix COCO_train2014_ --datafiles ...
     python tools/lrcn.py --coco --train --gpus 8 --batchsize 256 --datafiles ... --features ...           # data-parallel: 8 x 32 rows
     python tools/lrcn.py --coco --train --gpus 8 --cnn --model vgg.mat --imagedir train2014 --prefix COCO_train2014_ --datafiles ...   # from images
@@ -59,6 +60,12 @@ def build_parser():
     p.add_argument("--sample", type=int, default=0, help="--generate: draw this many captions per image instead of beam search (0 = beam search)")
     p.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature (0 = greedy)")
     p.add_argument("--topk", type=int, default=0, help="--sample: draw among the k most probable words only (0 = all)")
+    p.add_argument("--retrieval", action="store_true",
+                   help="image-caption retrieval (paper section 5.1 / Table 2): score --capnumber images of the --generate split, drawn as --generate "
+                        "draws them (a permutation seeded by --seed), against all their captions; R@1/5/10 and Medr both ways, "
+                        "<out>/retrieval.json and <out>/scores.npy")
+    p.add_argument("--retrieval_norm", default="mean", choices=["mean", "sum"],
+                   help="--retrieval: rank by log-likelihood per predicted token (mean) or in total (sum)")
     p.add_argument("--dropout", type=float, default=0.4, help="pdrop of train! (lrcn.jl:227)")
     p.add_argument("--features", nargs="+", default=[], help=".npz feature dictionaries: train [val] (formats.save_features)")
     p.add_argument("--imagedir", default=".", help="directory of the images for --extfeatures")
@@ -154,7 +161,7 @@ def main(argv=None):
         raise SystemExit("--hidden takes two sizes, the second even (LRCN-2f, lrcn.jl:496-504)")
     H1, H2 = o.hidden
     gen_chunk = 256  # images decoded together by the batched beam search (1280 hypothesis rows at beam 5: the decode GEMMs fill the chip)
-    ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, (o.sample or o.beam_width) * (gen_chunk if o.generate > 0 else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
+    ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, (o.sample or o.beam_width) * (gen_chunk if o.generate > 0 or o.retrieval else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
                     max_images=max(o.batchsize, 256 if o.train else 1) if o.cnn else 0)   # training: room for the crops of several batches per forward
     param = L.initweights(ctx, seed=o.seed if o.seed > 0 else 42) if host_model is None else L.model_from_arrays(host_model)
     say("LSTM is initialized")
@@ -249,6 +256,36 @@ def main(argv=None):
                     out.write(cap.caption_text(toks, idx2word) + "\n")
         if smp is not None:
             smp.close()
+        return 0
+
+    # ---------------------------------------------------------------- retrieval (paper section 5.1 / Table 2; not in lrcn.jl)
+    if o.retrieval:
+        import json
+        from lrcn_amd import retrieval
+        split = lists[2] if o.flickr and len(lists) > 2 else lists[min(1, len(lists) - 1)]   # the split and table of --generate
+        table = feats[min(1, len(feats) - 1)] if o.coco else feats[0]
+        ids = []
+        for k in rng.permutation(len(split)):
+            i = split[k][0][0]
+            if i not in ids:
+                ids.append(i)
+            if len(ids) == o.capnumber:
+                break
+        pos = {i: n for n, i in enumerate(ids)}
+        caps, img_of = [], []
+        for (i, words), n in split:   # every caption of those images that the model can score (1 .. 28 words, lrcn.jl:353)
+            if i in pos and 1 <= n <= 28:
+                caps.append([vocab.get(w, cap.UNK) - 1 for w in words])
+                img_of.append(pos[i])
+        s = L.score_matrix(ctx, param, feature_rows(table, ids), caps)
+        lens = [len(c) for c in caps]
+        res = retrieval.metrics(s, img_of, norm=o.retrieval_norm, lens=lens)
+        print(retrieval.format_line("Caption to Image", res["caption_to_image"]))
+        print(retrieval.format_line("Image to Caption", res["image_to_caption"]))
+        os.makedirs(o.out, exist_ok=True)
+        np.save(os.path.join(o.out, "scores.npy"), s)
+        with open(os.path.join(o.out, "retrieval.json"), "w") as fh:
+            json.dump(dict(res, norm=o.retrieval_norm, image_ids=[int(i) for i in ids], captions=len(caps), img_of_caption=img_of, lens=lens), fh)
         return 0
 
     # ---------------------------------------------------------------- extract features (lrcn.jl:162-172, 190-221)
