@@ -111,18 +111,18 @@ struct lrcn_ctx {
     int cur_B = 0;  // rows of the loss / lossgradient call in flight (the "beside the convolutions" GEMM hints apply from 256 rows)
     // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
     float *st_f32[4] = {nullptr, nullptr, nullptr, nullptr};   // h1,c1,h2,c2 [B][H]
-    float *st2_f32[4] = {nullptr, nullptr, nullptr, nullptr};  // ping-pong for the beam gather
+    // the other buffer of each state pair: the target of the single-image beam's gather and of the batched decode's k_gather_state, and
+    // the c(t) output of the batched decode's cell epilogues (decode_step swaps the pairs after a step)
+    float *st2_f32[4] = {nullptr, nullptr, nullptr, nullptr};
     void *st_h1 = nullptr, *st_h2 = nullptr, *st_x = nullptr, *st_x2 = nullptr, *st_a = nullptr;
     float *st_g = nullptr, *st_logits = nullptr, *st_prob = nullptr, *st_io = nullptr, *st_topv = nullptr;
     int32_t *st_topi = nullptr, *st_parent = nullptr;
-    // batched beam search (lrcn_beam_search_batch): token histories (ping-pong), bookkeeping, results -- all on the device
+    // the batched decode (decode_begin / decode_step; lrcn_beam_search_batch and lrcn_sample_batch): token histories (ping-pong for the
+    // beam's reorder; the sampler's rows keep bs_seq[0]), next input tokens, done flags and counter, results -- all on the device.  The
+    // sampler keeps its lengths in bs_res_len and its log-likelihoods in bs_p; bs_res_tok / bs_res_p are the beam's alone
     int32_t *bs_seq[2] = {nullptr, nullptr}, *bs_last = nullptr, *bs_done = nullptr, *bs_ndone = nullptr, *bs_res_tok = nullptr,
             *bs_res_len = nullptr;
     float *bs_p = nullptr, *bs_res_p = nullptr;
-    // lrcn_sample_batch (reuses the beam buffers above): what decode_logits_smax leaves for the sampler's own merge kernel --
-    // 0 = the beam's top-K merge, 1 = GEMM_OUT_SMAX_TOPK records only, 2 = GEMM_OUT_SMAX_GUMBEL records (draw parameters in dec_gumbel)
-    int dec_draw = 0;
-    SmaxEpi dec_gumbel{};
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;
@@ -1011,9 +1011,10 @@ int step_internal(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d
     return LRCN_OK;
 }
 
-// The same step for the batched beam decode, on the concatenated buffers: st_xh1 = [x | h1], st_xh2 = [x2 | h2] (T, the
-// h blocks already hold this step's input states), one GEMM per LSTM against W1cat / W2cat.  LRCN-1f: st_xh1 = [emb | x_cnn | h1]
-// (the caller wrote the x_cnn columns once: they do not change during a decode).
+// The batched decode (lrcn_beam_search_batch, lrcn_sample_batch) runs the same step on the concatenated buffers: st_xh1 = [x | h1],
+// st_xh2 = [x2 | h2] (T, the h blocks already hold this step's input states), one GEMM per LSTM against W1cat / W2cat.  LRCN-1f:
+// st_xh1 = [emb | x_cnn | h1] (decode_begin writes the x_cnn columns once: they do not change during a decode).  Its routes below
+// (decode_route) are chosen once per call; decode_begin and decode_step drive them.
 // The batched decode step with the cell math in the gate GEMM's epilogue (gemm_8p.hip GEMM_OUT_LSTM_FWD; round 5): from 256 hypotheses
 // the gate GEMM is a chip-filling contraction (5120 x 4000 x 2048 at 1024 images x 5 beams), and the f32 pre-activations it used to write
 // for a separate cell kernel -- 82 MB out and back per layer and step, plus the kernel -- never leave the workgroup.  The concatenated
@@ -1058,30 +1059,51 @@ bool decode_smax_on(const lrcn_ctx *c, int B, int K) {
     const char *k = getenv("LRCN_DECODE_SMAX");  // read per call (the tests switch it inside one process)
     return !(k && k[0] == '0') && c->dt == GEMM_T_BF16 && B >= 256 && K < SMAX_KC && c->V >= 256 && !(c->V & 3) && c->H2 > 64;  // (>= 2 K-tiles)
 }
-int decode_logits_smax(lrcn_ctx *c, const void *hT, int64_t ldh, const float *bias, int B, int K) {
-    const int V = c->V, H2 = c->H2, nrec = 2 * ((V + 255) / 256);
+// The same logits GEMM with any of the record epilogues (GEMM_OUT_SMAX_TOPK / _GUMBEL / _PICK) for M rows of h: every 128 columns of a row
+// reduce to one record of smax_part [M][smax_nrec][SMAX_REC] (allocated on first use, max_B rows).  e: the out-mode's own SmaxEpi fields
+// (GUMBEL: the draw parameters, PICK: the target columns); part and nrec are filled in here.
+int smax_nrec(const lrcn_ctx *c) { return 2 * ((c->V + 255) / 256); }
+int logits_records(lrcn_ctx *c, const void *hT, int64_t ldh, const float *bias, int M, int out_mode, const SmaxEpi &e) {
+    const int nrec = smax_nrec(c);
     if (!c->smax_part) DALLOC(c, c->smax_part, sizeof(float) * (size_t)c->maxB * nrec * SMAX_REC);
     GemmArgs g{};
     g.dtype = c->dt;
     g.A = hT; g.lda = ldh;
     g.B = c->Wod; g.ldb = c->ldH2;
-    g.M = B; g.N = V;
-    g.K = (int)round_up64(H2, 64);
-    if (g.K > ldh || g.K > c->ldH2) FAIL(c, LRCN_EINVAL, "decode logits: K = %d exceeds the operand rows", g.K);
+    g.M = M; g.N = c->V;
+    g.K = (int)round_up64(c->H2, 64);
+    if (g.K > ldh || g.K > c->ldH2) FAIL(c, LRCN_EINVAL, "logits GEMM: K = %d exceeds the operand rows", g.K);
     g.bias = bias;
     g.a_mode = GEMM_A_PLAIN;
-    g.out_mode = GEMM_OUT_SMAX_TOPK;
+    g.out_mode = out_mode;
     g.zero_page = c->zero_page;
+    g.smax = e;
     g.smax.part = c->smax_part; g.smax.nrec = nrec;
-    if (c->dec_draw == 2) {   // the sampled decode: each record keeps its Gumbel-max winner instead of a top-K list
-        g.out_mode = GEMM_OUT_SMAX_GUMBEL;
-        g.smax.temp = c->dec_gumbel.temp; g.smax.key0 = c->dec_gumbel.key0; g.smax.key1 = c->dec_gumbel.key1;
-        g.smax.current = c->dec_gumbel.current; g.smax.S = c->dec_gumbel.S;
+    hipError_t err = launch_gemm_8p(c->stream, g);
+    if (err != hipSuccess) FAIL(c, LRCN_EHIP, "logits GEMM + softmax records epilogue (out_mode %d): %s", out_mode, hipGetErrorString(err));
+    return LRCN_OK;
+}
+
+// Where the logits of a batched decode step go, fixed by the caller for the whole call:
+//   LOGITS   f32 logits in st_logits [B][ldV] (every route without decode_smax_on)
+//   TOPK     GEMM_OUT_SMAX_TOPK records merged to the K best columns of every row in st_topi / st_topv (the beam)
+//   RECORDS  GEMM_OUT_SMAX_TOPK records only, left in smax_part (the sampler at top_k >= 1 merges them itself)
+//   GUMBEL   GEMM_OUT_SMAX_GUMBEL records, left in smax_part, with the draw parameters `draw` (the sampler at top_k = 0, which sets
+//            draw.current before every step)
+struct DecodeTail {
+    enum Kind { LOGITS, TOPK, RECORDS, GUMBEL } kind = LOGITS;
+    int K = 0;
+    SmaxEpi draw{};
+};
+int decode_logits(lrcn_ctx *c, const float *const p[9], const void *hT, int64_t ldh, int B, const DecodeTail &t) {
+    if (t.kind == DecodeTail::LOGITS) {
+        GEMM(c, c->dt, hT, ldh, c->Wod, c->ldH2, c->st_logits, c->ldV, B, c->V, c->H2, p[8], true);   // lrcn.jl:550
+        return LRCN_OK;
     }
-    hipError_t e = launch_gemm_8p(c->stream, g);
-    if (e != hipSuccess) FAIL(c, LRCN_EHIP, "decode step (logits GEMM + softmax / top-K epilogue): %s", hipGetErrorString(e));
-    if (c->dec_draw) return LRCN_OK;   // lrcn_sample_batch merges the records itself
-    if (!k_softmax_topk_merge(c->stream, c->smax_part, nrec, B, K, c->st_topi, c->st_topv)) FAIL(c, LRCN_EINVAL, "softmax / top-K merge: K = %d, %d records", K, nrec);
+    int r = logits_records(c, hT, ldh, p[8], B, t.kind == DecodeTail::GUMBEL ? GEMM_OUT_SMAX_GUMBEL : GEMM_OUT_SMAX_TOPK, t.draw);
+    if (r || t.kind != DecodeTail::TOPK) return r;
+    if (!k_softmax_topk_merge(c->stream, c->smax_part, smax_nrec(c), B, t.K, c->st_topi, c->st_topv))
+        FAIL(c, LRCN_EINVAL, "softmax / top-K merge: K = %d, %d records", t.K, smax_nrec(c));
     return LRCN_OK;
 }
 
@@ -1122,77 +1144,113 @@ int decode_tables_build(lrcn_ctx *c, const float *const p[9], int N, int K) {
     KCHK(c, "decode tables");
     return LRCN_OK;
 }
-int step_decode_tables(lrcn_ctx *c, const float *const p[9], int B, const int32_t *parent, bool first, int smax_K) {
-    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
+
+// The route of a batched decode of R rows, chosen once per call.  K_records: the top-K width its logits epilogue would keep (the beam's K,
+// the sampler's top_k).
+struct DecodeRoute {
+    bool epi, smax, tables;
+};
+DecodeRoute decode_route(const lrcn_ctx *c, int R, int K_records) {
+    const bool epi = decode_epi_on(c, R);
+    return DecodeRoute{epi, epi && decode_smax_on(c, R, K_records), epi && decode_tables_on(c, R)};
+}
+
+// Everything a batched decode of N images x per_image rows (row r belongs to image r / per_image) does before its first step: the route's
+// weight copies, input = input * param[end-3] per image (lrcn.jl:611) repeated for the image's rows, zero states and [x | h] operands (their
+// K padding included), LRCN-1f's x_cnn columns of [emb | x_cnn | h1] (constant over the decode: a row never changes image), the tables.
+// The caller's own bookkeeping (histories, done flags, st_parent) follows it.
+int decode_begin(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int per_image, const DecodeRoute &rt) {
+    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h, R = N * per_image;
+    hipStream_t st = c->stream;
+    int r = rt.tables ? decode_tables_alloc(c) : LRCN_OK;
+    if (r || (r = prepare_weights(c, p, false, !rt.tables, false, rt.epi, rt.tables))) return r;
+    k_transpose(st, dt, 1, feats, N, LRCN_CNNOUT, N, c->F, LRCN_CNNOUT, 0);
+    GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, N, h, LRCN_CNNOUT, nullptr, true);
+    k_repeat_rows(st, GEMM_T_F32, c->dxcnn, c->ldh, N, per_image, h, c->xcnn);
+    const int Hs[4] = {H1, H1, H2, H2};
+    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemsetAsync(c->st_f32[i], 0, sizeof(float) * (size_t)R * Hs[i], st));
+    HIPCHK(c, hipMemsetAsync(c->st_xh1, 0, c->esz * (size_t)R * c->ldXH1, st));  // zero initial h1 / h2 (T copies) and K padding
+    HIPCHK(c, hipMemsetAsync(c->st_xh2, 0, c->esz * (size_t)R * c->ldXH2, st));
+    if (c->nl == 1) {
+        DropSpec none{};
+        k_concat_x2(st, dt, c->st_xh1, c->ldXH1, c->xcnn, c->ldh, 1, R, c->E, h, none);
+    }
+    return rt.tables ? decode_tables_build(c, p, N, per_image) : LRCN_OK;
+}
+
+// The three forms of a batched decode step (lrcn.jl:650-651 for all B rows at once): the input token of row r is bs_last[r]; its states
+// continue row parent[r]'s (parent NULL: the first step, zero states).  Each ends in decode_logits.
+// Tables (decode_tables_on): the parents' h1 / h2 into the gate GEMMs' operands, the cell epilogues add the token's / image's table row.
+int step_tables(lrcn_ctx *c, const float *const p[9], int B, const int32_t *parent, const DecodeTail &tail) {
+    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h;
     const int64_t ldA2 = c->ldh + c->ldH2;
-    if (!first) k_decode_prep_h(c->stream, parent, B, c->st_h1, c->ldH1, H1, c->st_h2, c->ldH2, H2, c->dec_A1, c->ldH1, c->dec_A2, ldA2, c->ldh);
-    int r = decode_gates_epi(c, c->dec_A1, c->ldH1, c->W1h_gi, H1, c->dec_T1, B, H1, first ? nullptr : c->st_f32[1], parent, c->st2_f32[1], c->st_h1,
+    if (parent) k_decode_prep_h(c->stream, parent, B, c->st_h1, c->ldH1, H1, c->st_h2, c->ldH2, H2, c->dec_A1, c->ldH1, c->dec_A2, ldA2, c->ldh);
+    int r = decode_gates_epi(c, c->dec_A1, c->ldH1, c->W1h_gi, H1, c->dec_T1, B, H1, parent ? c->st_f32[1] : nullptr, parent, c->st2_f32[1], c->st_h1,
                              c->ldH1, c->bs_last);
     if (r) return r;
     GEMM(c, dt, c->st_h1, c->ldH1, c->Wpd, c->ldH1, c->dec_A2, ldA2, B, h, H1, nullptr, false);   // x = s[1] * w[end-4] (lrcn.jl:544) into A2's left block
-    r = decode_gates_epi(c, c->dec_A2, ldA2, c->dec_W2c, (int)ldA2, c->dec_U2, B, H2, first ? nullptr : c->st_f32[3], parent, c->st2_f32[3], c->st_h2,
+    r = decode_gates_epi(c, c->dec_A2, ldA2, c->dec_W2c, (int)ldA2, c->dec_U2, B, H2, parent ? c->st_f32[3] : nullptr, parent, c->st2_f32[3], c->st_h2,
                          c->ldH2, c->dec_img);
-    if (r) return r;
-    if (smax_K > 0) {
-        if ((r = decode_logits_smax(c, c->st_h2, c->ldH2, p[8], B, smax_K))) return r;
-    } else {
-        GEMM(c, dt, c->st_h2, c->ldH2, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
-    }
-    KCHK(c, "step_decode (tables)");
+    if (r || (r = decode_logits(c, p, c->st_h2, c->ldH2, B, tail))) return r;
+    KCHK(c, "decode step (tables)");
     return LRCN_OK;
 }
-
-int step_decode(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2, bool epi = false, const int32_t *parent = nullptr, bool first = false,
-                int smax_K = 0) {   // smax_K > 0 (epi only): the logits end as st_topi / st_topv (decode_logits_smax) instead of st_logits
-    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
+// Cell epilogue (decode_epi_on): one launch writes the embedding of every row's token and its parent's h1 / h2 into the [x | h] operands; the
+// epilogues write h(t) to st_h1 / st_h2 (never into the operand they are still reading) and c(t) to st2_f32[1] / [3].
+int step_epi(lrcn_ctx *c, const float *const p[9], int B, const int32_t *parent, const DecodeTail &tail) {
+    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h;
+    const bool two = c->nl == 2;
     hipStream_t st = c->stream;
-    void *h1T = boff(c->st_xh1, c->ldX1, c->esz), *h2T = boff(c->st_xh2, c->ldH2, c->esz);
-    if (epi) {
-        // the cell epilogue writes h(t) to st_h1 / st_h2 (never into the [x | h] operand it is still reading); k_gather_state rebuilds
-        // the h blocks of st_xh1 / st_xh2 from the f32 states for the next step
-        // (epi: cell states ping-pong st_f32[1] -> st2_f32[1] / st_f32[3] -> st2_f32[3], read through `parent`; the caller swaps the pairs)
-        int r = decode_gates_epi(c, c->st_xh1, c->ldXH1, c->W1cat, (int)c->ldX1 + H1, p[1], B, H1, first ? nullptr : c->st_f32[1], parent, c->st2_f32[1],
-                                 c->st_h1, c->ldH1);
-        if (r) return r;
-        if (c->nl == 1) {
-            if (smax_K > 0) {
-                if ((r = decode_logits_smax(c, c->st_h1, c->ldH1, p[8], B, smax_K))) return r;
-            } else {
-                GEMM(c, dt, c->st_h1, c->ldH1, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
-            }
-            KCHK(c, "step_decode (1 layer, cell epilogue)");
-            return LRCN_OK;
-        }
+    k_decode_prep(st, c->WeT, c->ldE, c->bs_last, parent, B, c->E, c->st_h1, c->ldH1, H1, two ? c->st_h2 : nullptr, c->ldH2, H2, c->st_xh1, c->ldXH1,
+                  c->ldX1, two ? c->st_xh2 : nullptr, c->ldXH2, c->ldH2);
+    int r = decode_gates_epi(c, c->st_xh1, c->ldXH1, c->W1cat, (int)c->ldX1 + H1, p[1], B, H1, parent ? c->st_f32[1] : nullptr, parent, c->st2_f32[1],
+                             c->st_h1, c->ldH1);
+    if (r) return r;
+    if (two) {
         GEMM(c, dt, c->st_h1, c->ldH1, c->Wpd, c->ldH1, c->st_xh2, c->ldXH2, B, h, H1, nullptr, false);
-        k_concat_x2(st, dt, c->st_xh2, c->ldXH2, c->xcnn, c->ldh, 1, B, h, h, d2);
-        r = decode_gates_epi(c, c->st_xh2, c->ldXH2, c->W2cat, (int)c->ldH2 + H2, p[3], B, H2, first ? nullptr : c->st_f32[3], parent, c->st2_f32[3],
+        DropSpec none{};
+        k_concat_x2(st, dt, c->st_xh2, c->ldXH2, c->xcnn, c->ldh, 1, B, h, h, none);
+        r = decode_gates_epi(c, c->st_xh2, c->ldXH2, c->W2cat, (int)c->ldH2 + H2, p[3], B, H2, parent ? c->st_f32[3] : nullptr, parent, c->st2_f32[3],
                              c->st_h2, c->ldH2);
         if (r) return r;
-        if (smax_K > 0) {
-            if ((r = decode_logits_smax(c, c->st_h2, c->ldH2, p[8], B, smax_K))) return r;
-        } else {
-            GEMM(c, dt, c->st_h2, c->ldH2, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
-        }
-        KCHK(c, "step_decode (cell epilogue)");
-        return LRCN_OK;
     }
+    if ((r = decode_logits(c, p, two ? c->st_h2 : c->st_h1, two ? c->ldH2 : c->ldH1, B, tail))) return r;
+    KCHK(c, "decode step (cell epilogue)");
+    return LRCN_OK;
+}
+// Plain: GEMM + cell kernel, the states updated in place (in st_f32 and the h blocks of st_xh1 / st_xh2).  It reads no parent: the caller
+// moves the states to their rows' parents after the step where they differ.
+int step_plain(lrcn_ctx *c, const float *const p[9], int B, const DecodeTail &tail) {
+    const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h;
+    hipStream_t st = c->stream;
+    void *h1T = boff(c->st_xh1, c->ldX1, c->esz), *h2T = boff(c->st_xh2, c->ldH2, c->esz);
+    DropSpec none{};
+    k_embed_gather(st, dt, c->WeT, c->ldE, c->bs_last, 1, B, c->E, none, c->st_xh1, c->ldXH1);  // lrcn.jl:650
     GEMM(c, dt, c->st_xh1, c->ldXH1, c->W1cat, c->ldXH1, c->st_g, 4 * H1, B, 4 * H1, (int)c->ldX1 + H1, p[1], true);
     k_lstm_fwd(st, dt, c->st_g, 4 * H1, c->st_f32[1], B, H1, c->st_a, c->ld4H1, c->st_f32[1], h1T, c->ldXH1, c->st_f32[0]);
-    if (c->nl == 1) {
-        GEMM(c, dt, h1T, c->ldXH1, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
-        KCHK(c, "step_decode (1 layer)");
-        return LRCN_OK;
+    if (c->nl == 2) {
+        GEMM(c, dt, h1T, c->ldXH1, c->Wpd, c->ldH1, c->st_xh2, c->ldXH2, B, h, H1, nullptr, false);
+        k_concat_x2(st, dt, c->st_xh2, c->ldXH2, c->xcnn, c->ldh, 1, B, h, h, none);
+        GEMM(c, dt, c->st_xh2, c->ldXH2, c->W2cat, c->ldXH2, c->st_g, 4 * H2, B, 4 * H2, (int)c->ldH2 + H2, p[3], true);
+        k_lstm_fwd(st, dt, c->st_g, 4 * H2, c->st_f32[3], B, H2, c->st_a, c->ld4H2, c->st_f32[3], h2T, c->ldXH2, c->st_f32[2]);
     }
-    GEMM(c, dt, h1T, c->ldXH1, c->Wpd, c->ldH1, c->st_xh2, c->ldXH2, B, h, H1, nullptr, false);
-    k_concat_x2(st, dt, c->st_xh2, c->ldXH2, c->xcnn, c->ldh, 1, B, h, h, d2);
-    GEMM(c, dt, c->st_xh2, c->ldXH2, c->W2cat, c->ldXH2, c->st_g, 4 * H2, B, 4 * H2, (int)c->ldH2 + H2, p[3], true);
-    k_lstm_fwd(st, dt, c->st_g, 4 * H2, c->st_f32[3], B, H2, c->st_a, c->ld4H2, c->st_f32[3], h2T, c->ldXH2, c->st_f32[2]);
-    GEMM(c, dt, h2T, c->ldXH2, c->Wod, c->ldH2, c->st_logits, c->ldV, B, V, H2, p[8], true);
-    KCHK(c, "step_decode");
+    int r = c->nl == 2 ? decode_logits(c, p, h2T, c->ldXH2, B, tail) : decode_logits(c, p, h1T, c->ldXH1, B, tail);
+    if (r) return r;
+    KCHK(c, "decode step");
+    return LRCN_OK;
+}
+// One step of a batched decode on the call's route; from the second step (current > 1) the tables and epilogue forms read the parents in
+// st_parent.  The epilogue forms wrote c(t) into the other buffer of each pair: swapped here, so st_f32 holds every route's current states.
+int decode_step(lrcn_ctx *c, const float *const p[9], int R, const DecodeRoute &rt, int current, const DecodeTail &tail) {
+    const int32_t *parent = current > 1 ? c->st_parent : nullptr;
+    int r = rt.tables ? step_tables(c, p, R, parent, tail) : rt.epi ? step_epi(c, p, R, parent, tail) : step_plain(c, p, R, tail);
+    if (r || !rt.epi) return r;
+    std::swap(c->st_f32[1], c->st2_f32[1]);
+    if (c->nl == 2) std::swap(c->st_f32[3], c->st2_f32[3]);
     return LRCN_OK;
 }
 
-// the context's pinned host staging buffer, grown to at least `need` bytes (decode results: see lrcn_beam_search_batch)
+// the context's pinned host staging buffer, grown to at least `need` bytes (decode results: see decode_results_to_host)
 int pin_reserve(lrcn_ctx *c, size_t need) {
     if (need > c->pin_bytes) {
         if (c->pin) (void)hipHostFree(c->pin);
@@ -1201,6 +1259,34 @@ int pin_reserve(lrcn_ctx *c, size_t need) {
         if (hipHostMalloc(&c->pin, need, hipHostMallocDefault) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipHostMalloc(%zu) failed", need);
         c->pin_bytes = need;
     }
+    return LRCN_OK;
+}
+
+// the early-exit test of a batched decode: have `target` images / rows finished (bs_ndone)?  One 4-byte read that waits for the stream.
+int decode_poll_done(lrcn_ctx *c, int target, bool &done) {
+    int32_t nd = 0;
+    HIPCHK(c, hipMemcpyAsync(&nd, c->bs_ndone, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    done = nd >= target;
+    return LRCN_OK;
+}
+
+// a batched decode's results -- tok [rows][Lh], len [rows], val [rows] on the device -- into the caller's host arrays (out_val may be NULL),
+// through the context's PINNED staging buffer: a device -> pageable-host copy above 64 KB takes HIP's pin-on-the-fly path (measured:
+// +16 ms per decode from 512 images, whose token block is 67 KB -- more than the 12.9 ms of kernels)
+int decode_results_to_host(lrcn_ctx *c, const int32_t *tok, const int32_t *len, const float *val, int rows, int Lh, int32_t *out_tok, int *out_len,
+                           float *out_val) {
+    const size_t nb_tok = sizeof(int32_t) * (size_t)rows * Lh, nb_n = sizeof(int32_t) * (size_t)rows;
+    int r = pin_reserve(c, nb_tok + 2 * nb_n);
+    if (r) return r;
+    unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
+    HIPCHK(c, hipMemcpyAsync(pin, tok, nb_tok, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pin + nb_tok, len, nb_n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pin + nb_tok + nb_n, val, nb_n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out_tok, pin, nb_tok);
+    memcpy(out_len, pin + nb_tok, nb_n);
+    if (out_val) memcpy(out_val, pin + nb_tok + nb_n, nb_n);
     return LRCN_OK;
 }
 
@@ -1356,8 +1442,6 @@ int score_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, 
         GEMM(c, dt, c->dec_Aimg, c->ldH2, c->W2x, c->ldH2, U2 + (int64_t)n0 * 4 * H2, 4 * H2, nc, 4 * H2, H2, p[3], true);
     }
     // ---- pair side: pieces of at most max_B caption-major rows
-    const int nrec = 2 * ((V + 255) / 256);
-    if (!c->smax_part) DALLOC(c, c->smax_part, sizeof(float) * (size_t)maxB * nrec * SMAX_REC);
     for (int64_t r0 = 0; r0 < Rtot; r0 += maxB) {
         const int R = (int)std::min<int64_t>(maxB, Rtot - r0);
         const bool epi = decode_tables_on(c, R), fused = score_fused_on(c, R);
@@ -1386,20 +1470,10 @@ int score_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, 
                 k_lstm_fwd(st, dt, c->st_g, 4 * H2, t ? c2c : nullptr, Rt, H2, c->st_a, c->ld4H2, c2n, h2n, ldA2, nullptr);
             }
             if (fused) {
-                GemmArgs g{};
-                g.dtype = dt;
-                g.A = h2n; g.lda = ldA2;
-                g.B = c->Wod; g.ldb = c->ldH2;
-                g.M = Ml; g.N = V;
-                g.K = (int)round_up64(H2, 64);
-                g.bias = p[8];
-                g.a_mode = GEMM_A_PLAIN;
-                g.out_mode = GEMM_OUT_SMAX_PICK;
-                g.zero_page = c->zero_page;
-                g.smax.part = c->smax_part; g.smax.nrec = nrec; g.smax.tgt = tgt_row;
-                hipError_t e = launch_gemm_8p(st, g);
-                if (e != hipSuccess) FAIL(c, LRCN_EHIP, "score step (logits GEMM + log-softmax pick epilogue): %s", hipGetErrorString(e));
-                if (!k_score_pick_merge(st, c->smax_part, nrec, Rt, acc)) FAIL(c, LRCN_EINVAL, "score merge: %d records per row", nrec);
+                SmaxEpi pick{};
+                pick.tgt = tgt_row;
+                if ((r = logits_records(c, h2n, ldA2, p[8], Ml, GEMM_OUT_SMAX_PICK, pick))) return r;   // lrcn.jl:550, log-softmax pick epilogue
+                if (!k_score_pick_merge(st, c->smax_part, smax_nrec(c), Rt, acc)) FAIL(c, LRCN_EINVAL, "score merge: %d records per row", smax_nrec(c));
             } else {
                 GEMM(c, dt, h2n, ldA2, c->Wod, c->ldH2, c->st_logits, c->ldV, Rt, V, H2, p[8], true);   // lrcn.jl:550
                 k_softmax_xent(st, dt, c->st_logits, c->ldV, tgt_row, Rt, V, 1.0f, terms + maxB, nullptr, 0, terms);
@@ -2205,10 +2279,10 @@ int lrcn_beam_search(lrcn_ctx *c, const float *const p[9], const float *feat, in
 
 // generate/beam_search for N images at once (lrcn.jl:585-678 per image; the reference decodes one image at a time with K
 // sequential batch-1 lrcn() calls and a device->host copy of V floats per hypothesis per step).  Here the N*K hypotheses of all
-// images are the rows of ONE batched lrcn() step; softmax, top-K, candidate ordering, history update and the stop test
-// run on the device (beam_update_kernel); the host only polls a done-counter every few steps.  Per image the result is what
-// lrcn_beam_search returns (tests/test_gpu_lstm_parity.py).  feats: N x 4096 column-major; out_tokens: [N][nword + 2]
-// (bos first), out_len[N], out_prob[N] (may be NULL) on the HOST.
+// images are the rows of ONE batched lrcn() step (decode_begin / decode_step, shared with lrcn_sample_batch); softmax, top-K,
+// candidate ordering, history update and the stop test run on the device (beam_update_kernel); the host only polls a done-counter
+// every few steps.  Per image the result is what lrcn_beam_search returns (tests/test_gpu_lstm_parity.py).  feats: N x 4096
+// column-major; out_tokens: [N][nword + 2] (bos first), out_len[N], out_prob[N] (may be NULL) on the HOST.
 int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int nword, int32_t *out_tokens,
                            int *out_len, float *out_prob) {
     DeviceGuard dg(c);
@@ -2216,98 +2290,50 @@ int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *fe
     if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
     if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d exceeds max_B = %d", N, K, c->maxB);
     if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
-    const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
     const int R = N * K, Lh = nword + 2;
     hipStream_t st = c->stream;
-    const bool epi = decode_epi_on(c, R);
-    const bool smax = epi && decode_smax_on(c, R, K);
-    const bool tables = epi && decode_tables_on(c, R);
-    int r = tables ? decode_tables_alloc(c) : LRCN_OK;
+    const DecodeRoute rt = decode_route(c, R, K);
+    int r = decode_begin(c, p, feats, N, K, rt);
     if (r) return r;
-    r = prepare_weights(c, p, false, !tables, false, epi, tables);
-    if (r) return r;
-    // input = input * param[end-3] per image (lrcn.jl:611), each row repeated for the image's K hypotheses
-    k_transpose(st, dt, 1, feats, N, LRCN_CNNOUT, N, c->F, LRCN_CNNOUT, 0);
-    GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, N, h, LRCN_CNNOUT, nullptr, true);
-    k_repeat_rows(st, GEMM_T_F32, c->dxcnn, c->ldh, N, K, h, c->xcnn);
-    const int Hs[4] = {H1, H1, H2, H2};
-    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemsetAsync(c->st_f32[i], 0, sizeof(float) * (size_t)R * Hs[i], st));
-    HIPCHK(c, hipMemsetAsync(c->st_xh1, 0, c->esz * (size_t)R * c->ldXH1, st));  // zero initial h1 / h2 (T copies) and K padding
-    HIPCHK(c, hipMemsetAsync(c->st_xh2, 0, c->esz * (size_t)R * c->ldXH2, st));
-    if (c->nl == 1) {  // LRCN-1f: the x_cnn columns of [emb | x_cnn | h1] are constant over the decode (a hypothesis never changes image)
-        DropSpec nd{};
-        k_concat_x2(st, dt, c->st_xh1, c->ldXH1, c->xcnn, c->ldh, 1, R, E, h, nd);
-    }
     HIPCHK(c, hipMemsetAsync(c->bs_done, 0, sizeof(int32_t) * N, st));
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
     k_beam_init(st, c->bs_seq[0], c->bs_last, c->bs_p, R, Lh, LRCN_BOS);  // histories = [bos], probabilities 1, next input = bos
-    DropSpec none{};
+    DecodeTail tail{};
+    if (rt.smax) {   // :652, :655-656 in the logits GEMM's epilogue + merge
+        tail.kind = DecodeTail::TOPK;
+        tail.K = K;
+    }
+    const int Hs[4] = {c->H1, c->H1, c->H2, c->H2};
     int cur = 0;
-    if (tables && (r = decode_tables_build(c, p, N, K))) return r;
     for (int current = 1; current <= nword + 1; ++current) {
-        if (tables) {
-            r = step_decode_tables(c, p, R, current > 1 ? c->st_parent : nullptr, current == 1, smax ? K : 0);
-            if (r) return r;
-            std::swap(c->st_f32[1], c->st2_f32[1]);
-            std::swap(c->st_f32[3], c->st2_f32[3]);
-        } else if (epi) {
-            // one launch: embedding of every hypothesis' last token (lrcn.jl:650) + h1 / h2 of its parent (:673-676) into the [x | h] operands
-            const bool two = c->nl == 2;
-            k_decode_prep(st, c->WeT, c->ldE, c->bs_last, current > 1 ? c->st_parent : nullptr, R, E, c->st_h1, c->ldH1, H1, two ? c->st_h2 : nullptr,
-                          c->ldH2, H2, c->st_xh1, c->ldXH1, c->ldX1, two ? c->st_xh2 : nullptr, c->ldXH2, c->ldH2);
-            r = step_decode(c, p, R, none, true, current > 1 ? c->st_parent : nullptr, current == 1, smax ? K : 0);   // :651, all N*K hypotheses batched
-            if (r) return r;
-            std::swap(c->st_f32[1], c->st2_f32[1]);
-            if (two) std::swap(c->st_f32[3], c->st2_f32[3]);
-        } else {
-            k_embed_gather(st, dt, c->WeT, c->ldE, c->bs_last, 1, R, E, none, c->st_xh1, c->ldXH1);  // lrcn.jl:650
-            r = step_decode(c, p, R, none, false);                                          // :651, all N*K hypotheses batched
-            if (r) return r;
-        }
-        if (smax) {
-            // :652, :655-656 happened in the logits GEMM's epilogue + merge
-        } else if (!k_softmax_topk_rows(st, c->st_logits, c->ldV, R, V, K, c->st_topi, c->st_topv)) {  // :652, :655-656 in one pass
-            k_softmax_rows(st, c->st_logits, c->ldV, R, V, c->st_prob, c->ldV);
-            k_topk_rows(st, c->st_prob, c->ldV, R, V, K, c->st_topi, c->st_topv);
+        if ((r = decode_step(c, p, R, rt, current, tail))) return r;   // :650-651, all N*K hypotheses batched
+        if (!rt.smax && !k_softmax_topk_rows(st, c->st_logits, c->ldV, R, c->V, K, c->st_topi, c->st_topv)) {  // :652, :655-656 in one pass
+            k_softmax_rows(st, c->st_logits, c->ldV, R, c->V, c->st_prob, c->ldV);
+            k_topk_rows(st, c->st_prob, c->ldV, R, c->V, K, c->st_topi, c->st_topv);
         }
         k_beam_update(st, c->st_topi, c->st_topv, c->bs_seq[cur], c->bs_seq[cur ^ 1], c->bs_p, c->st_parent, c->bs_last, c->bs_done,
                       c->bs_ndone, c->bs_res_tok, c->bs_res_len, c->bs_res_p, N, K, Lh, current, nword, LRCN_EOS);
         cur ^= 1;
-        if (!epi) {   // :673-676: the four states follow their parents; the T copies of h1 / h2 for the next step's GEMMs ride along
+        if (!rt.epi) {   // :673-676: the plain step read no parent -- the four states follow theirs; the T copies of h1 / h2 for the next step's GEMMs ride along
             void *const hT[4] = {boff(c->st_xh1, c->ldX1, c->esz), nullptr, boff(c->st_xh2, c->ldH2, c->esz), nullptr};
             const int64_t ldT[4] = {c->ldXH1, 0, c->ldXH2, 0};
-            k_gather_state(st, dt, c->st_f32, c->st2_f32, hT, ldT, Hs, c->st_parent, R);
+            k_gather_state(st, c->dt, c->st_f32, c->st2_f32, hT, ldT, Hs, c->st_parent, R);
             for (int i = 0; i < 4; ++i) std::swap(c->st_f32[i], c->st2_f32[i]);
         }
-        if ((current & 3) == 0 && current <= nword) {  // every image finished early?
-            int32_t nd = 0;
-            HIPCHK(c, hipMemcpyAsync(&nd, c->bs_ndone, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            if (nd >= N) break;
-        }
+        bool done = false;   // every image finished early?
+        if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
+        if (done) break;
     }
     KCHK(c, "beam_search_batch");
-    // results through a PINNED staging buffer of the context: a device -> pageable-host copy above 64 KB takes HIP's pin-on-the-fly
-    // path (measured: +16 ms per decode from 512 images, whose token block is 67 KB -- more than the 12.9 ms of kernels)
-    const size_t nb_tok = sizeof(int32_t) * (size_t)N * Lh, nb_n = sizeof(int32_t) * (size_t)N;
-    if ((r = pin_reserve(c, nb_tok + 2 * nb_n))) return r;
-    unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
-    HIPCHK(c, hipMemcpyAsync(pin, c->bs_res_tok, nb_tok, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(pin + nb_tok, c->bs_res_len, nb_n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(pin + nb_tok + nb_n, c->bs_res_p, nb_n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(out_tokens, pin, nb_tok);
-    memcpy(out_len, pin + nb_tok, nb_n);
-    if (out_prob) memcpy(out_prob, pin + nb_tok + nb_n, nb_n);
-    return LRCN_OK;
+    return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, N, Lh, out_tokens, out_len, out_prob);
 }
 
 // Sampled generation (include/lrcn_sample.h; the sample() path of lrcn.jl:613-621, 680-687): the batched decode of lrcn_beam_search_batch
-// -- the same tables, cell epilogues and step forms, selected under the same conditions -- with R = N*S independent rows instead of
-// N*K beams: the parent index is the identity, and the per-step choice is a Gumbel-max draw per row (sample.hip) instead of top-K and
-// a beam reorder.  Where the beam's logits GEMM reduces to top-K records (decode_smax_on), top_k = 0 reduces to Gumbel records instead
-// (GEMM_OUT_SMAX_GUMBEL) and 1 <= top_k < SMAX_KC draws among the top-K records' best columns; otherwise the logits reach st_logits and
-// one workgroup per row draws (LRCN_DECODE_SMAX=0 forces that form).
+// (decode_begin / decode_step on the route decode_route picks) with R = N*S independent rows instead of N*K beams: the parent index is the
+// identity, and the per-step choice is a Gumbel-max draw per row (sample.hip) instead of top-K and a beam reorder.  Where the beam's logits
+// GEMM reduces to top-K records (decode_smax_on), top_k = 0 reduces to Gumbel records instead (GEMM_OUT_SMAX_GUMBEL) and 1 <= top_k < SMAX_KC
+// draws among the top-K records' best columns; otherwise the logits reach st_logits and one workgroup per row draws (LRCN_DECODE_SMAX=0
+// forces that form).
 int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k,
                       uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp) {
     DeviceGuard dg(c);
@@ -2316,94 +2342,42 @@ int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, 
     if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
     if (top_k < 0 || top_k > 32 || top_k > c->V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, min(32, V=%d)]", top_k, c->V);
     if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
-    const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
-    const int R = N * S, Lh = nword + 2;
+    const int R = N * S, Lh = nword + 2, nrec = smax_nrec(c);
     hipStream_t st = c->stream;
-    const bool epi = decode_epi_on(c, R);
-    const bool smax = epi && decode_smax_on(c, R, top_k);   // top_k < SMAX_KC
-    const bool tables = epi && decode_tables_on(c, R);
-    struct DrawReset {   // the beam decode never sees a sampler's draw mode, whichever way this call ends
-        lrcn_ctx *c;
-        ~DrawReset() { c->dec_draw = 0; }
-    } reset{c};
-    c->dec_draw = smax ? (top_k == 0 ? 2 : 1) : 0;
-    c->dec_gumbel = SmaxEpi{};
-    c->dec_gumbel.temp = temperature;
-    c->dec_gumbel.key0 = (uint32_t)seed;
-    c->dec_gumbel.key1 = (uint32_t)(seed >> 32);
-    c->dec_gumbel.S = S;
-    int r = tables ? decode_tables_alloc(c) : LRCN_OK;
+    const DecodeRoute rt = decode_route(c, R, top_k);   // smax: top_k < SMAX_KC
+    int r = decode_begin(c, p, feats, N, S, rt);
     if (r) return r;
-    r = prepare_weights(c, p, false, !tables, false, epi, tables);
-    if (r) return r;
-    // input = input * param[end-3] per image (lrcn.jl:611), each row repeated for the image's S samples
-    k_transpose(st, dt, 1, feats, N, LRCN_CNNOUT, N, c->F, LRCN_CNNOUT, 0);
-    GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, N, h, LRCN_CNNOUT, nullptr, true);
-    k_repeat_rows(st, GEMM_T_F32, c->dxcnn, c->ldh, N, S, h, c->xcnn);
-    const int Hs[4] = {H1, H1, H2, H2};
-    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemsetAsync(c->st_f32[i], 0, sizeof(float) * (size_t)R * Hs[i], st));
-    HIPCHK(c, hipMemsetAsync(c->st_xh1, 0, c->esz * (size_t)R * c->ldXH1, st));  // zero initial h1 / h2 (T copies) and K padding
-    HIPCHK(c, hipMemsetAsync(c->st_xh2, 0, c->esz * (size_t)R * c->ldXH2, st));
-    if (c->nl == 1) {  // LRCN-1f: the x_cnn columns of [emb | x_cnn | h1] are constant over the decode
-        DropSpec nd{};
-        k_concat_x2(st, dt, c->st_xh1, c->ldXH1, c->xcnn, c->ldh, 1, R, E, h, nd);
-    }
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
     SampleState ss{c->bs_seq[0], c->bs_last, c->bs_done, c->bs_res_len, c->bs_ndone, c->bs_p, Lh, 0, nword, LRCN_EOS};
     k_sample_init(st, ss, R, LRCN_BOS);   // histories = [bos], log-likelihoods 0, next input = bos
-    k_row_div(st, c->st_parent, R, 1);    // every row continues its own state
-    DropSpec none{};
-    if (tables && (r = decode_tables_build(c, p, N, S))) return r;
-    const int nrec = 2 * ((V + 255) / 256);
+    k_row_div(st, c->st_parent, R, 1);    // every row continues its own state: the plain step's in-place update needs no gather
+    DecodeTail tail{};
+    if (rt.smax && top_k == 0) {
+        tail.kind = DecodeTail::GUMBEL;
+        tail.draw.temp = temperature;
+        tail.draw.key0 = (uint32_t)seed;
+        tail.draw.key1 = (uint32_t)(seed >> 32);
+        tail.draw.S = S;
+    } else if (rt.smax) {
+        tail.kind = DecodeTail::RECORDS;
+    }
     for (int current = 1; current <= nword + 1; ++current) {
         ss.current = current;
-        c->dec_gumbel.current = current;
-        if (tables) {
-            r = step_decode_tables(c, p, R, current > 1 ? c->st_parent : nullptr, current == 1, smax ? SMAX_KC - 1 : 0);
-            if (r) return r;
-            std::swap(c->st_f32[1], c->st2_f32[1]);
-            std::swap(c->st_f32[3], c->st2_f32[3]);
-        } else if (epi) {
-            const bool two = c->nl == 2;
-            k_decode_prep(st, c->WeT, c->ldE, c->bs_last, current > 1 ? c->st_parent : nullptr, R, E, c->st_h1, c->ldH1, H1, two ? c->st_h2 : nullptr,
-                          c->ldH2, H2, c->st_xh1, c->ldXH1, c->ldX1, two ? c->st_xh2 : nullptr, c->ldXH2, c->ldH2);
-            r = step_decode(c, p, R, none, true, current > 1 ? c->st_parent : nullptr, current == 1, smax ? SMAX_KC - 1 : 0);
-            if (r) return r;
-            std::swap(c->st_f32[1], c->st2_f32[1]);
-            if (two) std::swap(c->st_f32[3], c->st2_f32[3]);
-        } else {
-            // the plain step updates the states in place (k_lstm_fwd), which is where an identity parent leaves them
-            k_embed_gather(st, dt, c->WeT, c->ldE, c->bs_last, 1, R, E, none, c->st_xh1, c->ldXH1);  // lrcn.jl:650
-            r = step_decode(c, p, R, none, false);
-            if (r) return r;
-        }
-        if (smax && top_k == 0) {
+        tail.draw.current = current;
+        if ((r = decode_step(c, p, R, rt, current, tail))) return r;
+        if (tail.kind == DecodeTail::GUMBEL) {
             if (!k_sample_gumbel_merge(st, c->smax_part, nrec, R, ss)) FAIL(c, LRCN_EINVAL, "sample merge: %d records per row", nrec);
-        } else if (smax) {
+        } else if (tail.kind == DecodeTail::RECORDS) {
             if (!k_sample_topk_merge(st, c->smax_part, nrec, R, top_k, temperature, seed, S, ss)) FAIL(c, LRCN_EINVAL, "sample top-k merge: top_k = %d, %d records", top_k, nrec);
         } else {
-            k_sample_rows(st, c->st_logits, c->ldV, R, V, top_k, temperature, seed, S, ss);
+            k_sample_rows(st, c->st_logits, c->ldV, R, c->V, top_k, temperature, seed, S, ss);
         }
-        if ((current & 3) == 0 && current <= nword) {  // every row finished early?
-            int32_t nd = 0;
-            HIPCHK(c, hipMemcpyAsync(&nd, c->bs_ndone, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            if (nd >= R) break;
-        }
+        bool done = false;   // every row finished early?
+        if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, R, done))) return r;
+        if (done) break;
     }
     KCHK(c, "sample_batch");
-    // results through the pinned staging buffer (see lrcn_beam_search_batch)
-    const size_t nb_tok = sizeof(int32_t) * (size_t)R * Lh, nb_n = sizeof(int32_t) * (size_t)R;
-    if ((r = pin_reserve(c, nb_tok + 2 * nb_n))) return r;
-    unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
-    HIPCHK(c, hipMemcpyAsync(pin, c->bs_seq[0], nb_tok, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(pin + nb_tok, c->bs_res_len, nb_n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(pin + nb_tok + nb_n, c->bs_p, nb_n, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    memcpy(out_tokens, pin, nb_tok);
-    memcpy(out_len, pin + nb_tok, nb_n);
-    if (out_logp) memcpy(out_logp, pin + nb_tok + nb_n, nb_n);
-    return LRCN_OK;
+    return decode_results_to_host(c, c->bs_seq[0], c->bs_res_len, c->bs_p, R, Lh, out_tokens, out_len, out_logp);
 }
 
 // Caption scoring (include/lrcn_score.h; paper section 5.1 / Table 2 -- not in lrcn.jl): see score_impl
