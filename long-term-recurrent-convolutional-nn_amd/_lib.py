@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LRCN_HIP_LIB") or os.path.join(CSRC, "liblrcn_hip.so"
 HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn.h"))
 SAMPLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sample.h"))  # lrcn_sample_batch (not in lrcn.h)
 SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.h"))    # lrcn_score_matrix / _pairs (not in lrcn.h)
+NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -139,10 +140,16 @@ SCORE_SIGNATURES = {
                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_nbest.h declares (bound by lib() as well)
+NBEST_SIGNATURES = {
+    "lrcn_beam_nbest_batch": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -162,7 +169,7 @@ def lib():
         # the one this process uses: import torch BEFORE the library so the dynamic linker binds to that instance.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

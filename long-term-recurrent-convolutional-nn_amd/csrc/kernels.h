@@ -68,6 +68,8 @@ void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l
                     float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
 // prob[v] = exp(logp) for one row each (beam search, lrcn.jl:652).
 void k_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *prob, int64_t ld_p);
+// out[v] = (x[v] - max) - log(sum exp(x - max)) for one row each (the n-best beam above k_softmax_topk_rows' V limit)
+void k_log_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *out, int64_t ld_o);
 
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)
@@ -198,11 +200,12 @@ void k_conv11_fused(hipStream_t st, int src_is_u8, const void *src, int N, int S
                     const float *bias, void *out);
 
 // softmax + top-K of every row in one pass (false: V too large for the register-resident form, use the two kernels)
-bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val);
+// logp: log-probabilities (x - max) - log(sum exp(x - max)) instead of probabilities (the n-best beam), same order
+bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val, bool logp = false);
 // out[i][r][:] = in[i][parent[r]][:] for the four recurrent states (row stride C[i]); hT[i] != NULL also receives a T copy (ld ldT[i])
 // second half of the logits GEMM's softmax / top-K epilogue (gemm.h SmaxEpi): records [R][nrec][SMAX_REC] -> idx / val [R][K] as k_softmax_topk_rows;
 // false = not applicable (K >= SMAX_KC, too many records)
-bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val);
+bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val, bool logp = false);
 // bf16 batched decode, one launch per step: embedding of each hypothesis' last token + h1 / h2 of its parent into the [x | h] operands
 void k_decode_prep(hipStream_t st, const void *wembT, int64_t ld_w, const int32_t *last, const int32_t *parent, int R, int E, const void *h1,
                    int64_t ld_h1, int H1, const void *h2, int64_t ld_h2, int H2, void *xh1, int64_t ld_xh1, int64_t off_h1, void *xh2, int64_t ld_xh2,
@@ -228,6 +231,28 @@ void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V
 // from GEMM_OUT_SMAX_GUMBEL records (top_k = 0) resp. GEMM_OUT_SMAX_TOPK records (1 <= top_k < SMAX_KC); false = not applicable
 bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s);
 bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
+
+// ---- nbest.hip: the per-step bookkeeping of the n-best beam (lrcn_beam_nbest_batch, include/lrcn_nbest.h) ----
+// Device state of N images x K slots (row r = n * K + k): live histories (ping-pong) and their cumulative log-probabilities (-inf: dead
+// slot); per image {live slots (a prefix), pool entries, done}; the pool of finished hypotheses, [N][K] best first, each {score, logp (float
+// bits), storage row, length}, whose tokens live in 2K storage rows per image (an entry never moves its tokens); the results, written when
+// an image is done.
+struct NbestState {
+    const int32_t *seq_in;
+    int32_t *seq_out, *parent, *last, *ndone;
+    int4 *img;                                         // [N] {nlive, pool count, done, 0}
+    float *cum;
+    int32_t *store;                                    // [N][2K][L]
+    int4 *pool;                                        // [N][K]
+    int32_t *res_tok, *res_len;                        // [N*K][L], [N*K]
+    float *res_logp, *res_score;                       // [N*K]
+    int K, L, current, nword, eos;
+    float lp_cur, lp_max;                              // (float)pow(current, alpha), (float)pow(nword + 1, alpha)
+};
+// every slot [bos], cum 0, one live slot, empty pool, not done (R = N * K rows)
+void k_nbest_init(hipStream_t st, const NbestState &s, int N, int bos);
+// one step for N images (one workgroup each) from this step's log-probability top-K topi / topv [N*K][K]; K <= 32
+void k_nbest_update(hipStream_t st, const int32_t *topi, const float *topv, const NbestState &s, int N);
 
 // ---- score.hip: the per-pair steps of caption scoring (lrcn_score_matrix / lrcn_score_pairs) ----
 // A2 (T) row r < R: columns [0, h) = P row row_cap[r] (P: this step's [caption][ldP] block of h1 Wproj), columns [h2_off, h2_off + zero_h2) = 0

@@ -460,6 +460,21 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float *logits, 
     for (int v = threadIdx.x; v < V; v += blockDim.x) prob[(int64_t)m * ld_p + v] = expf(row[v] - lse);
 }
 
+// log softmax of each row, (x - max) - log(sum exp(x - max)): the n-best beam's fallback above softmax_topk_rows_kernel's V limit
+__global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float *logits, int64_t ld_l, int M, int V, float *out, int64_t ld_o) {
+    __shared__ float sh[8];
+    const int m = blockIdx.x;
+    const float *row = logits + (int64_t)m * ld_l;
+    float mx = -INFINITY;
+    for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, row[v]);
+    mx = block_max(mx, sh);
+    float se = 0.0f;
+    for (int v = threadIdx.x; v < V; v += blockDim.x) se += expf(row[v] - mx);
+    se = block_sum(se, sh);
+    const float ls = logf(se);
+    for (int v = threadIdx.x; v < V; v += blockDim.x) out[(int64_t)m * ld_o + v] = (row[v] - mx) - ls;
+}
+
 template <typename Tin, typename Tout>
 __global__ void transpose_kernel(const Tin *in, int64_t ld_in, int R, int C, Tout *out, int64_t ld_out, int shift) {
     __shared__ float tile[32][33];
@@ -1106,7 +1121,9 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float *prob, int64
 // hardware exponential (one instruction per element instead of ~20): 1e-6 relative on the reported probabilities.
 // Q = float4 loads per thread: V <= 1024 Q.  Every thread keeps the best of its own not-yet-retired elements; a round is
 // one block-wide argmax over those 256 candidates, after which only the winner's owner rescans its registers.
-template <int Q>
+// LOGP (the n-best beam, lrcn_nbest.h): the values are log-probabilities (x - max) - log(sum) instead, computed from the logit and
+// not as log(p) (p underflows to 0 for the improbable words of a peaked row); the same ranking and tie-group rule on those values.
+template <int Q, bool LOGP = false>
 __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *logits, int64_t ld, int R, int V, int K, int32_t *idx,
                                                                 float *val) {
     __shared__ float sh[8];
@@ -1183,7 +1200,7 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *log
                 bv = sv[w];
                 bi = si[w];
             }
-        const float pv = expf(bv - lse);
+        const float pv = LOGP ? (bv - mx) - logf(se) : expf(bv - lse);
         if (k >= K && (pv != pK || bi == 0x7FFFFFFF)) break;  // uniform: every thread holds the same (bv, bi)
         if (threadIdx.x == 0) {
             wi[k] = bi;
@@ -1228,8 +1245,8 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *log
 // (distinct logits that round to one float), then the tie group is put in index order.  A record keeps SMAX_KC = K + 1 candidates
 // of its 128 columns, so a tie group that crosses the K boundary is exact as long as no more than SMAX_KC of it fall into one record.
 // Lane l owns records l, l + 64, ...; every record's list is sorted, so a lane's best candidate is the best list HEAD, and retiring a
-// candidate shifts that list (static indices only).
-template <int NR>
+// candidate shifts that list (static indices only).  LOGP: log-probabilities (x - max) - log(sum), as softmax_topk_rows_kernel<Q, true>.
+template <int NR, bool LOGP = false>
 __global__ __launch_bounds__(256) void softmax_topk_merge_kernel(const float *part, int nrec, int R, int K, int32_t *idx, float *val) {
     __shared__ float wv[4][64];
     __shared__ int wi[4][64];
@@ -1294,7 +1311,7 @@ __global__ __launch_bounds__(256) void softmax_topk_merge_kernel(const float *pa
                 bi = oi;
             }
         }
-        const float pv = expf(bv - lse);
+        const float pv = LOGP ? (bv - gm) - logf(se) : expf(bv - lse);
         if (k >= K && (pv != pK || bi == 0x7FFFFFFF)) break;  // wave-uniform
         if (lane == 0) {
             wi[w][k] = bi;
@@ -1494,6 +1511,9 @@ void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l
 void k_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *prob, int64_t ld_p) {
     hipLaunchKernelGGL(softmax_rows_kernel, dim3(M), dim3(256), 0, st, logits, ld_l, M, V, prob, ld_p);
 }
+void k_log_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *out, int64_t ld_o) {
+    hipLaunchKernelGGL(log_softmax_rows_kernel, dim3(M), dim3(256), 0, st, logits, ld_l, M, V, out, ld_o);
+}
 void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t ld_in, int R, int C, void *out,
                  int64_t ld_out, int shift) {
     const dim3 grid(cdiv(C, 32), cdiv(R, 32));
@@ -1657,17 +1677,21 @@ void k_beam_update(hipStream_t st, const int32_t *topi, const float *topv, const
 void k_repeat_rows(hipStream_t st, int dtype, const void *in, int64_t ld, int N, int K, int C, void *out) {
     DISPATCH_T(dtype, hipLaunchKernelGGL(repeat_rows_kernel<T>, dim3(N * K), dim3(256), 0, st, (const T *)in, ld, N * K, K, C, (T *)out));
 }
-bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val) {
-    if (V > 16384 || K > 32 || (ld % 4) || (reinterpret_cast<uintptr_t>(logits) & 15)) return false;
+template <bool LOGP> void launch_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val) {
     const int q = (V + 1023) / 1024;
     if (q <= 4)
-        hipLaunchKernelGGL(softmax_topk_rows_kernel<4>, dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
+        hipLaunchKernelGGL((softmax_topk_rows_kernel<4, LOGP>), dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
     else if (q <= 8)
-        hipLaunchKernelGGL(softmax_topk_rows_kernel<8>, dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
+        hipLaunchKernelGGL((softmax_topk_rows_kernel<8, LOGP>), dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
     else if (q <= 12)
-        hipLaunchKernelGGL(softmax_topk_rows_kernel<12>, dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
+        hipLaunchKernelGGL((softmax_topk_rows_kernel<12, LOGP>), dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
     else
-        hipLaunchKernelGGL(softmax_topk_rows_kernel<16>, dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
+        hipLaunchKernelGGL((softmax_topk_rows_kernel<16, LOGP>), dim3(R), dim3(256), 0, st, logits, ld, R, V, K, idx, val);
+}
+bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val, bool logp) {
+    if (V > 16384 || K > 32 || (ld % 4) || (reinterpret_cast<uintptr_t>(logits) & 15)) return false;
+    if (logp) launch_softmax_topk_rows<true>(st, logits, ld, R, V, K, idx, val);
+    else launch_softmax_topk_rows<false>(st, logits, ld, R, V, K, idx, val);
     return true;
 }
 void k_gather_state(hipStream_t st, int dtype, const float *const in[4], float *const out[4], void *const hT[4], const int64_t ldT[4],
@@ -1678,12 +1702,16 @@ void k_gather_state(hipStream_t st, int dtype, const float *const in[4], float *
     }
     DISPATCH_T(dtype, hipLaunchKernelGGL(gather_state_kernel<T>, dim3(R, 4), dim3(256), 0, st, g, parent));
 }
-bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val) {
-    if (K < 1 || K >= SMAX_KC || nrec < 1 || nrec > 256 || (reinterpret_cast<uintptr_t>(part) & 15)) return false;
+template <bool LOGP> void launch_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val) {
     const dim3 grid((R + 3) / 4);
-    if (nrec <= 64) hipLaunchKernelGGL(softmax_topk_merge_kernel<1>, grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
-    else if (nrec <= 128) hipLaunchKernelGGL(softmax_topk_merge_kernel<2>, grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
-    else hipLaunchKernelGGL(softmax_topk_merge_kernel<4>, grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
+    if (nrec <= 64) hipLaunchKernelGGL((softmax_topk_merge_kernel<1, LOGP>), grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
+    else if (nrec <= 128) hipLaunchKernelGGL((softmax_topk_merge_kernel<2, LOGP>), grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
+    else hipLaunchKernelGGL((softmax_topk_merge_kernel<4, LOGP>), grid, dim3(256), 0, st, part, nrec, R, K, idx, val);
+}
+bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val, bool logp) {
+    if (K < 1 || K >= SMAX_KC || nrec < 1 || nrec > 256 || (reinterpret_cast<uintptr_t>(part) & 15)) return false;
+    if (logp) launch_softmax_topk_merge<true>(st, part, nrec, R, K, idx, val);
+    else launch_softmax_topk_merge<false>(st, part, nrec, R, K, idx, val);
     return true;
 }
 void k_decode_prep(hipStream_t st, const void *wembT, int64_t ld_w, const int32_t *last, const int32_t *parent, int R, int E, const void *h1,

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/lrcn.h"
+#include "../../include/lrcn_nbest.h"
 #include "../../include/lrcn_sample.h"
 #include "../../include/lrcn_score.h"
 #include "comm.h"
@@ -119,10 +120,16 @@ struct lrcn_ctx {
     int32_t *st_topi = nullptr, *st_parent = nullptr;
     // the batched decode (decode_begin / decode_step; lrcn_beam_search_batch and lrcn_sample_batch): token histories (ping-pong for the
     // beam's reorder; the sampler's rows keep bs_seq[0]), next input tokens, done flags and counter, results -- all on the device.  The
-    // sampler keeps its lengths in bs_res_len and its log-likelihoods in bs_p; bs_res_tok / bs_res_p are the beam's alone
+    // sampler keeps its lengths in bs_res_len and its log-likelihoods in bs_p; bs_res_tok / bs_res_p are the beams' (the n-best beam's
+    // results: [N*K] entries in bs_res_tok / bs_res_len / bs_res_p, scores in nb_res_score)
     int32_t *bs_seq[2] = {nullptr, nullptr}, *bs_last = nullptr, *bs_done = nullptr, *bs_ndone = nullptr, *bs_res_tok = nullptr,
             *bs_res_len = nullptr;
     float *bs_p = nullptr, *bs_res_p = nullptr;
+    // lrcn_beam_nbest_batch (include/lrcn_nbest.h), lazily on its first call: the pool's token storage [maxB][2][LRCN_BEAM_MAXLEN] (2K rows per
+    // image), the pool [maxB] {score, logp, storage row, length}, per image {live slots, pool count, done}, live cum [maxB], scores out
+    int32_t *nb_store = nullptr;
+    int4 *nb_pool = nullptr, *nb_img = nullptr;
+    float *nb_cum = nullptr, *nb_res_score = nullptr;
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;
@@ -1090,9 +1097,11 @@ int logits_records(lrcn_ctx *c, const void *hT, int64_t ldh, const float *bias, 
 //   RECORDS  GEMM_OUT_SMAX_TOPK records only, left in smax_part (the sampler at top_k >= 1 merges them itself)
 //   GUMBEL   GEMM_OUT_SMAX_GUMBEL records, left in smax_part, with the draw parameters `draw` (the sampler at top_k = 0, which sets
 //            draw.current before every step)
+//   logp     with TOPK: log-probabilities instead of probabilities in st_topv (the n-best beam)
 struct DecodeTail {
     enum Kind { LOGITS, TOPK, RECORDS, GUMBEL } kind = LOGITS;
     int K = 0;
+    bool logp = false;
     SmaxEpi draw{};
 };
 int decode_logits(lrcn_ctx *c, const float *const p[9], const void *hT, int64_t ldh, int B, const DecodeTail &t) {
@@ -1102,7 +1111,7 @@ int decode_logits(lrcn_ctx *c, const float *const p[9], const void *hT, int64_t 
     }
     int r = logits_records(c, hT, ldh, p[8], B, t.kind == DecodeTail::GUMBEL ? GEMM_OUT_SMAX_GUMBEL : GEMM_OUT_SMAX_TOPK, t.draw);
     if (r || t.kind != DecodeTail::TOPK) return r;
-    if (!k_softmax_topk_merge(c->stream, c->smax_part, smax_nrec(c), B, t.K, c->st_topi, c->st_topv))
+    if (!k_softmax_topk_merge(c->stream, c->smax_part, smax_nrec(c), B, t.K, c->st_topi, c->st_topv, t.logp))
         FAIL(c, LRCN_EINVAL, "softmax / top-K merge: K = %d, %d records", t.K, smax_nrec(c));
     return LRCN_OK;
 }
@@ -1271,22 +1280,34 @@ int decode_poll_done(lrcn_ctx *c, int target, bool &done) {
     return LRCN_OK;
 }
 
-// a batched decode's results -- tok [rows][Lh], len [rows], val [rows] on the device -- into the caller's host arrays (out_val may be NULL),
-// through the context's PINNED staging buffer: a device -> pageable-host copy above 64 KB takes HIP's pin-on-the-fly path (measured:
-// +16 ms per decode from 512 images, whose token block is 67 KB -- more than the 12.9 ms of kernels)
+// a batched decode's results -- tok [rows][Lh], len [rows], val [rows] (and val2 [rows] if given) on the device -- into the caller's host
+// arrays (out_val, out_val2 may be NULL), through the context's PINNED staging buffer: a device -> pageable-host copy above 64 KB takes HIP's
+// pin-on-the-fly path (measured: +16 ms per decode from 512 images, whose token block is 67 KB -- more than the 12.9 ms of kernels)
 int decode_results_to_host(lrcn_ctx *c, const int32_t *tok, const int32_t *len, const float *val, int rows, int Lh, int32_t *out_tok, int *out_len,
-                           float *out_val) {
+                           float *out_val, const float *val2 = nullptr, float *out_val2 = nullptr) {
     const size_t nb_tok = sizeof(int32_t) * (size_t)rows * Lh, nb_n = sizeof(int32_t) * (size_t)rows;
-    int r = pin_reserve(c, nb_tok + 2 * nb_n);
+    int r = pin_reserve(c, nb_tok + (val2 ? 3 : 2) * nb_n);
     if (r) return r;
     unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
     HIPCHK(c, hipMemcpyAsync(pin, tok, nb_tok, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin + nb_tok, len, nb_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin + nb_tok + nb_n, val, nb_n, hipMemcpyDeviceToHost, c->stream));
+    if (val2) HIPCHK(c, hipMemcpyAsync(pin + nb_tok + 2 * nb_n, val2, nb_n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     memcpy(out_tok, pin, nb_tok);
     memcpy(out_len, pin + nb_tok, nb_n);
     if (out_val) memcpy(out_val, pin + nb_tok + nb_n, nb_n);
+    if (val2 && out_val2) memcpy(out_val2, pin + nb_tok + 2 * nb_n, nb_n);
+    return LRCN_OK;
+}
+
+// the n-best beam's device state (lrcn_beam_nbest_batch), allocated on its first call
+int nbest_alloc(lrcn_ctx *c) {
+    const size_t B = (size_t)c->maxB;
+    if (c->nb_store) return LRCN_OK;
+    DALLOC(c, c->nb_store, sizeof(int32_t) * B * 2 * LRCN_BEAM_MAXLEN);
+    DALLOC(c, c->nb_pool, sizeof(int4) * B);      DALLOC(c, c->nb_img, sizeof(int4) * B);
+    DALLOC(c, c->nb_cum, sizeof(float) * B);      DALLOC(c, c->nb_res_score, sizeof(float) * B);
     return LRCN_OK;
 }
 
@@ -2378,6 +2399,67 @@ int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, 
     }
     KCHK(c, "sample_batch");
     return decode_results_to_host(c, c->bs_seq[0], c->bs_res_len, c->bs_p, R, Lh, out_tokens, out_len, out_logp);
+}
+
+// The n-best beam search (include/lrcn_nbest.h): the batched decode of lrcn_beam_search_batch (decode_begin / decode_step on the route
+// decode_route picks, N*K rows) with log-probability top-K (the LOGP forms of the records merge and the rows kernel) and its own per-step
+// bookkeeping (nbest.hip): live slots in log space, a pool of finished hypotheses with length normalisation, the exact early stop.
+int lrcn_beam_nbest_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int nword, float alpha, int32_t *out_tokens,
+                          int *out_len, float *out_logp, float *out_score) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
+    if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
+    if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d must be in [1, max_B = %d]", N, K, c->maxB);
+    if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
+    if (!std::isfinite(alpha) || alpha < 0.0f) FAIL(c, LRCN_EINVAL, "alpha=%g must be finite and >= 0", (double)alpha);
+    const int R = N * K, Lh = nword + 2;
+    hipStream_t st = c->stream;
+    int r = nbest_alloc(c);
+    if (r) return r;
+    const DecodeRoute rt = decode_route(c, R, K);
+    if ((r = decode_begin(c, p, feats, N, K, rt))) return r;
+    HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
+    NbestState ns{};
+    ns.parent = c->st_parent; ns.last = c->bs_last; ns.ndone = c->bs_ndone; ns.img = c->nb_img; ns.cum = c->nb_cum;
+    ns.store = c->nb_store; ns.pool = c->nb_pool;
+    ns.res_tok = c->bs_res_tok; ns.res_len = c->bs_res_len; ns.res_logp = c->bs_res_p; ns.res_score = c->nb_res_score;
+    ns.K = K; ns.L = Lh; ns.nword = nword; ns.eos = LRCN_EOS;
+    ns.lp_max = (float)std::pow((double)(nword + 1), (double)alpha);
+    ns.seq_in = c->bs_seq[0];
+    k_nbest_init(st, ns, N, LRCN_BOS);   // histories = [bos], cum 0, next input = bos, one live slot, empty pools
+    DecodeTail tail{};
+    if (rt.smax) {   // log-probability top-K in the logits GEMM's epilogue + merge
+        tail.kind = DecodeTail::TOPK;
+        tail.K = K;
+        tail.logp = true;
+    }
+    const int Hs[4] = {c->H1, c->H1, c->H2, c->H2};
+    int cur = 0;
+    for (int current = 1; current <= nword + 1; ++current) {
+        if ((r = decode_step(c, p, R, rt, current, tail))) return r;
+        if (!rt.smax && !k_softmax_topk_rows(st, c->st_logits, c->ldV, R, c->V, K, c->st_topi, c->st_topv, true)) {
+            k_log_softmax_rows(st, c->st_logits, c->ldV, R, c->V, c->st_prob, c->ldV);
+            k_topk_rows(st, c->st_prob, c->ldV, R, c->V, K, c->st_topi, c->st_topv);
+        }
+        ns.seq_in = c->bs_seq[cur];
+        ns.seq_out = c->bs_seq[cur ^ 1];
+        ns.current = current;
+        ns.lp_cur = (float)std::pow((double)current, (double)alpha);
+        k_nbest_update(st, c->st_topi, c->st_topv, ns, N);
+        cur ^= 1;
+        if (!rt.epi) {   // the plain step read no parent: the four states follow theirs (and the T copies of h1 / h2)
+            void *const hT[4] = {boff(c->st_xh1, c->ldX1, c->esz), nullptr, boff(c->st_xh2, c->ldH2, c->esz), nullptr};
+            const int64_t ldT[4] = {c->ldXH1, 0, c->ldXH2, 0};
+            k_gather_state(st, c->dt, c->st_f32, c->st2_f32, hT, ldT, Hs, c->st_parent, R);
+            for (int i = 0; i < 4; ++i) std::swap(c->st_f32[i], c->st2_f32[i]);
+        }
+        bool done = false;   // every image finished early?
+        if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
+        if (done) break;
+    }
+    KCHK(c, "beam_nbest_batch");
+    return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, R, Lh, out_tokens, out_len, out_logp, c->nb_res_score, out_score);
 }
 
 // Caption scoring (include/lrcn_score.h; paper section 5.1 / Table 2 -- not in lrcn.jl): see score_impl

@@ -454,6 +454,30 @@ def sample_batch(ctx, param, feats, nsamples, nword, temperature=1.0, top_k=0, s
     return [[(list(out[r * L:r * L + n[r]]), lp[r]) for r in range(i * S, (i + 1) * S)] for i in range(N)]
 
 
+def beam_nbest_batch(ctx, param, feats, beam_width, nword, alpha=0.0):
+    """n-best beam search for N images in one device-resident decode (lrcn_beam_nbest_batch, include/lrcn_nbest.h): log space, a pool of
+    finished hypotheses, length normalisation score = logp / len^alpha (len = tokens after bos) and an exact early stop.  feats N x 4096 ->
+    per image up to beam_width (token ids incl. bos, logp, score), best score first; N * beam_width <= max_B."""
+    N, K, L = feats.shape[0], beam_width, nword + 2
+    out = (C.c_int32 * (N * K * L))()
+    n = (C.c_int * (N * K))()
+    lp = (C.c_float * (N * K))()
+    sc = (C.c_float * (N * K))()
+    ctx._call("lrcn_beam_nbest_batch", _p9(param), _ptr(feats), N, K, nword, float(alpha), out, n, lp, sc)
+    toks = np.ctypeslib.as_array(out).reshape(N * K, L).tolist()   # (one conversion: N * K rows of ctypes slices cost milliseconds)
+    n, lp, sc = list(n), list(lp), list(sc)
+    return [[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K, (i + 1) * K) if n[r] > 0] for i in range(N)]
+
+
+def nbest_captions(ctx, param, feats, index_to_word, beam_width, nword, alpha=0.0, normalize=False):
+    """beam_nbest_batch as caption text: per image the list of (caption, logp, score), best score first."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    return [[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in entries]
+            for entries in beam_nbest_batch(ctx, param, feats, beam_width, nword, alpha)]
+
+
 def _caption(seq, index_to_word):
     words = []
     for t in seq[1:]:

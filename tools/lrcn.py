@@ -60,6 +60,11 @@ def build_parser():
     p.add_argument("--sample", type=int, default=0, help="--generate: draw this many captions per image instead of beam search (0 = beam search)")
     p.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature (0 = greedy)")
     p.add_argument("--topk", type=int, default=0, help="--sample: draw among the k most probable words only (0 = all)")
+    p.add_argument("--nbest", action="store_true",
+                   help="--generate: n-best beam search in log space (include/lrcn_nbest.h) at --beam_width; writes <out>/nbest with "
+                        "--beam_width lines per image (id, score, logp, caption), candidates / ids keep each image's best")
+    p.add_argument("--length_norm", type=float, default=0.0,
+                   help="--nbest: rank by logp / len^ALPHA, len = predicted tokens (0 = raw log-likelihood, 1 = per token)")
     p.add_argument("--retrieval", action="store_true",
                    help="image-caption retrieval (paper section 5.1 / Table 2): score --capnumber images of the --generate split, drawn as --generate "
                         "draws them (a permutation seeded by --seed), against all their captions; R@1/5/10 and Medr both ways, "
@@ -218,6 +223,10 @@ def main(argv=None):
                 for line in L.sample_captions(ctx, param, f, idx2word, o.sample, o.generate, o.temperature, o.topk, sample_seed)[0]:
                     print(line)
                 return 0
+            if o.nbest:   # the n-best list, best score first: score<TAB>logp<TAB>caption
+                for toks, lp, sc in L.beam_nbest_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm)[0]:
+                    print("%.6f\t%.6f\t%s" % (sc, lp, cap.caption_text(toks, idx2word)))
+                return 0
             toks, _ = L.beam_search(ctx, param, f, o.beam_width, o.generate)
             print(cap.caption_text(toks, idx2word))
             return 0
@@ -236,6 +245,7 @@ def main(argv=None):
         gc.collect()
         gc.freeze()
         smp = open(os.path.join(o.out, "samples" + suffix), "w") if o.sample > 0 else None
+        nbf = open(os.path.join(o.out, "nbest" + suffix), "w") if o.nbest and o.sample <= 0 else None
         with open(os.path.join(o.out, "candidates" + suffix), "w") as out, open(os.path.join(o.out, "candidate_ids" + suffix), "w") as ido:
             for s0 in range(0, len(ids), gen_chunk):  # the reference decodes image by image; here gen_chunk images x beam_width rows per step
                 chunk = ids[s0:s0 + gen_chunk]
@@ -251,11 +261,21 @@ def main(argv=None):
                         for toks, lp in rows:
                             smp.write("%d\t%.6f\t%s\n" % (i, lp, cap.caption_text(toks, idx2word)))
                     continue
+                if nbf is not None:
+                    # candidates / ids keep each image's best entry; `nbest` holds the list: "id<TAB>score<TAB>logp<TAB>caption", best first
+                    for i, entries in zip(chunk, L.beam_nbest_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.generate, o.length_norm)):
+                        ido.write("%d\n" % i)
+                        out.write(cap.caption_text(entries[0][0], idx2word) + "\n")
+                        for toks, lp, sc in entries:
+                            nbf.write("%d\t%.6f\t%.6f\t%s\n" % (i, sc, lp, cap.caption_text(toks, idx2word)))
+                    continue
                 for i, (toks, _) in zip(chunk, L.beam_search_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.generate)):
                     ido.write("%d\n" % i)
                     out.write(cap.caption_text(toks, idx2word) + "\n")
         if smp is not None:
             smp.close()
+        if nbf is not None:
+            nbf.close()
         return 0
 
     # ---------------------------------------------------------------- retrieval (paper section 5.1 / Table 2; not in lrcn.jl)
