@@ -1172,8 +1172,8 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *log
     // and distinct logits can round to one float probability: if candidates beyond the K-th still share the K-th winner's
     // probability they belong to the same tie group, whose lowest INDICES win.  So the rounds go on (at most to 64 entries)
     // until the next candidate's probability differs; all of this is block-uniform.
-    float pK = -1.0f;
-    int n = 0;
+    float pK = -1.0f, prev_pv = 0.0f;
+    int n = 0, run = 0, n_gt = 0;   // run: first round of the current equal-probability run; n_gt: winners above pK
     for (int k = 0; k < 64; ++k) {
         float bv = lv;
         int bi = li;
@@ -1207,7 +1207,12 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *log
             wv[k] = pv;
         }
         n = k + 1;
-        if (k == K - 1) pK = pv;
+        if (k == 0 || pv != prev_pv) run = k;
+        prev_pv = pv;
+        if (k == K - 1) {
+            pK = pv;
+            n_gt = run;
+        }
         if (((bi >> 2) & 255) == (int)threadIdx.x) {  // the owner retires the winner and finds its next candidate
             const int slot = bi >> 10, j0 = bi & 3;
 #pragma unroll
@@ -1217,6 +1222,36 @@ __global__ __launch_bounds__(256) void softmax_topk_rows_kernel(const float *log
                     if (q == slot && j == j0) x[q][j] = -INFINITY;
             local_best(lv, li);
         }
+    }
+    // 64 rounds without a break: the tie group may go on beyond them (more distinct logits within one float probability than the rounds
+    // visit, in descending LOGIT order), and an unvisited member may have a lower index than a visited one.  Then the group's share of the
+    // K is taken from the whole row instead: the n_gt winners above pK stay, and the K - n_gt lowest columns whose probability is pK follow,
+    // one block-wide minimum per slot.  (Block-uniform; a flat model with > 64 logits inside one float probability gets here.  A group that
+    // ends exactly at round 63 also does, harmlessly: the rescan returns the same columns.)
+    if (n == 64) {
+        int prev = -1;
+        for (int k = n_gt; k < K; ++k) {
+            int bi = 0x7FFFFFFF;
+            for (int v = threadIdx.x; v < V; v += 256) {  // this thread's lowest qualifying column
+                const float xv = row[v];
+                if (v > prev && (LOGP ? (xv - mx) - logf(se) : expf(xv - lse)) == pK) {
+                    bi = v;
+                    break;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) bi = min(bi, __shfl_xor(bi, o));
+            __syncthreads();
+            if ((threadIdx.x & 63) == 0) si[threadIdx.x >> 6] = bi;
+            __syncthreads();
+            bi = min(min(si[0], si[1]), min(si[2], si[3]));
+            if (threadIdx.x == 0) {
+                wi[k] = bi;
+                wv[k] = pK;
+            }
+            prev = bi;
+        }
+        n = K;
     }
     if (threadIdx.x == 0) {
         for (int k = 1; k < n; ++k) {  // equal probabilities (distinct logits, same float): ascending index

@@ -1062,14 +1062,19 @@ int decode_gates_epi(lrcn_ctx *c, const void *xh, int64_t ldxh, const void *Wcat
 // The logits GEMM of a batched decode step with softmax + top-K in its epilogue (gemm_8p.hip GEMM_OUT_SMAX_TOPK; round 6): x * w[end-1] .+ w[end]
 // (lrcn.jl:550) is reduced tile by tile to per-row records and merged by k_softmax_topk_merge -- the B x V f32 logits (218 MB per step at
 // 5120 x 10640) are never written, and softmax_topk_rows_kernel's pass over them disappears.  LRCN_DECODE_SMAX=0: GEMM + that kernel.
+int smax_nrec(const lrcn_ctx *c) { return 2 * ((c->V + 255) / 256); }
+// Where a logits GEMM of R rows may reduce to records at all (every record route -- the decode's and the scoring's -- asks here): bf16,
+// from 256 rows, V % 4 == 0, >= 2 K-tiles, and no more records per row than the merges hold (V <= 32768).  Elsewhere the f32 logits route.
+bool smax_records_on(const lrcn_ctx *c, int R) {
+    return c->dt == GEMM_T_BF16 && R >= 256 && c->V >= 256 && !(c->V & 3) && c->H2 > 64 && smax_nrec(c) <= SMAX_MAX_NREC;
+}
 bool decode_smax_on(const lrcn_ctx *c, int B, int K) {
     const char *k = getenv("LRCN_DECODE_SMAX");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && c->dt == GEMM_T_BF16 && B >= 256 && K < SMAX_KC && c->V >= 256 && !(c->V & 3) && c->H2 > 64;  // (>= 2 K-tiles)
+    return !(k && k[0] == '0') && K < SMAX_KC && smax_records_on(c, B);
 }
 // The same logits GEMM with any of the record epilogues (GEMM_OUT_SMAX_TOPK / _GUMBEL / _PICK) for M rows of h: every 128 columns of a row
 // reduce to one record of smax_part [M][smax_nrec][SMAX_REC] (allocated on first use, max_B rows).  e: the out-mode's own SmaxEpi fields
 // (GUMBEL: the draw parameters, PICK: the target columns); part and nrec are filled in here.
-int smax_nrec(const lrcn_ctx *c) { return 2 * ((c->V + 255) / 256); }
 int logits_records(lrcn_ctx *c, const void *hT, int64_t ldh, const float *bias, int M, int out_mode, const SmaxEpi &e) {
     const int nrec = smax_nrec(c);
     if (!c->smax_part) DALLOC(c, c->smax_part, sizeof(float) * (size_t)c->maxB * nrec * SMAX_REC);
@@ -1318,7 +1323,7 @@ void ctx_sizes(const lrcn_ctx *c, int64_t sz[9]) { lrcn_param_sizes_n(c->nl, c->
 // LRCN_SCORE_FUSED=0: the logits GEMM writes f32 logits and k_softmax_xent reduces them, at every row count
 bool score_fused_on(const lrcn_ctx *c, int R) {
     const char *k = getenv("LRCN_SCORE_FUSED");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && c->dt == GEMM_T_BF16 && R >= 256 && c->V >= 256 && !(c->V & 3) && c->H2 > 64;
+    return !(k && k[0] == '0') && smax_records_on(c, R);
 }
 
 // pair_img == NULL: the N x M matrix; else the P pairs.  See lrcn_score.h for the plan; the routes below are chosen once per piece.
