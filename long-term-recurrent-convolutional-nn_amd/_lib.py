@@ -14,6 +14,7 @@ HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn.h"))
 SAMPLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sample.h"))  # lrcn_sample_batch (not in lrcn.h)
 SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.h"))    # lrcn_score_matrix / _pairs (not in lrcn.h)
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
+ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -32,6 +33,11 @@ class Config(C.Structure):
     _fields_ = [("device", C.c_int), ("E", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("V", C.c_int),
                 ("max_B", C.c_int), ("max_T", C.c_int), ("lstm_dtype", C.c_int), ("vgg_dtype", C.c_int),
                 ("max_images", C.c_int), ("n_layers", C.c_int)]
+
+
+class ActConfig(C.Structure):   # lrcn_act_config of include/lrcn_activity.h
+    _fields_ = [("device", C.c_int), ("F", C.c_int), ("H", C.c_int), ("C", C.c_int), ("max_B", C.c_int), ("max_T", C.c_int),
+                ("dtype", C.c_int), ("deterministic", C.c_int)]
 
 
 class Dropout(C.Structure):
@@ -147,9 +153,24 @@ NBEST_SIGNATURES = {
 }
 
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_activity.h declares (bound by lib() as well)
+ACTIVITY_SIGNATURES = {
+    "lrcn_act_create": (C.c_int, [C.POINTER(ActConfig), C.POINTER(C.c_void_p)]),
+    "lrcn_act_destroy": (None, [C.c_void_p]),
+    "lrcn_act_last_error": (C.c_char_p, [C.c_void_p]),
+    "lrcn_act_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lrcn_act_param_sizes": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "lrcn_act_init_weights": (C.c_int, [C.c_void_p, P4, C.c_uint64]),
+    "lrcn_act_loss_grad": (C.c_int, [C.c_void_p, P4, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p,
+                                     C.POINTER(C.c_double)]),
+    "lrcn_act_predict": (C.c_int, [C.c_void_p, P4, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+}
+
+
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER]
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER,
+                                                                                                   ACTIVITY_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -169,7 +190,8 @@ def lib():
         # the one this process uses: import torch BEFORE the library so the dynamic linker binds to that instance.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
+                list(ACTIVITY_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
