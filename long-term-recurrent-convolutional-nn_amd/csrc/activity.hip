@@ -1,24 +1,19 @@
 // activity.hip -- LRCN activity recognition (include/lrcn_activity.h): one LSTM layer over per-frame features and a per-step softmax
-// head whose distributions are averaged over each clip's real frames.  The recurrence reuses the caption path's pieces (launch_gemm,
-// k_lstm_fwd / k_lstm_bwd, the fused bf16 step kernels of lstm_fused.hip, k_colsum, k_transpose_multi); the new kernels are
+// head whose distributions are averaged over each clip's real frames.  The recurrence is the caption model's (host.h lstm_recurrence_fwd /
+// _bwd: the fused bf16 step kernels of lstm_fused.hip or GEMM + k_lstm_fwd / k_lstm_bwd), with launch_gemm, k_colsum and k_transpose_multi
+// around it; the new kernels are
 //   act_frames_kernel -- the caller's clip-major column-major f32 features -> time-major rows X [t*B + b][f] (T) and, for the weight
 //                        gradient, their transpose X' [f][t*B + b] (T, zero K padding), in one pass through an LDS tile
 //   act_head_kernel   -- one workgroup per clip, its T logit rows in step order: log-softmax, the masked NLL term, dlogits, per-step
 //                        probabilities and the clip average (no atomics: the loss and the probabilities are reproducible bit for bit)
 //   act_loss_sum_kernel -- the per-clip NLL terms summed in clip order (double)
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <string>
-#include <vector>
 
 #include "../../include/lrcn_activity.h"
-#include "common.h"
-#include "gemm.h"
-#include "kernels.h"
+#include "host.h"
+
+using namespace lrcn_impl;
 
 namespace {
 
@@ -154,11 +149,6 @@ __global__ void act_loss_sum_kernel(const double *loss_clip, int B, double *out)
         out[0] = s;
     }
 }
-
-inline int64_t ld64(int64_t n) { return round_up64(n, 64); }
-inline char *boff(void *p, int64_t elems, size_t esz) { return reinterpret_cast<char *>(p) + elems * (int64_t)esz; }
-inline const char *boff(const void *p, int64_t elems, size_t esz) { return reinterpret_cast<const char *>(p) + elems * (int64_t)esz; }
-
 }  // namespace
 
 struct lrcn_act {
@@ -193,56 +183,11 @@ struct lrcn_act {
     bool up_pending = false;
 };
 
-#define AFAIL(a, code, ...)                      \
-    do {                                         \
-        char _b[512];                            \
-        snprintf(_b, sizeof(_b), __VA_ARGS__);   \
-        (a)->err = _b;                           \
-        return (code);                           \
-    } while (0)
-#define AHIP(a, expr)                                                                           \
-    do {                                                                                        \
-        hipError_t _e = (expr);                                                                 \
-        if (_e != hipSuccess) AFAIL(a, LRCN_EHIP, "%s: %s", #expr, hipGetErrorString(_e));      \
-    } while (0)
-#define AKCHK(a, what)                                                                          \
-    do {                                                                                        \
-        hipError_t _e = hipGetLastError();                                                      \
-        if (_e != hipSuccess) AFAIL(a, LRCN_EHIP, "%s: %s", what, hipGetErrorString(_e));       \
-    } while (0)
-
 namespace {
 
 std::string g_act_create_err;
 
-struct ActDeviceGuard {
-    int prev = -1;
-    bool switched = false;
-    explicit ActDeviceGuard(int dev) {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~ActDeviceGuard() {
-        if (switched) (void)hipSetDevice(prev);
-    }
-};
-
-template <class P> int act_alloc(lrcn_act *a, P *&p, size_t bytes) {
-    void *q = nullptr;
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(&q, bytes) != hipSuccess) AFAIL(a, LRCN_ENOMEM, "hipMalloc of %zu bytes failed", bytes);
-    a->allocs.push_back(q);
-    p = reinterpret_cast<P *>(q);
-    // zero padding from the start (K padding of the bf16 contractions); drained so that no later stream can overtake the fill
-    if (hipMemset(q, 0, bytes) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) AFAIL(a, LRCN_EHIP, "hipMemset failed");
-    return LRCN_OK;
-}
-#define AALLOC(a, p, bytes)                            \
-    do {                                               \
-        int _r = act_alloc(a, p, (size_t)(bytes));     \
-        if (_r) return _r;                             \
-    } while (0)
-
-// C[M][N] (+)= A[M][K] B[N][K]'; bf16 K rounded up to the operands' zero padding as the caption path does
+// C[M][N] (+)= A[M][K] B[N][K]' (K: gemm_k), deterministic split-K on the handle's own workspace
 int act_gemm(lrcn_act *a, const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int M, int N, int K, const float *bias,
              bool beta = false, bool c_is_zero = false) {
     GemmArgs g{};
@@ -251,7 +196,7 @@ int act_gemm(lrcn_act *a, const void *A, int64_t lda, const void *B, int64_t ldb
     g.B = B; g.ldb = ldb;
     g.C = C; g.ldc = ldc;
     g.M = M; g.N = N;
-    g.K = (a->dt == GEMM_T_BF16 && lda >= round_up64(K, 64) && ldb >= round_up64(K, 64)) ? (int)round_up64(K, 64) : K;
+    g.K = gemm_k(a->dt, lda, ldb, K);
     g.bias = bias;
     g.c_f32 = 1;
     g.beta = beta;
@@ -263,7 +208,7 @@ int act_gemm(lrcn_act *a, const void *A, int64_t lda, const void *B, int64_t ldb
     g.ws = a->ws;
     g.ws_bytes = a->ws_bytes;
     hipError_t e = launch_gemm(a->stream, g);
-    if (e != hipSuccess) AFAIL(a, LRCN_EHIP, "gemm M=%d N=%d K=%d: %s", M, N, K, hipGetErrorString(e));
+    if (e != hipSuccess) FAIL(a, LRCN_EHIP, "gemm M=%d N=%d K=%d: %s", M, N, K, hipGetErrorString(e));
     return LRCN_OK;
 }
 #define AGEMM(...)                       \
@@ -272,11 +217,11 @@ int act_gemm(lrcn_act *a, const void *A, int64_t lda, const void *B, int64_t ldb
         if (_r) return _r;               \
     } while (0)
 
-// the caption path's rule (lrcn_api.hip lstm_fused_on): the fused bf16 step kernels up to 128 rows, LRCN_LSTM_FUSED=0 turns them off
-bool act_fused_on(const lrcn_act *a, int B) {
-    const char *k = getenv("LRCN_LSTM_FUSED");
-    const char *mb = getenv("LRCN_LSTM_FUSED_MAXB");
-    return !(k && k[0] == '0') && B <= (mb ? atoi(mb) : 128) && lstm_fused_eligible(a->dt, B, a->cfg.H, a->ldH, a->ld4H);
+// the recurrence's plain-form GEMM (host.h lstm_recurrence_*)
+auto rec_gemm(lrcn_act *a) {
+    return [a](const void *A, int64_t lda, const void *B, int64_t ldb, float *C, int64_t ldc, int M, int N, int K, bool beta, bool c_is_zero) {
+        return act_gemm(a, A, lda, B, ldb, C, ldc, M, N, K, nullptr, beta, c_is_zero);
+    };
 }
 
 template <typename T> void launch_head(hipStream_t st, int nq, const float *logits, int64_t ldl, int Tn, int B, int C, const int32_t *labels,
@@ -293,26 +238,26 @@ template <typename T> void launch_head(hipStream_t st, int nq, const float *logi
 }
 
 int check_call(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B) {
-    if (!p || !p[0] || !p[1] || !p[2] || !p[3]) AFAIL(a, LRCN_EINVAL, "null parameter tensor");
-    if (!feats) AFAIL(a, LRCN_EINVAL, "null feats");
-    if (T < 1 || T > a->cfg.max_T) AFAIL(a, LRCN_EINVAL, "T=%d outside [1,%d]", T, a->cfg.max_T);
-    if (B < 1 || B > a->cfg.max_B) AFAIL(a, LRCN_EINVAL, "B=%d outside [1,%d]", B, a->cfg.max_B);
+    if (!p || !p[0] || !p[1] || !p[2] || !p[3]) FAIL(a, LRCN_EINVAL, "null parameter tensor");
+    if (!feats) FAIL(a, LRCN_EINVAL, "null feats");
+    if (T < 1 || T > a->cfg.max_T) FAIL(a, LRCN_EINVAL, "T=%d outside [1,%d]", T, a->cfg.max_T);
+    if (B < 1 || B > a->cfg.max_B) FAIL(a, LRCN_EINVAL, "B=%d outside [1,%d]", B, a->cfg.max_B);
     for (int b = 0; b < B; ++b) {
-        if (labels && (labels[b] < 0 || labels[b] >= a->cfg.C)) AFAIL(a, LRCN_EINVAL, "labels[%d]=%d outside [0,%d)", b, labels[b], a->cfg.C);
-        if (lens && (lens[b] < 1 || lens[b] > T)) AFAIL(a, LRCN_EINVAL, "lens[%d]=%d outside [1,%d]", b, lens[b], T);
+        if (labels && (labels[b] < 0 || labels[b] >= a->cfg.C)) FAIL(a, LRCN_EINVAL, "labels[%d]=%d outside [0,%d)", b, labels[b], a->cfg.C);
+        if (lens && (lens[b] < 1 || lens[b] > T)) FAIL(a, LRCN_EINVAL, "lens[%d]=%d outside [1,%d]", b, lens[b], T);
     }
     return LRCN_OK;
 }
 
 // labels (may be NULL) and lens (NULL = T) -> the device's meta array, through the pinned staging buffer (reused once the last upload ran)
 int upload_meta(lrcn_act *a, const int32_t *labels, const int32_t *lens, int T, int B) {
-    if (a->up_pending) AHIP(a, hipEventSynchronize(a->up_done));
+    if (a->up_pending) HIPCHK(a, hipEventSynchronize(a->up_done));
     for (int b = 0; b < B; ++b) {
         a->hmeta[b] = labels ? labels[b] : -1;
         a->hmeta[a->cfg.max_B + b] = lens ? lens[b] : T;
     }
-    AHIP(a, hipMemcpyAsync(a->dmeta, a->hmeta, sizeof(int32_t) * 2 * (size_t)a->cfg.max_B, hipMemcpyHostToDevice, a->stream));
-    AHIP(a, hipEventRecord(a->up_done, a->stream));
+    HIPCHK(a, hipMemcpyAsync(a->dmeta, a->hmeta, sizeof(int32_t) * 2 * (size_t)a->cfg.max_B, hipMemcpyHostToDevice, a->stream));
+    HIPCHK(a, hipEventRecord(a->up_done, a->stream));
     a->up_pending = true;
     return LRCN_OK;
 }
@@ -320,15 +265,13 @@ int upload_meta(lrcn_act *a, const int32_t *labels, const int32_t *lens, int T, 
 // frames -> Gx -> recurrence -> logits.  with_xt: also the transposed frames into TB (the weight gradient's operand).
 int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T, int B, bool bwd) {
     const int F = a->cfg.F, H = a->cfg.H, C = a->cfg.C, dt = a->dt, M = T * B;
-    const size_t es = a->esz;
     const int64_t ldF = a->ldF, ldH = a->ldH, ld4H = a->ld4H, ldC = a->ldC, ldM = ld64(M);
     hipStream_t st = a->stream;
     // parameter shadows (W memory [4H][F+H], Wout memory [C][H])
     k_cast_rows(st, dt, p[0], F + H, 4 * H, F, a->Wx, ldF);
     k_cast_rows(st, dt, p[0] + F, F + H, 4 * H, H, a->Wh, ldH);
     k_cast_rows(st, dt, p[2], H, C, H, a->Wo, ldH);
-    const bool fused = dt == GEMM_T_BF16 && act_fused_on(a, B);
-    if (bwd || fused) k_transpose(st, dt, 1, p[0] + F, F + H, 4 * H, H, a->WhT, ld4H, 0);
+    if (bwd || lstm_fused_on(dt, B, H, ldH, ld4H)) k_transpose(st, dt, 1, p[0] + F, F + H, 4 * H, H, a->WhT, ld4H, 0);
     if (bwd) k_transpose(st, dt, 1, p[2], H, C, H, a->WoT, ldC, 0);
     // frames, time-major (and transposed for dW)
     {
@@ -340,24 +283,12 @@ int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T,
             hipLaunchKernelGGL(act_frames_kernel<float>, grid, dim3(256), 0, st, feats, F, T, B, (float *)a->X, ldF,
                                bwd ? (float *)a->TB : nullptr, ldM);
     }
-    AKCHK(a, "shadows / frames");
+    KCHK(a, "shadows / frames");
     // input projection of every frame at once: Gx = X W[0:F] + b
     AGEMM(a, a->X, ldF, a->Wx, ldF, a->Gx, 4 * H, M, 4 * H, F, p[1]);
     // recurrence: contracts h only
-    for (int s = 0; s < T; ++s) {
-        float *G = a->Gx + (int64_t)s * B * 4 * H;
-        void *acts = boff(a->acts, (int64_t)s * B * ld4H, es), *h_new = boff(a->Hall, (int64_t)s * B * ldH, es);
-        const void *h_prev = s ? boff(a->Hall, (int64_t)(s - 1) * B * ldH, es) : nullptr;
-        float *c_prev = s ? a->Call + (int64_t)(s - 1) * B * H : nullptr, *c_new = a->Call + (int64_t)s * B * H;
-        if (s > 0 && fused) {
-            hipError_t e = launch_lstm_rec_fwd(st, h_prev, ldH, a->Wh, G, c_prev, B, H, acts, ld4H, c_new, h_new, a->zero_page, true);
-            if (e != hipSuccess) AFAIL(a, LRCN_EHIP, "lstm_rec_fwd: %s", hipGetErrorString(e));
-            continue;
-        }
-        if (s > 0) AGEMM(a, h_prev, ldH, a->Wh, ldH, G, 4 * H, B, 4 * H, H, nullptr, true);
-        k_lstm_fwd(st, dt, G, 4 * H, c_prev, B, H, acts, ld4H, c_new, h_new, ldH, nullptr);
-    }
-    AKCHK(a, "recurrence");
+    if (int r = lstm_recurrence_fwd(a, true, rec_gemm(a), T, B, H, ldH, ld4H, a->Gx, a->Wh, a->acts, a->Call, a->Hall)) return r;
+    KCHK(a, "recurrence");
     // logits of every step: z = h Wout + bout
     AGEMM(a, a->Hall, ldH, a->Wo, ldH, a->Logits, ldC, M, C, H, p[3]);
     return LRCN_OK;
@@ -384,29 +315,10 @@ int act_backward(lrcn_act *a, const float *const p[4], int T, int B, float *cons
     AGEMM(a, a->TA, ldM, boff(a->TB, (int64_t)(F + H) * ldM, es), ldM, g[2], H, C, H, M, nullptr);
     k_colsum(st, dt, a->dLog, ldC, M, C, g[3], det);
     AGEMM(a, a->dLog, ldC, a->WoT, ldC, a->dHall, H, M, H, C, nullptr);
-    AKCHK(a, "head backward");
+    KCHK(a, "head backward");
     // reverse recurrence -> dZ
-    if (dt == GEMM_T_BF16 && act_fused_on(a, B)) {
-        k_lstm_bwd(st, dt, boff(a->acts, (int64_t)(T - 1) * B * ld4H, es), ld4H, T > 1 ? a->Call + (int64_t)(T - 2) * B * H : nullptr,
-                   a->Call + (int64_t)(T - 1) * B * H, a->dHall + (int64_t)(T - 1) * B * H, H, nullptr, 0, a->dc, 1, B, H,
-                   boff(a->dZ, (int64_t)(T - 1) * B * ld4H, es), ld4H);
-        for (int s = T - 1; s >= 1; --s) {
-            hipError_t e = launch_lstm_rec_bwd(st, boff(a->dZ, (int64_t)s * B * ld4H, es), ld4H, a->WhT, boff(a->acts, (int64_t)(s - 1) * B * ld4H, es),
-                                               s > 1 ? a->Call + (int64_t)(s - 2) * B * H : nullptr, a->Call + (int64_t)(s - 1) * B * H,
-                                               a->dHall + (int64_t)(s - 1) * B * H, a->dc, B, H, boff(a->dZ, (int64_t)(s - 1) * B * ld4H, es),
-                                               a->zero_page, true);
-            if (e != hipSuccess) AFAIL(a, LRCN_EHIP, "lstm_rec_bwd: %s", hipGetErrorString(e));
-        }
-    } else {
-        for (int s = T - 1; s >= 0; --s) {
-            k_lstm_bwd(st, dt, boff(a->acts, (int64_t)s * B * ld4H, es), ld4H, s ? a->Call + (int64_t)(s - 1) * B * H : nullptr,
-                       a->Call + (int64_t)s * B * H, a->dHall + (int64_t)s * B * H, H, a->dhrec, s < T - 1, a->dc, s == T - 1, B, H,
-                       boff(a->dZ, (int64_t)s * B * ld4H, es), ld4H);
-            if (s > 0)  // dh_prev = dZ[s] Wh' (dhrec was zeroed by the cell kernel above)
-                AGEMM(a, boff(a->dZ, (int64_t)s * B * ld4H, es), ld4H, a->WhT, ld4H, a->dhrec, H, B, H, 4 * H, nullptr, false, true);
-        }
-    }
-    AKCHK(a, "recurrence backward");
+    if (int r = lstm_recurrence_bwd(a, true, rec_gemm(a), T, B, H, ld4H, a->acts, a->Call, a->dHall, a->WhT, a->dZ)) return r;
+    KCHK(a, "recurrence backward");
     // dW = dZ' [X | h_prev] in one GEMM (X' is already in TB rows [0, F)), db = colsum(dZ)
     {
         TrPlan pl{};
@@ -416,7 +328,7 @@ int act_backward(lrcn_act *a, const float *const p[4], int T, int B, float *cons
     }
     AGEMM(a, a->TA, ldM, a->TB, ldM, g[0], F + H, 4 * H, F + H, M, nullptr);
     k_colsum(st, dt, a->dZ, ld4H, M, 4 * H, g[1], det);
-    AKCHK(a, "weight gradients");
+    KCHK(a, "weight gradients");
     return LRCN_OK;
 }
 
@@ -437,7 +349,7 @@ const char *lrcn_act_last_error(const lrcn_act *a) { return a ? a->err.c_str() :
 
 void lrcn_act_destroy(lrcn_act *a) {
     if (!a) return;
-    ActDeviceGuard dg(a->cfg.device);
+    DeviceGuard dg(a->cfg.device);
     (void)hipDeviceSynchronize();
     for (void *p : a->allocs) (void)hipFree(p);
     if (a->hmeta) (void)hipHostFree(a->hmeta);
@@ -455,33 +367,33 @@ static int act_create_impl(lrcn_act *a) {
     const int64_t Mmax = (int64_t)c.max_B * c.max_T;
     a->ldMmax = ld64(Mmax);
     const size_t es = a->esz;
-    AALLOC(a, a->zero_page, 4096);
+    DALLOC(a, a->zero_page, 4096);
     a->ws_bytes = 48u << 20;
-    AALLOC(a, a->ws, a->ws_bytes);
-    AALLOC(a, a->Wx, es * 4 * H * a->ldF);
-    AALLOC(a, a->Wh, es * 4 * H * a->ldH);
-    AALLOC(a, a->WhT, es * H * a->ld4H);
-    AALLOC(a, a->Wo, es * C * a->ldH);
-    AALLOC(a, a->WoT, es * H * a->ldC);
-    AALLOC(a, a->X, es * Mmax * a->ldF);
-    AALLOC(a, a->TA, es * (size_t)(4 * H > C ? 4 * H : C) * a->ldMmax);
-    AALLOC(a, a->TB, es * (size_t)(F + 2 * H) * a->ldMmax);
-    AALLOC(a, a->Gx, sizeof(float) * Mmax * 4 * H);
-    AALLOC(a, a->acts, es * Mmax * a->ld4H);
-    AALLOC(a, a->Call, sizeof(float) * Mmax * H);
-    AALLOC(a, a->Hall, es * Mmax * a->ldH);
-    AALLOC(a, a->Logits, sizeof(float) * Mmax * a->ldC);
-    AALLOC(a, a->dLog, es * Mmax * a->ldC);
-    AALLOC(a, a->dHall, sizeof(float) * Mmax * H);
-    AALLOC(a, a->dZ, es * Mmax * a->ld4H);
-    AALLOC(a, a->dc, sizeof(float) * c.max_B * H);
-    AALLOC(a, a->dhrec, sizeof(float) * c.max_B * H);
-    AALLOC(a, a->loss_clip, sizeof(double) * c.max_B);
-    AALLOC(a, a->loss_sum, sizeof(double) * 2);
-    AALLOC(a, a->dmeta, sizeof(int32_t) * 2 * c.max_B);
-    AHIP(a, hipHostMalloc((void **)&a->hmeta, sizeof(int32_t) * 2 * c.max_B, hipHostMallocDefault));
-    AHIP(a, hipHostMalloc((void **)&a->hloss, sizeof(double) * 2, hipHostMallocDefault));
-    AHIP(a, hipEventCreateWithFlags(&a->up_done, hipEventDisableTiming));
+    DALLOC(a, a->ws, a->ws_bytes);
+    DALLOC(a, a->Wx, es * 4 * H * a->ldF);
+    DALLOC(a, a->Wh, es * 4 * H * a->ldH);
+    DALLOC(a, a->WhT, es * H * a->ld4H);
+    DALLOC(a, a->Wo, es * C * a->ldH);
+    DALLOC(a, a->WoT, es * H * a->ldC);
+    DALLOC(a, a->X, es * Mmax * a->ldF);
+    DALLOC(a, a->TA, es * (size_t)(4 * H > C ? 4 * H : C) * a->ldMmax);
+    DALLOC(a, a->TB, es * (size_t)(F + 2 * H) * a->ldMmax);
+    DALLOC(a, a->Gx, sizeof(float) * Mmax * 4 * H);
+    DALLOC(a, a->acts, es * Mmax * a->ld4H);
+    DALLOC(a, a->Call, sizeof(float) * Mmax * H);
+    DALLOC(a, a->Hall, es * Mmax * a->ldH);
+    DALLOC(a, a->Logits, sizeof(float) * Mmax * a->ldC);
+    DALLOC(a, a->dLog, es * Mmax * a->ldC);
+    DALLOC(a, a->dHall, sizeof(float) * Mmax * H);
+    DALLOC(a, a->dZ, es * Mmax * a->ld4H);
+    DALLOC(a, a->dc, sizeof(float) * c.max_B * H);
+    DALLOC(a, a->dhrec, sizeof(float) * c.max_B * H);
+    DALLOC(a, a->loss_clip, sizeof(double) * c.max_B);
+    DALLOC(a, a->loss_sum, sizeof(double) * 2);
+    DALLOC(a, a->dmeta, sizeof(int32_t) * 2 * c.max_B);
+    HIPCHK(a, hipHostMalloc((void **)&a->hmeta, sizeof(int32_t) * 2 * c.max_B, hipHostMallocDefault));
+    HIPCHK(a, hipHostMalloc((void **)&a->hloss, sizeof(double) * 2, hipHostMallocDefault));
+    HIPCHK(a, hipEventCreateWithFlags(&a->up_done, hipEventDisableTiming));
     return LRCN_OK;
 }
 
@@ -513,7 +425,7 @@ int lrcn_act_create(const lrcn_act_config *cfg, lrcn_act **out) {
         g_act_create_err = "device " + std::to_string(c.device) + " not present";
         return LRCN_EINVAL;
     }
-    ActDeviceGuard dg(c.device);
+    DeviceGuard dg(c.device);
     lrcn_act *a = new lrcn_act();
     a->cfg = c;
     const int r = act_create_impl(a);
@@ -534,8 +446,8 @@ int lrcn_act_set_stream(lrcn_act *a, void *stream) {
 
 int lrcn_act_init_weights(lrcn_act *a, float *const p[4], uint64_t seed) {
     if (!a) return LRCN_EINVAL;
-    if (!p || !p[0] || !p[1] || !p[2] || !p[3]) AFAIL(a, LRCN_EINVAL, "null parameter tensor");
-    ActDeviceGuard dg(a->cfg.device);
+    if (!p || !p[0] || !p[1] || !p[2] || !p[3]) FAIL(a, LRCN_EINVAL, "null parameter tensor");
+    DeviceGuard dg(a->cfg.device);
     const int F = a->cfg.F, H = a->cfg.H, C = a->cfg.C;
     hipStream_t st = a->stream;
     // the rule of lrcn_init_weights (tensor keys 0 and 7: the caption model's W1 and Wout slots)
@@ -544,18 +456,18 @@ int lrcn_act_init_weights(lrcn_act *a, float *const p[4], uint64_t seed) {
     k_fill(st, p[1], H, 1.0f);  // forget-gate bias
     k_init_uniform(st, p[2], (int64_t)H * C, (float)std::sqrt(2.0 / ((double)H + (double)C)), seed, 7);
     k_fill(st, p[3], C, 0.0f);
-    AKCHK(a, "init_weights");
+    KCHK(a, "init_weights");
     return LRCN_OK;
 }
 
 int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
                        float *const g[4], double *loss_host) {
     if (!a) return LRCN_EINVAL;
-    if (!labels) AFAIL(a, LRCN_EINVAL, "null labels");
-    if (g && (!g[0] || !g[1] || !g[2] || !g[3])) AFAIL(a, LRCN_EINVAL, "null gradient tensor");
+    if (!labels) FAIL(a, LRCN_EINVAL, "null labels");
+    if (g && (!g[0] || !g[1] || !g[2] || !g[3])) FAIL(a, LRCN_EINVAL, "null gradient tensor");
     int r = check_call(a, p, feats, labels, lens, T, B);
     if (r) return r;
-    ActDeviceGuard dg(a->cfg.device);
+    DeviceGuard dg(a->cfg.device);
     int64_t total = 0;
     for (int b = 0; b < B; ++b) total += lens ? lens[b] : T;
     if ((r = upload_meta(a, labels, lens, T, B))) return r;
@@ -570,11 +482,11 @@ int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats,
         launch_head<float>(a->stream, nq, a->Logits, a->ldC, T, B, a->cfg.C, a->dmeta, a->dmeta + a->cfg.max_B, scale, bwd ? a->dLog : nullptr,
                            a->ldC, a->loss_clip, nullptr, nullptr);
     hipLaunchKernelGGL(act_loss_sum_kernel, dim3(1), dim3(64), 0, a->stream, a->loss_clip, B, a->loss_sum);
-    AKCHK(a, "head");
+    KCHK(a, "head");
     if (bwd && (r = act_backward(a, p, T, B, g))) return r;
     if (loss_host) {
-        AHIP(a, hipMemcpyAsync(a->hloss, a->loss_sum, sizeof(double), hipMemcpyDeviceToHost, a->stream));
-        AHIP(a, hipStreamSynchronize(a->stream));
+        HIPCHK(a, hipMemcpyAsync(a->hloss, a->loss_sum, sizeof(double), hipMemcpyDeviceToHost, a->stream));
+        HIPCHK(a, hipStreamSynchronize(a->stream));
         *loss_host = a->hloss[0] / (double)total;
     }
     return LRCN_OK;
@@ -583,10 +495,10 @@ int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats,
 int lrcn_act_predict(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *lens, int T, int B, float *clip_probs,
                      float *frame_probs) {
     if (!a) return LRCN_EINVAL;
-    if (!clip_probs) AFAIL(a, LRCN_EINVAL, "null clip_probs");
+    if (!clip_probs) FAIL(a, LRCN_EINVAL, "null clip_probs");
     int r = check_call(a, p, feats, nullptr, lens, T, B);
     if (r) return r;
-    ActDeviceGuard dg(a->cfg.device);
+    DeviceGuard dg(a->cfg.device);
     if ((r = upload_meta(a, nullptr, lens, T, B))) return r;
     if ((r = act_forward(a, p, feats, T, B, false))) return r;
     const int nq = cdiv(a->cfg.C, 256);
@@ -596,7 +508,7 @@ int lrcn_act_predict(lrcn_act *a, const float *const p[4], const float *feats, c
     else
         launch_head<float>(a->stream, nq, a->Logits, a->ldC, T, B, a->cfg.C, nullptr, a->dmeta + a->cfg.max_B, 0.0f, nullptr, 0, nullptr,
                            clip_probs, frame_probs);
-    AKCHK(a, "head");
+    KCHK(a, "head");
     return LRCN_OK;
 }
 

@@ -1,0 +1,231 @@
+// ctx.h -- the caption model's context (struct lrcn_ctx, opaque at the ABI) and the internal helpers that more than one of its
+// files needs: lrcn_api.hip (context, training, update), decode.hip (beam search, sampling, n-best, scoring), vgg.hip (VGG-16 forward).
+#pragma once
+#include <utility>
+
+#include "comm.h"
+#include "host.h"
+
+namespace lrcn_impl {
+
+struct VggLayer {
+    void *w = nullptr;    // [Cout][9*Cin] T (conv) ; conv1_1: [64][32]
+    void *w_fused = nullptr;  // conv1_1 only (bf16): [64][32] in the K order of the fused conv1_1+conv1_2 kernel
+    float *b = nullptr;   // [Cout] f32
+    int Cin = 0, Cout = 0, S = 0, pool = 0;
+    // LRCN_FP8 (layers conv2_2 .. conv5_3): e4m3 weights [Cout][9*Cin], per-channel weight scale, effective epilogue scale/bias
+    void *w8 = nullptr;
+    float *sw = nullptr, *escale = nullptr, *ebias = nullptr;
+};
+constexpr int kFp8First = 3;  // conv2_2: the first layer with Cin % 128 == 0
+
+}  // namespace lrcn_impl
+
+struct lrcn_ctx {
+    lrcn_config cfg{};
+    hipStream_t stream = nullptr;
+    std::string err;
+    std::vector<void *> allocs;
+    int dt = 0, vdt = 0;
+    size_t esz = 4, vesz = 4;
+    int E = 0, H1 = 0, H2 = 0, h = 0, V = 0, maxB = 0, maxS = 0;
+    int nl = 2;             // LSTM layers: 2 = the reference's LRCN-2f (lrcn.jl:540-551), 1 = LRCN-1f (BASELINE configs[1])
+    int X1 = 0;             // input width of LSTM-1: E (2 layers) or E + h = [embedding | x_cnn] (1 layer)
+    int64_t ldX1 = 0;
+    int64_t ldE = 0, ldH1 = 0, ldH2 = 0, ldh = 0, ld4H1 = 0, ld4H2 = 0, ldV = 0, ldM = 0, ldB = 0;
+    // shadow weights (T)
+    void *W1x = nullptr, *W1h = nullptr, *W1xT = nullptr, *W1hT = nullptr;
+    // decode only: [x | h] concatenated along K -- weights [4H][ldXH] and the step inputs [B][ldXH]: one gate GEMM per LSTM
+    void *W1cat = nullptr, *W2cat = nullptr, *st_xh1 = nullptr, *st_xh2 = nullptr;
+    int64_t ldXH1 = 0, ldXH2 = 0;
+    void *W2x = nullptr, *W2h = nullptr, *W2xT = nullptr, *W2hT = nullptr;
+    // batched decode with input-projection TABLES (round 6; decode_tables_on): T1 [V][4H1] = Wembed W1x + b1 per TOKEN, U2 [images][4H2] =
+    // x_cnn W2x(right half) + b2 per IMAGE (f32, gate-block columns), the gate GEMMs' operands A1 = h1[parent] and A2 = [h1 Wproj | h2[parent]],
+    // W2's matching weights (x_cnn columns left out, rows interleaved) and the image of every hypothesis row; all lazily allocated
+    float *dec_T1 = nullptr, *dec_U2 = nullptr;
+    void *dec_A1 = nullptr, *dec_A2 = nullptr, *dec_W2c = nullptr, *dec_Aimg = nullptr;
+    int32_t *dec_img = nullptr;
+    float *smax_part = nullptr;             // [maxB][2 ceil(V / 256)][SMAX_REC]: the logits GEMM's softmax / top-K records of a batched decode step (round 6), lazily
+    void *alt_gi[2] = {nullptr, nullptr};   // LRCN_OPT_FUSED_UPDATE: the second set's gate-interleaved copies (round 6), written by the Adam kernel
+    bool gi_live = false;                   // a training call has taken the cell-epilogue route: the fused update keeps the interleaved copies current
+    bool shadow_has_gi = false;             // ... and the current set's were made by it
+    void *W1h_gi = nullptr, *W2h_gi = nullptr;  // recurrent weights with (unit, gate)-interleaved rows (gemm_8p.hip LSTM_FWD epilogue), lazily
+    void *Wpd = nullptr, *WpT = nullptr, *Wcd = nullptr, *WeT = nullptr, *Wod = nullptr, *WoT = nullptr;
+    // LRCN_OPT_FUSED_UPDATE: the second set of the 14 training shadows above.  The Adam kernel of a train step writes the NEXT step's
+    // shadows into it while (per-group pipeline) the backward pass may still be reading the current set; then the two sets swap roles.
+    void *alt[14] = {};
+    bool opt_fused = false, opt_det = false;
+    int64_t conv_chunk_bytes = 0;           // LRCN_OPT_CONV_CHUNK_BYTES (0 = default)
+    unsigned fused_groups = 0;              // gradient groups whose fused Adam has been issued in the current step (bit per group)
+    int fused_step = 0;                     // the `step` those bits belong to: a call with another step starts a new mask
+    unsigned refresh_groups = 0;            // lrcn_refresh_shadows_group: groups whose shadows of the NEXT step have been issued
+    bool shadow_valid = false;              // the current set holds the shadows (direct AND transposed) of the parameters at shadow_p
+    const float *shadow_p[9] = {};
+    float *dWe_rm = nullptr;                // [V][ldE] f32, all zero between calls: row-major staging of the embedding gradient
+    unsigned long long *sort_keys = nullptr;  // [maxS * maxB] (token, row) keys of the ordered embedding-gradient sums
+    double *logp_rows = nullptr;            // [maxS * maxB] per-row log p(target): the ordered loss sum of LRCN_OPT_DETERMINISTIC
+    // sparse exchange of the embedding gradient (lrcn_set_embed_rows_buffer): lossgradient writes its (T+1) B rows of d(x_lstm) and their
+    // token ids HERE instead of scattering them into the dense gradient; lrcn_embed_grad_from_rows sums the rows of all ranks in a fixed order
+    float *emb_rows_out = nullptr;
+    int32_t *emb_tok_out = nullptr;
+    int emb_rows_cap = 0;
+    unsigned long long *imp_keys = nullptr;  // [8192] sort keys of lrcn_embed_grad_from_rows
+    // activations
+    int32_t *tok = nullptr, *tok_in = nullptr, *tok_tgt = nullptr;
+    void *F = nullptr, *FT = nullptr;
+    float *xcnn = nullptr;
+    void *Xemb = nullptr, *A1 = nullptr, *H1all = nullptr, *X2 = nullptr, *A2 = nullptr, *H2all = nullptr;
+    float *G1 = nullptr, *C1 = nullptr, *G2 = nullptr, *C2 = nullptr, *Logits = nullptr;
+    void *dLog = nullptr, *dZ1 = nullptr, *dZ2 = nullptr, *dX2 = nullptr;
+    float *dH1all = nullptr, *dH2all = nullptr, *dXemb = nullptr, *dhrec = nullptr, *dc = nullptr, *dxcnn = nullptr;
+    void *TA = nullptr, *TB = nullptr;  // transposed-operand scratch: up to [max(4H,V)][ldM] and [max(2*H2, E+H1)][ldM]
+    void *dxcT = nullptr;
+    double *logp = nullptr;
+    void *zero_page = nullptr;
+    hipEvent_t grad_ev[LRCN_GRAD_GROUPS] = {};  // recorded when the gradients of a group are final (lrcn_grad_group_wait)
+    void *gemm_ws = nullptr;  // split-K slabs of gemm_8p / gemm_skinny (LSTM side)
+    void *vgg_ws = nullptr;   // same for fc6/fc7: the VGG forward may run on another stream, concurrently with the LSTM step
+    size_t gemm_ws_bytes = 0;
+    int last_norm = 1, last_S = 1;
+    int cur_B = 0;  // rows of the loss / lossgradient call in flight (the "beside the convolutions" GEMM hints apply from 256 rows)
+    // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
+    float *st_f32[4] = {nullptr, nullptr, nullptr, nullptr};   // h1,c1,h2,c2 [B][H]
+    // the other buffer of each state pair: the target of the single-image beam's gather and of the batched decode's k_gather_state, and
+    // the c(t) output of the batched decode's cell epilogues (decode_step swaps the pairs after a step)
+    float *st2_f32[4] = {nullptr, nullptr, nullptr, nullptr};
+    void *st_h1 = nullptr, *st_h2 = nullptr, *st_x = nullptr, *st_x2 = nullptr, *st_a = nullptr;
+    float *st_g = nullptr, *st_logits = nullptr, *st_prob = nullptr, *st_io = nullptr, *st_topv = nullptr;
+    int32_t *st_topi = nullptr, *st_parent = nullptr;
+    // the batched decode (decode_begin / decode_step; lrcn_beam_search_batch and lrcn_sample_batch): token histories (ping-pong for the
+    // beam's reorder; the sampler's rows keep bs_seq[0]), next input tokens, done flags and counter, results -- all on the device.  The
+    // sampler keeps its lengths in bs_res_len and its log-likelihoods in bs_p; bs_res_tok / bs_res_p are the beams' (the n-best beam's
+    // results: [N*K] entries in bs_res_tok / bs_res_len / bs_res_p, scores in nb_res_score)
+    int32_t *bs_seq[2] = {nullptr, nullptr}, *bs_last = nullptr, *bs_done = nullptr, *bs_ndone = nullptr, *bs_res_tok = nullptr,
+            *bs_res_len = nullptr;
+    float *bs_p = nullptr, *bs_res_p = nullptr;
+    // lrcn_beam_nbest_batch (include/lrcn_nbest.h), lazily on its first call: the pool's token storage [maxB][2][LRCN_BEAM_MAXLEN] (2K rows per
+    // image), the pool [maxB] {score, logp, storage row, length}, per image {live slots, pool count, done}, live cum [maxB], scores out
+    int32_t *nb_store = nullptr;
+    int4 *nb_pool = nullptr, *nb_img = nullptr;
+    float *nb_cum = nullptr, *nb_res_score = nullptr;
+    // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
+    void *sc_arena = nullptr;
+    size_t sc_bytes = 0;
+    // VGG
+    int vgg_wg_cap = 0;  // > 0: cap on the convolution grids (lrcn_vgg_set_wg_cap)
+    bool vgg_loaded = false;
+    bool vgg_fp8 = false, fp8_ready = false;  // LRCN_FP8: conv2_2..conv5_3 in e4m3 once lrcn_vgg_calibrate has run
+    float *amax_dev = nullptr;                // [13] per-layer output amax collected by the calibration pass
+    float act_scale[13] = {};                 // sa of layer l's output (l = 2..12)
+    lrcn_impl::VggLayer conv[13];
+    void *fc6w = nullptr, *fc7w = nullptr;
+    float *fc6b = nullptr, *fc7b = nullptr;
+    void *actA = nullptr, *actB = nullptr, *im2col = nullptr, *f6 = nullptr, *img16 = nullptr;
+    float *featsRM = nullptr;  // [N][4096] f32 row-major
+    // live timing of the dominant kernel (the 12 implicit-GEMM conv launches conv1_2..conv5_3), see lrcn_profile*
+    bool prof = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
+    size_t prof_used = 0;
+    double prof_ms = 0.0;
+    int64_t prof_launches = 0;
+    // level 2 (lrcn_profile(ctx, 2)): event pairs around the HBM-bound segments of SURVEY 8(d), see lrcn_profile_segment
+    int prof_level = 0;
+    struct SegProf {
+        std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
+        size_t used = 0;
+        double ms = 0.0, bytes = 0.0;
+        int64_t n = 0;
+    } seg[LRCN_SEG_COUNT];
+    std::string vgg_routes;  // kernel family per layer of the most recent VGG forward (lrcn_debug_route)
+    // image front end: the full averageImage (lrcn_set_average_image), per-batch image descriptors, float scratch of the unfused path
+    float *avg_img = nullptr;
+    bool avg_on = false;
+    void *img_meta = nullptr;
+    int img_meta_cap = 0;
+    float *pre_f32 = nullptr;
+    // data parallelism: RCCL communicator (lrcn_comm_init) and one stream per gradient group for [all-reduce -> Adam]
+    // weight-gradient stream: the dW / db GEMMs of lossgradient feed nothing but update!, so they run on their own stream beside the
+    // reverse recurrences (which are chains of small launches that leave CUs idle); own split-K workspace, fork / join by events
+    hipStream_t wg_stream = nullptr;
+    bool wg_stream_owned = true;   // false: handed in through lrcn_set_wg_stream (not destroyed here)
+    hipEvent_t wg_fork[4] = {}, wg_done = nullptr;
+    hipEvent_t xc_fork = nullptr, xc_done = nullptr;  // the image-embedding GEMM of the forward pass on the weight-gradient stream (loss_impl)
+    void *wg_ws = nullptr;
+    void *pin = nullptr;      // pinned host staging for results larger than HIP's fast pageable-copy path (lrcn_beam_search_batch)
+    size_t pin_bytes = 0;
+    unsigned long long *stamps = nullptr;  // kernel-development: per-tile segment stamps (LRCN_STAMPS=1, lrcn_debug_stamps)
+    int64_t stamps_n = 0;
+    int *tile_ctr = nullptr;  // per-layer work queues of the capped persistent convolution grids (GemmArgs::tile_ctr)
+    // input feed (lrcn_upload_crops): uint8 crops travel host -> HBM on the context's own copy stream into one of kStage staging buffers,
+    // beside the running step; a VGG forward that is handed a staging buffer waits (on the device) for its upload, and the upload into a
+    // staging buffer waits for the one kernel of the forward that last read it (the crops are consumed by the forward's FIRST kernel).
+    // The copy stream never carries a device-side wait for a read that has not happened yet.  Measured (bench.py, host 4 steps ahead of the
+    // device, which is where it runs when nothing holds it back): a hipStreamWaitEvent on an event one or two steps in the device's future
+    // is a barrier packet at the head of a HARDWARE queue that the copy stream shares with compute streams (HIP maps its streams onto a few
+    // hardware queues) -- kernels queued behind it stall, and the step ran 8.5 instead of 7.0 ms until the host happened to fall back.  So an
+    // upload whose staging buffer is still unread BLOCKS THE CALLING THREAD (hipEventSynchronize) and then queues a copy with no dependency.
+    // With kStage buffers that happens only when the host is more than kStage - 1 steps ahead of the device: a bound on the run-ahead.
+    static constexpr int kStage = 3;
+    hipStream_t copy_stream = nullptr;
+    uint8_t *stage[kStage] = {};
+    hipEvent_t up_done[kStage] = {}, rd_done[kStage] = {};
+    bool stage_full[kStage] = {};   // holds crops that no forward has been issued on yet
+    bool stage_read[kStage] = {};   // rd_done[j] has been recorded at least once
+    int stage_next = 0;
+    LrcnComm *comm = nullptr;
+    hipStream_t comm_stream = nullptr;  // every collective of the communicator is issued on this ONE stream, in group order
+    bool comm_stream_owned = false;     // created here (destroyed here), or handed in through lrcn_comm_set_stream
+    // bucket[g] == comm_stream for every g since round 4: the groups become final in order, so one stream runs [wait, all-reduce, Adam] of
+    // group after group and loses nothing, while five streams on HIP's four hardware queues meant that one of them shared a queue with the
+    // VGG side stream and its Adam waited for the whole forward (dp.py streams_share_a_queue)
+    hipStream_t bucket[LRCN_GRAD_GROUPS] = {};
+    hipEvent_t ar_done[LRCN_GRAD_GROUPS] = {};
+    hipEvent_t bucket_done[LRCN_GRAD_GROUPS] = {};
+    bool bucket_pending[LRCN_GRAD_GROUPS] = {};
+};
+
+namespace lrcn_impl {
+
+// A pair of HIP events around one segment of a call, on the stream its work is launched on (lrcn_profile level 2; a no-op otherwise).
+struct SegScope {
+    lrcn_ctx *c;
+    hipStream_t st;
+    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
+    SegScope(lrcn_ctx *c_, int seg, hipStream_t st_, double bytes) : c(c_), st(st_) {
+        if (c->prof_level < 2) return;
+        auto &sp = c->seg[seg];
+        if (sp.used == sp.ev.size()) {
+            std::pair<hipEvent_t, hipEvent_t> e;
+            if (hipEventCreate(&e.first) != hipSuccess || hipEventCreate(&e.second) != hipSuccess) return;
+            sp.ev.push_back(e);
+        }
+        ev = &sp.ev[sp.used++];
+        sp.bytes += bytes;
+        sp.n += 1;
+        (void)hipEventRecord(ev->first, st);
+    }
+    ~SegScope() {
+        if (ev) (void)hipEventRecord(ev->second, st);
+    }
+};
+
+// C[M][N] (+)= A[M][K] * B[N][K]^T on the context's stream or (on_wg_stream) its weight-gradient stream, with its route hints (lrcn_api.hip)
+int gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int M, int N, int K,
+         const float *bias, bool c_f32, bool beta = false, bool relu = false, bool c_is_zero = false, bool on_wg_stream = false);
+
+#define GEMM(...)                     \
+    do {                              \
+        int _r = gemm(__VA_ARGS__);   \
+        if (_r) return _r;            \
+    } while (0)
+
+// f32 column-major params -> K-contiguous shadows in T (lrcn_api.hip; see DESIGN.md "shadow weights")
+int prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_bwd, bool cat = false, bool gi = false, bool cat_perm = false,
+                    bool dec_tables = false);
+// lrcn() on the context's single-step buffers (lrcn_api.hip): lrcn_step and the single-image beam search
+int step_internal(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2, bool h_ready = false);
+// the VGG-16 forward of N images into featsRM (vgg.hip): lrcn_train_step_dp and the image entry points
+int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean, bool calibrate = false);
+int vgg_check(lrcn_ctx *c, int N);
+
+}  // namespace lrcn_impl

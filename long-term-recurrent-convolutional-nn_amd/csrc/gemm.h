@@ -15,7 +15,7 @@ enum { GEMM_OUT_PLAIN = 0, GEMM_OUT_CONV = 1, GEMM_OUT_POOL = 2, GEMM_OUT_LSTM_F
 // 28 MB of records.  A record is SMAX_REC floats (64 bytes): [0] max, [1] sum, [2 .. 2+KC) values, [8 .. 8+KC) column ids (int bits).
 enum { SMAX_KC = 6, SMAX_REC = 16 };
 // The records merges (softmax_topk_merge_kernel, sample_*_merge_kernel, score_pick_merge_kernel) hold at most 4 records per lane of one wave:
-// a row of more than SMAX_MAX_NREC records (V > 32768) takes the f32-logits route instead (lrcn_api.hip smax_records_on).
+// a row of more than SMAX_MAX_NREC records (V > 32768) takes the f32-logits route instead (decode.hip smax_records_on).
 enum { SMAX_MAX_NREC = 256 };
 // GEMM_OUT_SMAX_GUMBEL (the sampled decode, lrcn_sample_batch): the same tiles and records, but instead of the top-K list a record carries the
 // Gumbel-max winner of its 128 columns: [0] max, [1] sum exp(x - max), [2] best z / T + g (T = 0: best z), [3] its column (int bits), [4] its z.

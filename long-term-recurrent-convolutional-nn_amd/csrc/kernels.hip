@@ -1434,7 +1434,7 @@ __global__ __launch_bounds__(256) void decode_prep_kernel(const bf16_t *wembT, i
     }
 }
 
-// The prep launch of the decode step with input-projection TABLES (lrcn_api.hip decode_tables; round 6): the gate GEMMs contract the hidden
+// The prep launch of the decode step with input-projection TABLES (decode.hip decode_tables; round 6): the gate GEMMs contract the hidden
 // state alone, so only the parents' h move -- h1[parent] into the rows of A1, h2[parent] into the h block of A2 = [h1 Wproj | h2].
 __global__ __launch_bounds__(256) void decode_prep_h_kernel(const int32_t *parent, const bf16_t *h1, int64_t ld_h1, int H1, const bf16_t *h2,
                                                             int64_t ld_h2, int H2, bf16_t *a1, int64_t ld_a1, bf16_t *a2, int64_t ld_a2, int64_t off_h2) {

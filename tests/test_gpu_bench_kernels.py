@@ -186,7 +186,7 @@ def test_beam_width_larger_than_vocabulary_is_rejected():
 
 def test_vgg_forward_with_layer_inputs_beyond_4GiB_equals_256_image_chunks(biased_vgg):
     # 1280 images: conv2_2's bf16 input is 4.1 GB, past what the direct-to-LDS kernels address with 32-bit offsets -- the layer is cut
-    # into launches of whole images (lrcn_api.hip launch_conv_chunked) instead of falling through to the register-staged kernel.
+    # into launches of whole images (vgg.hip launch_conv_chunked) instead of falling through to the register-staged kernel.
     # Same kernels, same tiles per image => the features equal those of five 256-image forwards (fc6/fc7 split K differently: 1e-3).
     w, _ = biased_vgg
     N = 1280

@@ -1,4 +1,4 @@
-"""GPU: the > 4 GiB input cut of the implicit-GEMM convolutions (lrcn_api.hip launch_conv_chunked: per-chunk A / C pointer offsets,
+"""GPU: the > 4 GiB input cut of the implicit-GEMM convolutions (vgg.hip launch_conv_chunked: per-chunk A / C pointer offsets,
 pooled versus un-pooled output stride, per-chunk M) -- a product path for max_images above ~1171 that no ordinary test batch reaches.
 LRCN_OPT_CONV_CHUNK_BYTES lowers the cut so that a handful of images already runs as several launches per layer; the features must be the
 single-launch features.  Where a chunk is small enough to change a layer's kernel route (split-K below 64 / 16 images) the
