@@ -27,11 +27,11 @@
 // work, slower than two launches; the u8 -> bf16 - mean pass is now a 25 us elementwise pre-kernel.)
 // LDS patch image: pixel q = py*18 + px at q*128 bytes, 16-byte chunk c at position c ^ g(py,px),
 //   g = (((px >> 1) & 3) << 1) | (py & 1): conflict-free for the 16-lane groups of ds_read_b128 at every tap shift.
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "gemm.h"
+#include "knob.h"
 
 namespace {
 
@@ -610,10 +610,8 @@ hipError_t launch_conv64_fused11(hipStream_t stream, const void *img16, const vo
                                  const float *bias, void *out, int N, int S, const void *zero_page, int wg_cap, unsigned long long *stamps) {
     if (!img16 || !w11 || !b11 || !w || !out || !zero_page || N < 1 || S < 16 || (S % 16)) return hipErrorInvalidValue;
     if ((int64_t)N * (S + 4) * (S + 4) * 3 >= (1ll << 31)) return hipErrorInvalidValue;
-    {
-        const char *gen = getenv("LRCN_FUSE11_GEN");  // 1: this file's alternating kernel (round 3); default: conv64f.hip
-        if (!(gen && gen[0] == '1')) return launch_conv64f(stream, img16, w11, w, bias, out, N, S, zero_page, wg_cap, stamps);
-    }
+    // LRCN_FUSE11_GEN=1: this file's alternating kernel (round 3); default: conv64f.hip
+    if (knob_char("LRCN_FUSE11_GEN") != '1') return launch_conv64f(stream, img16, w11, w, bias, out, N, S, zero_page, wg_cap, stamps);
     Conv64Args a{};
     a.w = reinterpret_cast<const bf16_t *>(w);
     a.bias = bias;

@@ -87,7 +87,7 @@ struct lrcn_ctx {
     void *vgg_ws = nullptr;   // same for fc6/fc7: the VGG forward may run on another stream, concurrently with the LSTM step
     size_t gemm_ws_bytes = 0;
     int last_norm = 1, last_S = 1;
-    int cur_B = 0;  // rows of the loss / lossgradient call in flight (the "beside the convolutions" GEMM hints apply from 256 rows)
+    int cur_B = 0;  // rows of the loss / lossgradient call in flight (gemm() picks its "beside the convolutions" hint by it)
     // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
     float *st_f32[4] = {nullptr, nullptr, nullptr, nullptr};   // h1,c1,h2,c2 [B][H]
     // the other buffer of each state pair: the target of the single-image beam's gather and of the batched decode's k_gather_state, and
@@ -112,6 +112,7 @@ struct lrcn_ctx {
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;
     // VGG
+    int ncu = 0;         // compute units of cfg.device (lrcn_create)
     int vgg_wg_cap = 0;  // > 0: cap on the convolution grids (lrcn_vgg_set_wg_cap)
     bool vgg_loaded = false;
     bool vgg_fp8 = false, fp8_ready = false;  // LRCN_FP8: conv2_2..conv5_3 in e4m3 once lrcn_vgg_calibrate has run
@@ -185,6 +186,10 @@ struct lrcn_ctx {
 };
 
 namespace lrcn_impl {
+
+// Nothing runs beside the LSTM step: no VGG forward with capped grids on another stream (what the two-stream trainer sets up).  Its negation
+// is THE test for "beside the capped convolutions"; the routes that apply there to 256..512 rows also ask bg_row_window (gemm.h).
+inline bool lstm_alone(const lrcn_ctx *c) { return !(c->vgg_wg_cap >= 8 && c->vgg_loaded); }
 
 // A pair of HIP events around one segment of a call, on the stream its work is launched on (lrcn_profile level 2; a no-op otherwise).
 struct SegScope {

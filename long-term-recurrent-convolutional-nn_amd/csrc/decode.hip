@@ -23,8 +23,7 @@ namespace {
 // weights are then made with (unit, gate)-interleaved rows (prepare_weights cat_perm), the bias rides in as a broadcast row, the
 // activated gates are not kept (no backward pass).  LRCN_DECODE_EPI=0: GEMM + cell kernel as before.
 bool decode_epi_on(const lrcn_ctx *c, int B) {
-    const char *k = getenv("LRCN_DECODE_EPI");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && c->dt == GEMM_T_BF16 && B >= 256 && !(c->H1 & 3) && !(c->H2 & 3);
+    return !knob_off("LRCN_DECODE_EPI") && c->dt == GEMM_T_BF16 && B >= 256 && !(c->H1 & 3) && !(c->H2 & 3);
 }
 int decode_gates_epi(lrcn_ctx *c, const void *xh, int64_t ldxh, const void *Wcat, int K, const float *bias, int B, int H, const float *c_prev,
                      const int32_t *c_prev_idx, float *c_out, void *h_out, int64_t ld_h_out, const int32_t *gx_idx = nullptr) {
@@ -64,8 +63,7 @@ bool smax_records_on(const lrcn_ctx *c, int R) {
     return c->dt == GEMM_T_BF16 && R >= 256 && c->V >= 256 && !(c->V & 3) && c->H2 > 64 && smax_nrec(c) <= SMAX_MAX_NREC;
 }
 bool decode_smax_on(const lrcn_ctx *c, int B, int K) {
-    const char *k = getenv("LRCN_DECODE_SMAX");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && K < SMAX_KC && smax_records_on(c, B);
+    return !knob_off("LRCN_DECODE_SMAX") && K < SMAX_KC && smax_records_on(c, B);
 }
 // The same logits GEMM with any of the record epilogues (GEMM_OUT_SMAX_TOPK / _GUMBEL / _PICK) for M rows of h: every 128 columns of a row
 // reduce to one record of smax_part [M][smax_nrec][SMAX_REC] (allocated on first use, max_B rows).  e: the out-mode's own SmaxEpi fields
@@ -137,8 +135,7 @@ int decode_logits(lrcn_ctx *c, const float *const p[9], const void *hT, int64_t 
 // the embedding gather and the concat launch disappear.  Same products, f32 accumulation in two chains instead of one.  Memory for FLOPs:
 // T1 is 170 MB of the 288 GB.  LRCN_DECODE_TABLES=0: the [x | h] form.
 bool decode_tables_on(const lrcn_ctx *c, int B) {
-    const char *k = getenv("LRCN_DECODE_TABLES");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && c->nl == 2 && decode_epi_on(c, B) && c->H1 > 64 && c->H2 > 64;
+    return !knob_off("LRCN_DECODE_TABLES") && c->nl == 2 && decode_epi_on(c, B) && c->H1 > 64 && c->H2 > 64;
 }
 int decode_tables_alloc(lrcn_ctx *c) {
     const size_t es = c->esz;
@@ -336,8 +333,7 @@ int nbest_alloc(lrcn_ctx *c) {
 // ------------------------------------------------------------------------------------------- caption scoring (include/lrcn_score.h)
 // LRCN_SCORE_FUSED=0: the logits GEMM writes f32 logits and k_softmax_xent reduces them, at every row count
 bool score_fused_on(const lrcn_ctx *c, int R) {
-    const char *k = getenv("LRCN_SCORE_FUSED");  // read per call (the tests switch it inside one process)
-    return !(k && k[0] == '0') && smax_records_on(c, R);
+    return !knob_off("LRCN_SCORE_FUSED") && smax_records_on(c, R);
 }
 
 // pair_img == NULL: the N x M matrix; else the P pairs.  See lrcn_score.h for the plan; the routes below are chosen once per piece.

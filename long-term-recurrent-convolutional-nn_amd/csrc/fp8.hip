@@ -6,7 +6,7 @@
 //   layer        y8 = e4m3(relu(acc * escale[co] + ebias[co])),  escale = sa_in sw / sa_out,  ebias = b / sa_out
 // (the 2x2 max-pool, where fused, commutes with the positive scale and the monotone rounding).
 // The reference has no reduced-precision path (lrcn.jl:724-728 runs conv4 in Float32); parity of this path is stated
-// against the fp32 CPU oracle with the tolerance written in tests/test_gpu_fp8.py.
+// against the fp32 CPU oracle with the tolerance written in tests/test_gpu_vgg_parity.py.
 #include "common.h"
 #include "kernels.h"
 

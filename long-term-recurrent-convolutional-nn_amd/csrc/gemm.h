@@ -79,8 +79,8 @@ struct GemmArgs {
     LstmEpi lstm;           // out_mode GEMM_OUT_LSTM_FWD / _BWD only
     SmaxEpi smax;           // out_mode GEMM_OUT_SMAX_TOPK / _GUMBEL / _PICK only (bias = the logits' bias row; C unused)
     int cfg_pref;           // gemm_8p.hip: 0 = the dispatcher's tile menu, 2 = prefer the 256 x 128 tile (set by the bg_cus route)
-    int free_cus;           // > 0 (rows per GPU below the bg_cus route's threshold): this many CUs are free beside the capped convolution grids --
-                            // the split-K planner cuts K so that tiles x slices fit them in ONE round (round 5)
+    int free_cus;           // > 0 (fewer than kBgMinRows rows per GPU): this many CUs are free beside the capped convolution grids --
+                            // the split-K planner cuts K so that tiles x slices fit them in ONE round
     int bg_cus;             // > 0: this contraction runs BESIDE the capped persistent convolution grids of another stream and will
                             // find about this many free CUs (lrcn_api.hip sets it for the LSTM GEMMs when lrcn_vgg_set_wg_cap is
                             // active): the dispatcher then prefers a route whose workgroups fit them in one round
@@ -88,7 +88,7 @@ struct GemmArgs {
                             // walking a fixed share, so one that starts late (its CU still busy with another stream's kernel) does
                             // fewer tiles instead of stretching the whole launch; NULL = static round-robin walk
     unsigned long long *stamps;  // kernel-development: per-tile s_memtime stamps of gemm8p_tile's segments (8 per tile), or NULL
-    int splitk_forced;      // launch_gemm_8p(.., splitk): take the caller's slice count as it is (gemm.hip's 8p-bg-splitk route)
+    int splitk_forced;      // launch_gemm_8p(.., splitk): take the caller's slice count as it is (lrcn_api.hip's LRCN_BWD_SLABS route)
     int splitk_no_reduce;   // ... and leave the f32 slabs [slices][M][N] in ws for the caller's next kernel to sum (no reduce launch, C untouched)
     int deterministic;      // 1: no float-atomic split-K (gemm_glds.hip takes one K range per tile; gemm_8p's slab split-K is ordered anyway)
     int dbg;                // kernel-development ablation flags (LRCN_DBG env): 8 = gemm_8p.hip does not issue the next tile's first K-tile early
@@ -97,9 +97,18 @@ struct GemmArgs {
     size_t ws_bytes;
 };
 
+// The "beside the convolutions" routes (bg_cus: the 8p-bg rung of gemm_route.hip, the cell-epilogue and K-sliced recurrences of lrcn_api.hip)
+// apply to contractions of kBgMinRows..kBgMaxRows rows (below, the VGG forward's own grids are small, more CUs are free, and the LSTM chain is
+// the critical path).
+constexpr int kBgMinRows = 256, kBgMaxRows = 512;
+inline bool bg_row_window(int rows) { return rows >= kBgMinRows && rows <= kBgMaxRows; }
+
+// The router (gemm_route.hip): picks one of the engines below, or gemm.hip's first-generation kernel (gemm_nt) when none fits.
 // Requirements (checked): A/B base 16-byte aligned, lda/ldb multiples of the 16-byte chunk (4 f32 / 8 bf16),
 // CONV3: Cin a multiple of 32 (f32) / 64 (bf16).  Returns hipSuccess or an error; never faults on bad shapes.
 hipError_t launch_gemm(hipStream_t stream, const GemmArgs &g);
+// gemm.hip: the register-staged kernel for any shape that passed the router's argument checks (f32 or bf16)
+hipError_t launch_gemm_nt(hipStream_t stream, const GemmArgs &g);
 
 // Test / development aid: the kernel family the most recent launch on this thread took ("8p:0" = 256x256 tile, "8p:1" = 256x128,
 // "8p:2" = 512x128, "8p-splitk:N", "glds", "skinny", "gemm_nt", "conv64", "conv64-fused11", ...).  lrcn_debug_last_route() returns it.

@@ -1,4 +1,5 @@
-// gemm.hip -- NT GEMM / implicit-GEMM 3x3 convolution on the gfx950 matrix cores.
+// gemm.hip -- NT GEMM / implicit-GEMM 3x3 convolution on the gfx950 matrix cores: the first-generation, register-staged kernel (route
+// "gemm_nt").  gemm_route.hip sends a contraction here when no later engine fits, after checking its arguments.
 //
 //   C[M][N] (+)= A[M][K] * B[N][K]^T (+ bias[N]) (ReLU) (2x2 max-pool over 4 consecutive rows)
 //
@@ -15,10 +16,7 @@
 //
 // Replaces, in the reference: cublasSgemm at lrcn.jl:529/545/550/558 (+ their AutoGrad duals), conv4+bias+relu+pool
 // at lrcn.jl:724-726, fcx at lrcn.jl:728.
-#include <cstdio>
 #include "gemm.h"
-
-#include <cstdlib>
 
 #include "common.h"
 
@@ -265,98 +263,6 @@ template <typename T> hipError_t dispatch(hipStream_t s, const GemmArgs &g) {
 
 }  // namespace
 
-static thread_local char g_route[48] = "";
-static thread_local int g_route_cfg = -1;
-void gemm_debug_note_route(const char *route, int cfg) {
-    if (route) {
-        if (cfg >= 0) snprintf(g_route, sizeof(g_route), "%s:%d", route, cfg);
-        else snprintf(g_route, sizeof(g_route), "%s", route);
-    } else {
-        g_route_cfg = cfg;  // tile config / slice count of the launch in flight (composed into the string by launch_gemm)
-    }
-}
-const char *gemm_debug_last_route() { return g_route; }
-
-static hipError_t launch_gemm_routed(hipStream_t stream, const GemmArgs &g, const char **route);
-hipError_t launch_gemm(hipStream_t stream, const GemmArgs &g) {
-    static const bool trace = getenv("LRCN_GEMM_TRACE") != nullptr;  // development: print the kernel family every GEMM takes
-    const char *route = "?";
-    g_route_cfg = -1;
-    const hipError_t e = launch_gemm_routed(stream, g, &route);
-    gemm_debug_note_route(route, g_route_cfg);
-    if (trace) fprintf(stderr, "[gemm] M=%d N=%d K=%d lda=%ld ldb=%ld amode=%d out=%d beta=%d -> %s\n", g.M, g.N, g.K, (long)g.lda, (long)g.ldb, g.a_mode, g.out_mode, (int)g.beta, route);
-    return e;
-}
-static hipError_t launch_gemm_routed(hipStream_t stream, const GemmArgs &g, const char **route) {
-    if (g.dtype == GEMM_T_F8) {  // e4m3: the phase-interleaved convolution kernel or nothing
-        int64_t blocks = 0;
-        if (g.M <= 0 || !g.A || !g.B || !g.C || gemm_8p_config(g, &blocks) < 0) return hipErrorInvalidValue;
-        *route = "8p-f8";
-        return launch_gemm_8p(stream, g);
-    }
-    if (g.M <= 0 || g.N <= 0 || g.K <= 0 || !g.A || !g.B || !g.C) return hipErrorInvalidValue;
-    // LRCN_GLDS=0 disables the direct-to-LDS path, LRCN_GLDS=force uses it whenever eligible (tests); default: when
-    // the grid fills the chip.
-    const char *knob = getenv("LRCN_GLDS");
-    const char *knob8 = getenv("LRCN_8P");  // LRCN_8P=0 disables the phase-interleaved path, =force lowers its grid threshold
-    const char *knobs = getenv("LRCN_SKINNY");  // LRCN_SKINNY=0 disables the skinny-M weight-streaming kernel
-    const bool skinny_ok = !(knob && knob[0] == '0') && !(knobs && knobs[0] == '0') && gemm_skinny_eligible(g);
-    if (!(knob && knob[0] == '0') && !(knob8 && knob8[0] == '0')) {
-        int64_t blocks = 0;
-        // (beside the capped convolution grids a launch that fills 3/4 of the FREE CUs in one round counts as filling the chip; LRCN_FREE_8P_MIN:
-        // that fraction in percent, development knob)
-        static const int free_pct = getenv("LRCN_FREE_8P_MIN") ? atoi(getenv("LRCN_FREE_8P_MIN")) : 75;
-        if (gemm_8p_config(g, &blocks) >= 0 &&
-            ((knob8 && knob8[0] == 'f') || blocks >= 128 || (g.free_cus > 0 && blocks * 100 >= (int64_t)g.free_cus * free_pct && blocks <= g.free_cus))) {
-            *route = "8p";
-            return launch_gemm_8p(stream, g);
-        }
-        // Beside the capped convolution grids only ~bg_cus CUs are free: a launch of many small workgroups runs in several rounds
-        // on them, one of few large tiles (less operand traffic per FLOP) in one.  The recurrent GEMM of the B = 256 step
-        // (256 x 4000 x 1024): 126 workgroups of 128 x 64 take 13 us alone but 50 us beside the VGG forward (4 rounds on 32 CUs);
-        // 32 workgroups of 256 x 128 take 25 us either way.
-        static const int bg_minN = getenv("LRCN_BG_MINN") ? atoi(getenv("LRCN_BG_MINN")) : 512;  // development knob
-        if (g.bg_cus > 0 && g.a_mode == GEMM_A_PLAIN && g.M >= 256 && g.M <= 512 && g.N >= bg_minN) {
-            GemmArgs h = g;
-            h.cfg_pref = 2;
-            if (gemm_8p_config(h, &blocks) >= 0 && blocks <= 2 * g.bg_cus) {
-                // few tiles and a long K (the backward dh GEMM of the recurrence: 8 tiles x 63 K-tiles): K slices over the free CUs
-                static const int bg_sk = getenv("LRCN_BG_SPLITK") ? atoi(getenv("LRCN_BG_SPLITK")) : 0;  // development knob (0 = off)
-                if (bg_sk > 1 && blocks * bg_sk <= g.bg_cus && g.K >= 64 * 8 * bg_sk && g.c_f32 && !g.beta && !g.relu && g.out_mode == GEMM_OUT_PLAIN &&
-                    g.ws && (size_t)bg_sk * g.M * g.N * sizeof(float) <= g.ws_bytes && (g.ldc % 4) == 0 && (g.N % 4) == 0 && !((uintptr_t)g.C & 15)) {
-                    *route = "8p-bg-splitk";
-                    h.splitk_forced = 1;
-                    return launch_gemm_8p(stream, h, bg_sk);
-                }
-                *route = "8p-bg";
-                return launch_gemm_8p(stream, h);
-            }
-        }
-        if (skinny_ok && g.M <= 128) { *route = "skinny"; return launch_gemm_skinny(stream, g); }
-        const char *ksk = getenv("LRCN_8P_SPLITK");  // kernel-development knob: 0 disables the split-K form
-        const int sk = (ksk && ksk[0] == '0') ? 0 : gemm_8p_splitk(g, &blocks);
-        const char *kth = getenv("LRCN_8P_SPLITK_MIN");
-        if (sk > 1 && blocks >= (kth ? atoi(kth) : 96)) { *route = "8p-splitk"; return launch_gemm_8p(stream, g, sk); }
-    }
-    if (!(knob && knob[0] == '0') && gemm_glds_eligible(g)) {
-        const int64_t blocks = gemm_glds_blocks(g);
-        if (blocks > 0 && ((knob && knob[0] == 'f') || blocks >= 96)) { *route = "glds"; return launch_gemm_glds(stream, g); }
-    }
-    if (skinny_ok) { *route = "skinny-last"; return launch_gemm_skinny(stream, g); }
-    if (!(knob && knob[0] == '0') && gemm_glds_eligible(g) && gemm_glds_blocks(g) >= 16) {  // few tiles, but still far ahead of gemm_nt
-        *route = "glds-small";
-        return launch_gemm_glds(stream, g);
-    }  // 128 < M <= 256 with too few tiles for the paths above
-    const int ce = g.dtype == GEMM_T_BF16 ? 8 : 4;
-    if (((uintptr_t)g.A & 15) || ((uintptr_t)g.B & 15) || (g.ldb % ce)) return hipErrorInvalidValue;
-    if (g.a_mode == GEMM_A_CONV3) {
-        const int bk = g.dtype == GEMM_T_BF16 ? 64 : 32;
-        if (g.Cin % bk || g.K != 9 * g.Cin || (g.H & 1) || (g.W & 1) || g.M % (g.H * g.W)) return hipErrorInvalidValue;
-    } else if (g.lda % ce) {
-        return hipErrorInvalidValue;
-    }
-    if (g.out_mode != GEMM_OUT_PLAIN && ((g.H & 1) || (g.W & 1) || g.H <= 0 || g.W <= 0)) return hipErrorInvalidValue;
-    if (g.out_mode == GEMM_OUT_POOL && (g.beta || (g.M & 3))) return hipErrorInvalidValue;
-    *route = "gemm_nt";
+hipError_t launch_gemm_nt(hipStream_t stream, const GemmArgs &g) {
     return g.dtype == GEMM_T_BF16 ? dispatch<bf16_t>(stream, g) : dispatch<float>(stream, g);
 }

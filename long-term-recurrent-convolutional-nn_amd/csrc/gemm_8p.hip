@@ -18,11 +18,11 @@
 // Hazards (two wave groups one barrier apart): a half-tile is read one super-phase AFTER the one whose first barrier
 // follows the wait that retires it (every wave retires its own pieces, the barrier publishes them); a slot is re-staged
 // >= 3 barriers after the leading group's last ds_read of it (>= 2 after the trailing group's).
-#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
 #include "gemm.h"
+#include "knob.h"
 #include "philox.h"
 
 namespace {
@@ -1121,13 +1121,8 @@ int gemm_8p_config(const GemmArgs &g, int64_t *blocks) {
     // beside the capped convolution grids (g.free_cus CUs free): the wider tile when only IT fits them in one round -- the logits GEMM of a
     // 32-row rank (384 x 10640): 84 tiles of 256 x 256 instead of 168 of 256 x 128 on 96 CUs
     if (g.free_cus > 0 && g.N > 128 && b0 <= g.free_cus && b1 > g.free_cus) cfg = 0;
-    {
-        static const char *fc = getenv("LRCN_8P_CFG");  // kernel-development knob: force the 256 x 256 (0) or 256 x 128 (1) tile
-        if (fc && (fc[0] == '0' || fc[0] == '1') && g.N > 128) cfg = fc[0] - '0';
-    }
     *blocks = cfg == 0 ? b0 : b1;
-    const char *t = getenv("LRCN_8P_TALL");  // kernel-development knob: 0 disables the 512 x 128 tile
-    if (cfg == 1 && g.N <= 128 && cdiv(g.M, 512) >= 400 && !(t && t[0] == '0')) {
+    if (cfg == 1 && g.N <= 128 && cdiv(g.M, 512) >= 400) {  // the 512 x 128 tile
         cfg = 2;
         *blocks = cdiv(g.M, 512);
     }
@@ -1261,8 +1256,7 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         if (g.dtype != GEMM_T_BF16 || g.a_mode != GEMM_A_PLAIN || splitk > 1 || (g.N & 3) || g.M < 256 || g.N < 256 || !g.smax.part ||
             g.smax.nrec != 2 * cdiv(g.N, 256) || ((uintptr_t)g.smax.part & 15) || (g.bias && ((uintptr_t)g.bias & 15)) || !gemm_glds_eligible(g))
             return hipErrorInvalidValue;
-        static const char *dbg5 = getenv("LRCN_DBG");
-        g.dbg = dbg5 ? atoi(dbg5) : 0;
+        g.dbg = knob_int("LRCN_DBG", 0);
         g.inv_w2 = g.inv_h2 = 0;
         gemm_debug_note_route(nullptr, 0);
         if (epi == GEMM_OUT_SMAX_GUMBEL) {
@@ -1275,13 +1269,11 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
         }
         return launch_one<2, 4, 4, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_SMAX_TOPK>(stream, g, 1);
     }
-    static const char *dbg = getenv("LRCN_DBG");  // kernel-development ablation flags (gemm.h)
-    g.dbg = dbg ? atoi(dbg) : 0;
+    g.dbg = knob_int("LRCN_DBG", 0);  // kernel-development ablation flags (gemm.h)
     g.inv_w2 = g.inv_h2 = 0;
     if ((g.a_mode == GEMM_A_CONV3 || g.out_mode == GEMM_OUT_CONV || g.out_mode == GEMM_OUT_POOL) && g.W >= 4 && g.H >= 4) {
         const uint64_t wmax = (uint64_t)((g.M + 511) >> 2) + 128, dmax = (uint64_t)(g.W > g.H ? g.W : g.H) >> 1;  // rows past M in the last tile included
-        static const char *nofd = getenv("LRCN_FASTDIV");  // LRCN_FASTDIV=0: the dividing decode (tests compare the two)
-        if (wmax * dmax < (1ull << 32) && !(nofd && nofd[0] == '0')) {
+        if (wmax * dmax < (1ull << 32)) {  // the reciprocals are exact for every row of the launch; else the kernel divides
             g.inv_w2 = fastdiv_inv((unsigned)g.W >> 1);
             g.inv_h2 = fastdiv_inv((unsigned)g.H >> 1);
         }
@@ -1298,8 +1290,8 @@ hipError_t launch_gemm_8p(hipStream_t stream, const GemmArgs &g0, int splitk) {
                                                : launch_one<4, 2, 2, 2, GEMM_A_PLAIN, true, false, GEMM_OUT_LSTM_BWD>(stream, g, 1);
     }
     if (splitk > 1) {
-        // the caller's slice count must be the planner's, unless it is the "beside the convolutions" route's own choice (g.splitk_forced:
-        // the planner counts the whole chip's CUs, that route the free ones; its eligibility was checked by the router)
+        // the caller's slice count must be the planner's, unless it is the K-sliced backward recurrence's own choice (g.splitk_forced:
+        // the planner counts the whole chip's CUs, that route the free ones; its eligibility was checked by lstm_layer_bwd)
         if (!g.splitk_forced && gemm_8p_splitk(g, &blocks) != splitk) return hipErrorInvalidValue;
         hipError_t e = g.a_mode == GEMM_A_CONV3 ? dispatch<GEMM_A_CONV3, true>(stream, g, 1, splitk) : dispatch<GEMM_A_PLAIN, true>(stream, g, 1, splitk);
         if (e != hipSuccess) return e;

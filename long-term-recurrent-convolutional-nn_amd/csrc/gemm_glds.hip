@@ -12,10 +12,10 @@
 //     t run; one barrier per K-step;
 //   * workgroups are renumbered so that the N-tiles sharing one im2col panel run on the same XCD (same L2).
 // MFMA: v_mfma_f32_32x32x16_bf16; rows in window-major pixel order so 2x2 max-pool = max of 4 accumulator registers.
-#include <cstdlib>
 
 #include "common.h"
 #include "gemm.h"
+#include "knob.h"
 
 namespace {
 
@@ -449,8 +449,7 @@ bool gemm_glds_eligible(const GemmArgs &g) {
 hipError_t launch_gemm_glds(hipStream_t stream, const GemmArgs &g0) {
     if (!gemm_glds_eligible(g0)) return hipErrorInvalidValue;
     GemmArgs g = g0;
-    const char *dbg = getenv("LRCN_DBG");
-    g.dbg = dbg ? atoi(dbg) : 0;
+    g.dbg = knob_int("LRCN_DBG", 0);
     if (g.dtype == GEMM_T_F32) return dispatch<float, GEMM_A_CONV3>(stream, g);
     return g.a_mode == GEMM_A_CONV3 ? dispatch<bf16_t, GEMM_A_CONV3>(stream, g) : dispatch<bf16_t, GEMM_A_PLAIN>(stream, g);
 }

@@ -12,6 +12,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "knob.h"
 
 #define FAIL(ctx, code, ...)                          \
     do {                                              \
@@ -84,11 +85,12 @@ inline int gemm_k(int dtype, int64_t lda, int64_t ldb, int K) {
     return (dtype == GEMM_T_BF16 && lda >= round_up64(K, 64) && ldb >= round_up64(K, 64)) ? (int)round_up64(K, 64) : K;
 }
 
-// The fused bf16 step kernels of lstm_fused.hip (GEMM + cell in one launch per step) for a recurrence of B rows.  Read per call.
+// The fused bf16 step kernels of lstm_fused.hip (GEMM + cell in one launch per step) for a recurrence of B rows, up to kLstmFusedMaxRows:
+// from 256 rows their LDS-heavy workgroups take more from convolutions running beside them than the separate launches do (lstm_fused.hip).
+// LRCN_LSTM_FUSED=0: GEMM + cell as separate launches at every batch size.
+constexpr int kLstmFusedMaxRows = 128;
 inline bool lstm_fused_on(int dtype, int B, int H, int64_t ldH, int64_t ld4H) {
-    const char *k = getenv("LRCN_LSTM_FUSED");  // LRCN_LSTM_FUSED=0: GEMM + cell as separate launches at every batch size
-    const char *mb = getenv("LRCN_LSTM_FUSED_MAXB");  // kernel-development knob: largest batch routed to the fused step kernels
-    return !(k && k[0] == '0') && B <= (mb ? atoi(mb) : 128) && lstm_fused_eligible(dtype, B, H, ldH, ld4H);
+    return !knob_off("LRCN_LSTM_FUSED") && B <= kLstmFusedMaxRows && lstm_fused_eligible(dtype, B, H, ldH, ld4H);
 }
 
 // One LSTM layer's recurrence over S steps of B rows (row m = s*B + b) on a handle `h` (lrcn_ctx, lrcn_act: stream, dt, esz, zero_page,

@@ -103,7 +103,7 @@ struct PrepPlan {
     PrepDesc d[PREP_MAX];
     int n;
     int total;                      // tiles of all descriptors (set by the launchers)
-    int grid_cap;                   // k_adam_shadows: > 0 = at most this many workgroups walk the tiles (an update beside the backward pass)
+    int grid_cap;                   // always 0 (a capped update grid lost its measurement, DESIGN_HISTORY.md); kept for the kernels' argument layout
     float lr, b1, b2, eps, c1, c2;  // k_adam_shadows
 };
 void k_prepare_weights(hipStream_t st, int dtype, PrepPlan &plan);

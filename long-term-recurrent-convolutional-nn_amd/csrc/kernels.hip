@@ -511,9 +511,7 @@ __global__ void transpose_kernel(const Tin *in, int64_t ld_in, int R, int C, Tou
 template <typename T, bool ADAM = false> __global__ __launch_bounds__(256) void prepare_weights_kernel(const PrepPlan plan) {
     // 64 x 64 tiles, 16 bytes in / 8 bytes out per thread access (bf16); generic element-wise path for f32 shadows and edges
     __shared__ float tile[64][65];
-    // plan.total tiles walked by gridDim.x workgroups: one tile per workgroup, or -- a capped grid (k_adam_shadows' grid_cap) -- a few
-    // workgroups that walk them all, so that an update running BESIDE the backward pass streams at a fraction of the chip's bandwidth
-    // instead of taking every CU from the latency-bound kernels of the recurrence
+    // plan.total tiles walked by gridDim.x workgroups (the launchers start one workgroup per tile)
     for (int bid = blockIdx.x; bid < plan.total; bid += gridDim.x) {
     if (bid != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed stores have read `tile`
     int d = 0;
@@ -1586,8 +1584,7 @@ void k_adam_shadows(hipStream_t st, int dtype, PrepPlan &plan, int step, float l
     plan.c1 = (float)(1.0 - pow((double)b1, (double)step));
     plan.c2 = (float)(1.0 - pow((double)b2, (double)step));
     plan.total = tiles;
-    const int grid = (plan.grid_cap > 0 && plan.grid_cap < tiles) ? plan.grid_cap : tiles;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((prepare_weights_kernel<T, true>), dim3(grid), dim3(256), 0, st, plan));
+    DISPATCH_T(dtype, hipLaunchKernelGGL((prepare_weights_kernel<T, true>), dim3(tiles), dim3(256), 0, st, plan));
 }
 void k_cast_rows(hipStream_t st, int dtype, const float *in, int64_t ld_in, int R, int C, void *out, int64_t ld_out) {
     const dim3 grid(cdiv(ld_out, 256) > 64 ? 64 : cdiv(ld_out, 256), R);

@@ -20,6 +20,11 @@
 static thread_local std::string g_create_err;
 using namespace lrcn_impl;
 
+// Beside the capped convolution grids, from kBgMinRows rows, the large time-batched GEMMs walk their tiles persistently on this many
+// workgroups per free CU instead of queueing hundreds: they get the same CUs either way, but take none from a convolution workgroup at a
+// kernel boundary.
+constexpr int kBgWgsPerFreeCu = 4;
+
 // C[M][N] (+)= A[M][K] * B[N][K]^T
 int lrcn_impl::gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int M, int N,
          int K, const float *bias, bool c_f32, bool beta, bool relu, bool c_is_zero, bool on_wg_stream) {
@@ -45,39 +50,20 @@ int lrcn_impl::gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const vo
     g.deterministic = c->opt_det;
     g.ws = on_wg_stream ? c->wg_ws : c->gemm_ws;  // one split-K workspace per stream
     g.ws_bytes = c->gemm_ws_bytes;
-    {   // the LSTM GEMMs of a two-stream training step run beside the capped convolution grids (LRCN_BG_ROUTE=0 turns the hint off)
-        static const char *kb = getenv("LRCN_BG_ROUTE");
-        // from 256 rows per GPU only: below, the VGG forward's own grids are small, more CUs are free, and the LSTM chain is the critical
-        // path -- the hints measured 1.64 -> 1.79 ms/step at 32 rows, 2.39 -> 2.43 at 64, 4.11 -> 4.12 at 128, 7.31 -> 7.20 at 256
-        static const char *kmb = getenv("LRCN_BG_MINB");  // kernel-development knob: rows per GPU from which the hints apply (default 256)
-        static const char *kfc = getenv("LRCN_FREE_CUS_HINT");  // 0: the split-K planner assumes the whole chip, as before round 5
-        if (c->vgg_wg_cap >= 8 && c->vgg_loaded && c->cur_B < (kmb ? atoi(kmb) : 256) && !(kfc && kfc[0] == '0')) {
-            static int ncu1 = 0;
-            if (!ncu1) {
-                hipDeviceProp_t pr;
-                ncu1 = (hipGetDeviceProperties(&pr, c->cfg.device) == hipSuccess) ? pr.multiProcessorCount : 256;
-            }
-            g.free_cus = ncu1 - c->vgg_wg_cap > 0 ? ncu1 - c->vgg_wg_cap : 0;
-        }
-        if (c->vgg_wg_cap >= 8 && c->vgg_loaded && c->cur_B >= (kmb ? atoi(kmb) : 256) && !(kb && kb[0] == '0')) {
-            static int ncu = 0;
-            if (!ncu) {
-                hipDeviceProp_t pr;
-                ncu = (hipGetDeviceProperties(&pr, c->cfg.device) == hipSuccess) ? pr.multiProcessorCount : 256;
-            }
-            g.bg_cus = ncu - c->vgg_wg_cap > 0 ? ncu - c->vgg_wg_cap : 0;
-            // ... and the large time-batched GEMMs walk their tiles persistently on that many workgroups instead of queueing hundreds
-            // of them: they get the same CUs either way, but no longer take a convolution workgroup's CU at a kernel boundary
-            static const char *kc = getenv("LRCN_BG_CAP");  // workgroups per free CU (0 = uncapped).  Round 3, three same-box rounds of
-            const int capmul = kc ? atoi(kc) : 4;           // 2 / 4 / 6 / 8: 7.56 / 7.44 / 7.45 / 7.48 ms per step (round 2 had 2 ahead)
-            if (capmul > 0 && g.bg_cus >= 8) g.wg_cap = g.bg_cus * capmul;
+    if (!lstm_alone(c)) {  // beside the capped convolution grids: tell the router how many CUs those leave (gemm.h free_cus / bg_cus)
+        const int free_cus = std::max(c->ncu - c->vgg_wg_cap, 0);
+        if (c->cur_B < kBgMinRows) {
+            g.free_cus = free_cus;
+        } else {
+            g.bg_cus = free_cus;
+            if (free_cus >= 8) g.wg_cap = free_cus * kBgWgsPerFreeCu;
         }
     }
     hipError_t e = launch_gemm(on_wg_stream ? c->wg_stream : c->stream, g);
     if (e != hipSuccess) FAIL(c, LRCN_EHIP, "gemm M=%d N=%d K=%d: %s", M, N, K, hipGetErrorString(e));
-    {   // kernel-development aid: LRCN_TRACE_ROUTES=1 prints which kernel family every contraction of a call took
-        static const char *kt = getenv("LRCN_TRACE_ROUTES");
-        if (kt && kt[0] == '1') fprintf(stderr, "gemm M=%d N=%d K=%d %s-> %s\n", M, N, K, on_wg_stream ? "(wg stream) " : "", gemm_debug_last_route());
+    // kernel-development aid: LRCN_TRACE_ROUTES=1 prints which kernel family every contraction of a call took
+    if (knob_char("LRCN_TRACE_ROUTES") == '1') {
+        fprintf(stderr, "gemm M=%d N=%d K=%d %s-> %s\n", M, N, K, on_wg_stream ? "(wg stream) " : "", gemm_debug_last_route());
     }
     return LRCN_OK;
 }
@@ -199,16 +185,8 @@ int adam_fused(lrcn_ctx *c, float *const p[9], const float *const g[9], float *c
         d.src = p[k]; d.g = g[k]; d.m = m[k]; d.v = v[k];
         d.R = 1; d.C = (int)sz[k]; d.cs = (int)sz[k];
     }
-    // A group's update issued on its own stream runs BESIDE the rest of the backward pass (the per-group pipeline).  Kernel-development knob
-    // LRCN_ADAM_GROUP_WGS = n > 0: only n persistent workgroups walk the tiles of groups 0..3, so that the update does not take every CU from
-    // the recurrence's latency-bound kernels.  MEASURED AND LEFT OFF (emulated rank of 8, per-group pipeline, ms per step): uncapped 1.40 /
-    // 1.41, 192 workgroups 1.44 / 1.46, 128: 1.50, 96: 1.63, 64: 1.96, 32: 2.93 -- the capped stream of Wout's 340 MB is still running when
-    // the step joins its update stream; the groups' updates are on the critical path, not beside it.
-    {
-        static const char *kg = getenv("LRCN_ADAM_GROUP_WGS");
-        const int cap = kg ? atoi(kg) : 0;
-        plan.grid_cap = (group >= 0 && group < LRCN_GRAD_GROUPS - 1 && st != c->stream) ? cap : 0;
-    }
+    // (a group's update on its own stream runs beside the rest of the backward pass on an UNCAPPED grid: the groups' updates are on the step's
+    // critical path, not beside it)
     k_adam_shadows(st, c->dt, plan, step, lr, b1, b2, eps);
     KCHK(c, "adam (fused with the shadow pass)");
     return LRCN_OK;
@@ -219,9 +197,6 @@ void fused_update_done(lrcn_ctx *c, float *const p[9]) {  // every tensor's Adam
     c->shadow_valid = true;
     c->shadow_has_gi = c->gi_live && c->alt_gi[0] != nullptr;
 }
-
-// nothing runs beside the LSTM step: no VGG forward with capped grids on another stream (what the two-stream trainer sets up)
-bool lstm_alone(const lrcn_ctx *c) { return !(c->vgg_wg_cap >= 8 && c->vgg_loaded); }
 
 // The recurrent GEMM with the cell math in its epilogue (gemm_8p.hip GEMM_OUT_LSTM_*), for the two-stream training step at 256..512
 // rows per GPU: one launch of 32 (forward) / 8 (backward) workgroups per timestep instead of GEMM + cell kernel.  LRCN_LSTM_EPI=f turns
@@ -238,14 +213,12 @@ bool lstm_alone(const lrcn_ctx *c) { return !(c->vgg_wg_cap >= 8 && c->vgg_loade
 //            combined by a second launch or a grid barrier.
 // The same forward epilogue IS the default of the batched beam decode (decode_gates_epi below), where its GEMMs fill the chip.
 bool lstm_epi_on(lrcn_ctx *c, int B) {
-    const char *k = getenv("LRCN_LSTM_EPI"), *kb = getenv("LRCN_BG_ROUTE");
-    return c->dt == GEMM_T_BF16 && c->vgg_wg_cap >= 8 && c->vgg_loaded && B >= 256 && B <= 512 && !(c->H1 & 3) && !(c->H2 & 3) &&
-           (k && (k[0] == '1' || k[0] == 'f')) && !(kb && kb[0] == '0');
+    const char k = knob_char("LRCN_LSTM_EPI");
+    return c->dt == GEMM_T_BF16 && !lstm_alone(c) && bg_row_window(B) && !(c->H1 & 3) && !(c->H2 & 3) && (k == '1' || k == 'f');
 }
 // LRCN_LSTM_EPI=f: the forward recurrence only (its launch has 32 workgroups -- one per free CU; the backward dh GEMM has N = H: 8 tiles)
 bool lstm_epi_bwd_on(lrcn_ctx *c, int B, int H) {
-    const char *k = getenv("LRCN_LSTM_EPI");
-    return lstm_epi_on(c, B) && k && k[0] == '1' && H >= 128;   // its GEMM has N = H columns: at least one 128-column tile
+    return lstm_epi_on(c, B) && knob_char("LRCN_LSTM_EPI") == '1' && H >= 128;   // its GEMM has N = H columns: at least one 128-column tile
 }
 // the recurrence's plain-form GEMM (host.h lstm_recurrence_*): gemm() on the context's stream, so the route hints of a step apply
 auto rec_gemm(lrcn_ctx *c) {
@@ -329,10 +302,9 @@ int lstm_layer_bwd(lrcn_ctx *c, int S, int B, int H, int64_t ld4H, const void *a
     // OFF BY DEFAULT like the forward cell epilogue: the LSTM chain is not what bounds the step, and a shorter chain is returned as a lower
     // clock for the convolutions; the route is kept, tested against the CPU oracle, for a configuration where the chain matters.
     {
-        const char *ksl = getenv("LRCN_BWD_SLABS");   // read per call (the tests switch it inside one process)
-        const int nsl = ksl ? atoi(ksl) : 0;
+        const int nsl = knob_int("LRCN_BWD_SLABS", 0);
         const int Kp = (int)round_up64(4 * H, 64);
-        if (!fused && nsl >= 2 && nsl <= 8 && dt == GEMM_T_BF16 && c->vgg_wg_cap >= 8 && c->vgg_loaded && B >= 256 && B <= 512 && !(H & 3) && H >= 128 &&
+        if (!fused && nsl >= 2 && nsl <= 8 && dt == GEMM_T_BF16 && !lstm_alone(c) && bg_row_window(B) && !(H & 3) && H >= 128 &&
             Kp / 64 >= 8 * nsl && Kp <= ld4H && (size_t)nsl * B * H * sizeof(float) <= c->gemm_ws_bytes && c->gemm_ws) {
             float *slabs = reinterpret_cast<float *>(c->gemm_ws);
             for (int s = S - 1; s >= 0; --s) {
@@ -397,9 +369,9 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
     // recurrence: its three launches (transpose, split-K GEMM, reduce: ~20 us at 32 rows) run on the weight-gradient stream beside that
     // chain and are joined before the concat (round 5).  Not beside the capped VGG forward from 256 rows (as the weight gradients:
     // there a second stream of LSTM-side workgroups takes CUs from the convolutions); LRCN_WG_STREAM=0 / 1 forces it off / on.
-    const char *kwgf = getenv("LRCN_WG_STREAM");
-    static const char *kxf = getenv("LRCN_XCNN_FORK");  // development knob: 0 keeps the image embedding on the main stream
-    const bool xfork = two && !(kxf && kxf[0] == '0') && (kwgf ? kwgf[0] != '0' : !(c->vgg_wg_cap >= 8 && c->vgg_loaded && B >= 256));
+    const bool beside_vgg = !lstm_alone(c) && B >= kBgMinRows;
+    const bool par = knob_set("LRCN_WG_STREAM") ? !knob_off("LRCN_WG_STREAM") : !beside_vgg;  // the weight-gradient stream is in use
+    const bool xfork = two && par;
     auto image_embedding = [&](hipStream_t s_, bool on_wg) -> int {
         // feats (B x 4096 column-major = memory [4096][B]) -> F [B][4096] (T)
         k_transpose(s_, dt, 1, feats, B, LRCN_CNNOUT, B, c->F, LRCN_CNNOUT, 0);
@@ -474,10 +446,7 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
     // Not from 256 rows per GPU beside the capped VGG forward: there the convolutions are the critical path and a second stream
     // of LSTM-side workgroups takes CUs from them at every kernel boundary (measured on one box, ms/step off -> on: LSTM step
     // alone 2.117 -> 2.052 at 256 rows, 1.086 -> 1.072 at 32; two-stream step 1.679 -> 1.611 at 32 but 7.38 -> 7.54 at 256).
-    // LRCN_WG_STREAM=0 / 1 forces it off / on.
-    const char *kwg = getenv("LRCN_WG_STREAM");
-    const bool beside_vgg = c->vgg_wg_cap >= 8 && c->vgg_loaded && B >= 256;
-    const bool par = kwg ? kwg[0] != '0' : !beside_vgg;
+    // LRCN_WG_STREAM=0 / 1 forces it off / on (`par`, above).
     hipStream_t sw = par ? c->wg_stream : st;
     int nfork = 0;
     auto fork = [&]() -> int {  // sw waits for everything issued on the main stream so far
@@ -574,20 +543,16 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
             k_embed_rows_export(st, c->dXemb, c->ldX1, S, B, E, two ? d1 : none, c->emb_rows_out);
             HIPCHK(c, hipMemcpyAsync(c->emb_tok_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
         } else {
-            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (kernels.hip).
-            // LRCN_EMBED_SCATTER=0: the direct scatter (one float atomic per element, 64 cache lines per wave instruction: 99 vs ~25 us).
-            static const char *ks = getenv("LRCN_EMBED_SCATTER");
-            bool done = false;
-            if (!(ks && ks[0] == '0')) {
-                if (!c->dWe_rm) DALLOC(c, c->dWe_rm, sizeof(float) * (size_t)V * c->ldE);
-                unsigned long long *keys = nullptr;
-                if (c->opt_det) {
-                    if (!c->sort_keys) DALLOC(c, c->sort_keys, sizeof(unsigned long long) * (size_t)c->maxS * c->maxB);
-                    keys = c->sort_keys;
-                }
-                done = k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, grads[6], keys);
-                if (!done && c->opt_det) FAIL(c, LRCN_EINVAL, "LRCN_OPT_DETERMINISTIC supports (T+1)*B <= 8192 rows per call (got %d)", M);
+            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (kernels.hip);
+            // where that kernel declines, the direct scatter (one float atomic per element, 64 cache lines per wave instruction).
+            if (!c->dWe_rm) DALLOC(c, c->dWe_rm, sizeof(float) * (size_t)V * c->ldE);
+            unsigned long long *keys = nullptr;
+            if (c->opt_det) {
+                if (!c->sort_keys) DALLOC(c, c->sort_keys, sizeof(unsigned long long) * (size_t)c->maxS * c->maxB);
+                keys = c->sort_keys;
             }
+            const bool done = k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, grads[6], keys);
+            if (!done && c->opt_det) FAIL(c, LRCN_EINVAL, "LRCN_OPT_DETERMINISTIC supports (T+1)*B <= 8192 rows per call (got %d)", M);
             if (!done) {
                 HIPCHK(c, hipMemsetAsync(grads[6], 0, sizeof(float) * (size_t)V * E, st));
                 k_embed_scatter(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, grads[6]);
@@ -632,8 +597,7 @@ void ctx_sizes(const lrcn_ctx *c, int64_t sz[9]) { lrcn_param_sizes_n(c->nl, c->
 // LRCN_DP_FORCE_PIPELINE=1: run the per-group [all-reduce -> Adam] pipeline (and the collectives) even on a one-rank communicator,
 // so that a single-GPU box exercises exactly the code N > 1 runs (tests)
 bool dp_force_pipeline() {
-    const char *k = getenv("LRCN_DP_FORCE_PIPELINE");
-    return k && k[0] == '1';
+    return knob_char("LRCN_DP_FORCE_PIPELINE") == '1';
 }
 
 int ensure_buckets(lrcn_ctx *c) {
@@ -913,10 +877,8 @@ int lrcn_create(const lrcn_config *cfg, lrcn_ctx **out) {
             return LRCN_EHIP;
         }
     }
-    {   // environment defaults of the options (lrcn_set_option overrides): LRCN_DETERMINISTIC=1
-        const char *kd = getenv("LRCN_DETERMINISTIC");
-        c->opt_det = kd && kd[0] == '1';
-    }
+    c->opt_det = knob_char("LRCN_DETERMINISTIC") == '1';  // environment default of the option (lrcn_set_option overrides)
+    if (hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || c->ncu < 1) c->ncu = 256;
     c->dt = cfg->lstm_dtype == LRCN_BF16 ? GEMM_T_BF16 : GEMM_T_F32;
     c->vdt = cfg->vgg_dtype == LRCN_F32 ? GEMM_T_F32 : GEMM_T_BF16;  // LRCN_FP8: bf16 everywhere outside conv2_2..conv5_3
     c->vgg_fp8 = cfg->vgg_dtype == LRCN_FP8;

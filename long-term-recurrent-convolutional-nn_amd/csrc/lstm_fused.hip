@@ -7,13 +7,14 @@
 // four K-slices of the dh contraction (backward) are computed by the four WAVES of the workgroup, each an independent
 // [M x 16] MFMA GEMM with its own LDS-DMA ring (no barrier in the K loop -- a wave only reads what it staged itself), and
 // meet in LDS for the elementwise cell math.  63 workgroups for H = 1000 per block of 64 rows (grid.y).  Used up to
-// B = 128 (LRCN_LSTM_FUSED_MAXB): at B = 256 it is faster alone (2.39 -> 2.21 ms per LSTM step) but its 252 LDS-heavy
+// B = 128 (host.h kLstmFusedMaxRows): at B = 256 it is faster alone (2.39 -> 2.21 ms per LSTM step) but its 252 LDS-heavy
 // workgroups take more from the concurrently running convolutions than the separate launches do.
 #include <type_traits>
 
 #include "common.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "knob.h"
 
 namespace {
 
@@ -370,16 +371,10 @@ template <int U> __global__ __launch_bounds__(256) void lstm_rec_fwd2_kernel(con
 // workgroups).  Beside the VGG forward of the two-stream step they LOSE (1.555 -> 1.685 ms per step at 32 rows, 2.30 -> 2.56 at 64):
 // twice to four times as many workgroups, each holding 108-128 KiB of LDS, displace the convolution workgroups (one per CU, 128-160 KiB)
 // from more CUs at every kernel boundary.
-int rec2_max_batch() {
-    const char *k = getenv("LRCN_LSTM_REC2");  // read per launch (the tests switch it inside one process)
-    return k ? atoi(k) : 64;
-}
+int rec2_max_batch() { return knob_int("LRCN_LSTM_REC2", 64); }
 
 // Beside the VGG forward (`alone` false): the 12-unit forms up to this many rows (LRCN_LSTM_REC3; 0 = never, the ring forms of 16 units).
-int rec3_max_batch() {
-    const char *k = getenv("LRCN_LSTM_REC3");
-    return k ? atoi(k) : 32;
-}
+int rec3_max_batch() { return knob_int("LRCN_LSTM_REC3", 32); }
 
 template <class K> hipError_t set_lds(K kern, int lds, LdsAttrMask &done) { return set_max_lds(reinterpret_cast<const void *>(kern), lds, done); }
 

@@ -22,10 +22,7 @@ int stamps_reserve(lrcn_ctx *c, int64_t need) {
     }
     return LRCN_OK;
 }
-bool conv64_enabled() {
-    const char *k = getenv("LRCN_CONV64");  // LRCN_CONV64=0 routes the Cin = 64 layers back to the implicit-GEMM kernels
-    return !(k && k[0] == '0');
-}
+bool conv64_enabled() { return !knob_off("LRCN_CONV64"); }  // LRCN_CONV64=0 routes the Cin = 64 layers back to the implicit-GEMM kernels
 // f8_inv_scale > 0: write e4m3(out * f8_inv_scale) if the layer's kernel can (returns *wrote_f8), else bf16 as usual
 constexpr int kTileCtrStride = 8 + 2 * 512;  // ints per layer: 8 queue heads + two hand-off slots per workgroup (<= 512 workgroups)
 // An implicit-GEMM convolution of N images (g.M = N * H * W rows, operands and output of `es` bytes per element), cut into launches
@@ -83,7 +80,7 @@ int conv_layer(lrcn_ctx *c, int dtype, const void *in, const VggLayer &L, int N,
         const bool f8 = f8_inv_scale > 0.0f && !L.pool;
         if (wrote_f8) *wrote_f8 = f8;
         unsigned long long *stamps = nullptr;
-        if (getenv("LRCN_STAMPS")) {  // kernel development (tools/conv64_stamps.py): 16 stamps per 16 x 16 tile per 64-channel chunk 0
+        if (knob_set("LRCN_STAMPS")) {  // kernel development (tools/conv64_stamps.py): 16 stamps per 16 x 16 tile per 64-channel chunk 0
             if (int r = stamps_reserve(c, (int64_t)N * (L.S / 16) * (L.S / 16) * 16)) return r;
             stamps = c->stamps;
         }
@@ -94,7 +91,7 @@ int conv_layer(lrcn_ctx *c, int dtype, const void *in, const VggLayer &L, int N,
     GemmArgs g = conv_args(c, dtype, in, L, N, out, tile_ctr);
     g.ws = c->vgg_ws;  // one split-K workspace per stream: the VGG forward may run beside the LSTM step (gemm_ws)
     g.ws_bytes = c->vgg_ws ? c->gemm_ws_bytes : 0;
-    if (getenv("LRCN_STAMPS")) {  // kernel-development (include/lrcn.h lrcn_debug_stamps)
+    if (knob_set("LRCN_STAMPS")) {  // kernel-development (include/lrcn.h lrcn_debug_stamps)
         if (int r = stamps_reserve(c, ((int64_t)g.M / 256 + 1) * ((int64_t)g.N / 128 + 1) * 8)) return r;
         g.stamps = c->stamps;
     }
@@ -127,8 +124,8 @@ int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean
     if (fp8 && !c->fp8_ready) FAIL(c, LRCN_ESTATE, "vgg_dtype = LRCN_FP8: call lrcn_vgg_calibrate before the first forward");
     const int vdt = c->vdt;
     const float m0 = mean ? mean[0] : 0.f, m1 = mean ? mean[1] : 0.f, m2 = mean ? mean[2] : 0.f;
-    const char *kf = getenv("LRCN_FUSE11");  // LRCN_FUSE11=0: conv1_1 and conv1_2 as two launches
-    const bool fuse11 = vdt == GEMM_T_BF16 && src_u8 && c->conv[0].w_fused && conv64_enabled() && !(kf && kf[0] == '0');
+    // LRCN_FUSE11=0: conv1_1 and conv1_2 as two launches
+    const bool fuse11 = vdt == GEMM_T_BF16 && src_u8 && c->conv[0].w_fused && conv64_enabled() && !knob_off("LRCN_FUSE11");
     const float *avg = (src_u8 && c->avg_on) ? c->avg_img : nullptr;
     // crops that arrived through lrcn_upload_crops: the forward's stream waits for the upload; the staging buffer is free again as soon as the
     // ONE kernel below that reads the uint8 source has run (recorded right after it)
@@ -201,13 +198,10 @@ int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean
     // workgroup starting late (its CU still held by an LSTM-stream kernel) stretches the whole launch; pulling costs 2 % alone
     // (6.59 -> 6.74 ms per forward at cap 224) and gains nothing in the step (7.54 -> 7.64 ms) -- the contention is not tail imbalance.
     int *ctr = nullptr;
-    {
-        static const char *kd = getenv("LRCN_DYN_TILES");
-        if (c->vgg_wg_cap >= 8 && kd && kd[0] == '1') {
-            if (!c->tile_ctr) DALLOC(c, c->tile_ctr, sizeof(int) * 13 * kTileCtrStride);
-            HIPCHK(c, hipMemsetAsync(c->tile_ctr, 0, sizeof(int) * 13 * kTileCtrStride, c->stream));
-            ctr = c->tile_ctr;
-        }
+    if (c->vgg_wg_cap >= 8 && knob_char("LRCN_DYN_TILES") == '1') {
+        if (!c->tile_ctr) DALLOC(c, c->tile_ctr, sizeof(int) * 13 * kTileCtrStride);
+        HIPCHK(c, hipMemsetAsync(c->tile_ctr, 0, sizeof(int) * 13 * kTileCtrStride, c->stream));
+        ctr = c->tile_ctr;
     }
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     if (c->prof) {
@@ -223,7 +217,7 @@ int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean
     int l0 = 1;
     if (fuse11) {  // conv1_1 + conv1_2 + pool1 in one launch, straight from the uint8 crops: actA is never written
         unsigned long long *stamps = nullptr;
-        if (getenv("LRCN_STAMPS") && getenv("LRCN_STAMPS")[0] == 'f') {  // LRCN_STAMPS=f: stamp the fused conv1 kernel of a VGG forward
+        if (knob_char("LRCN_STAMPS") == 'f') {  // LRCN_STAMPS=f: stamp the fused conv1 kernel of a VGG forward
             if (int r = stamps_reserve(c, (int64_t)N * 14 * 14 * 16)) return r;
             stamps = c->stamps;
         }
@@ -381,10 +375,6 @@ int lrcn_bench_conv(lrcn_ctx *c, int N, int S, int Cin, int Cout, int pool, int 
     k_init_uniform(c->stream, tmp, (int64_t)w_e, (float)std::sqrt(2.0 / (9.0 * Cin)), 12, 1);
     k_cast_rows(c->stream, GEMM_T_BF16, tmp, 9 * Cin, Cout, 9 * Cin, w, 9 * Cin);
     k_fill(c->stream, bias, Cout, 0.01f);
-    if (getenv("LRCN_BENCH_ZERO")) {  // all-zero operands: the same instruction stream at the clock the chip holds WITHOUT data toggling
-        (void)hipMemsetAsync(in, 0, 2 * in_e, c->stream);   // (MI355X_MICROARCH.md, DVFS give-back): separates issue efficiency from power
-        (void)hipMemsetAsync(w, 0, 2 * w_e, c->stream);
-    }
     VggLayer L;
     L.w = w; L.b = bias; L.Cin = Cin; L.Cout = Cout; L.S = S; L.pool = pool;
     int r = conv_layer(c, GEMM_T_BF16, in, L, N, out);  // warm-up
