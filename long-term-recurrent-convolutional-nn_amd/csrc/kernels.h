@@ -1,5 +1,5 @@
-// kernels.h -- launchers of the non-GEMM kernels of liblrcn_hip (gfx950).  dtype: GEMM_T_F32 / GEMM_T_BF16 selects
-// the element type "T" of activation/shadow buffers; everything marked f32 is always float.
+// kernels.h -- launchers of the non-GEMM kernels of liblrcn_hip (gfx950), one section per .hip file that defines them, in the Makefile's
+// order.  dtype: GEMM_T_F32 / GEMM_T_BF16 selects the element type "T" of activation/shadow buffers; everything marked f32 is always float.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,23 +11,37 @@ struct DropSpec {
     int which;          // 1 = the mask of lrcn.jl:542, 2 = the mask of lrcn.jl:547
 };
 
-// tok_in[s][b] = bos (s==0) | tokens[s-1][b];  tok_tgt[s][b] = tokens[s][b] (s<T) | eos.   (lrcn.jl:556,565,569,576)
-void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc);
+// ---- lstm_fused.hip ----
+// Small-batch fused recurrent steps (lstm_fused.hip; bf16, B <= 64): one launch = the recurrent GEMM of a timestep + the cell
+// update (forward) / the dh GEMM of step s + the cell backward of step s-1.
+bool lstm_fused_eligible(int dtype, int B, int H, int64_t ldh, int64_t ld4);
+hipError_t launch_lstm_rec_fwd(hipStream_t st, const void *h_prev, int64_t ldh, const void *Wh, const float *Gx, const float *c_prev, int B,
+                               int H, void *acts, int64_t ld_a, float *c_new, void *h_new, const void *zero_page, bool alone = false);
+hipError_t launch_lstm_rec_bwd(hipStream_t st, const void *dz_s, int64_t ld4, const void *WhT, const void *acts, const float *c_prev,
+                               const float *c_new, const float *dh_ext, float *dc, int B, int H, void *dz_out, const void *zero_page,
+                               bool alone = false);
+// alone: nothing else runs on the GPU beside the LSTM step -- up to LRCN_LSTM_REC2 rows (default 64) the step kernels then take
+// their 8-units-per-workgroup forms (125 / 250 workgroups instead of 63; lstm_fused.hip)
 
+// ---- conv11.hip ----
+// conv1_1 + preprocessing fused, bf16 (conv11.hip): src = uint8 crops img[n][row][col][3] or float (S,S,3,N);
+// w [64][32] bf16 (k = tap*3+c), out NHWC bf16 [n][y][x][64] with bias + ReLU.
+void k_conv11_fused(hipStream_t st, int src_is_u8, const void *src, int N, int S, float m0, float m1, float m2, const void *w,
+                    const float *bias, void *out);
+
+// ---- fp8.hip: OCP e4m3 plumbing of the VGG convolution stack ----
+void k_quant_conv_w_fp8(hipStream_t st, const float *w, int Cin, int Cout, void *out, float *sw);
+void k_amax(hipStream_t st, int in_f32, const void *x, int64_t n, float *out);  // atomic max of |x| into *out (caller zeroes)
+void k_cast_bf16_fp8(hipStream_t st, const void *x, int64_t n, float inv_scale, void *out);  // n % 8 == 0
+void k_cast_fp8_bf16(hipStream_t st, const void *x, int64_t n, float scale, void *out);
+void k_fp8_epilogue_params(hipStream_t st, const float *b, const float *sw, int Cout, float sa_in, float sa_out, float *escale, float *ebias);
+void k_ref_to_nhwc_fp8(hipStream_t st, const float *x, int W, int H, int C, int N, float inv_scale, void *out);
+void k_nhwc_fp8_to_ref(hipStream_t st, const void *in, int W, int H, int C, int N, float scale, float *out);
+
+// ---- kernels.hip: what more than one model file launches ----
 // Xemb[m][e] = WembT[tok_in[m]][e] * dropmask   (lrcn.jl:556/569 gather + :542 dropout), m = s*B+b.
 void k_embed_gather(hipStream_t st, int dtype, const void *wembT, int64_t ld_w, const int32_t *tok_in, int S, int B,
                     int E, DropSpec d, void *xemb, int64_t ld_x);
-// dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32).
-void k_embed_scatter(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E,
-                     int V, DropSpec d, float *dwembed);
-
-// The same through an E-contiguous staging array stage[V][ld_s] (f32, all zero on entry and on exit): coalesced atomics per token row,
-// then one dense transpose that writes EVERY element of dwembed (no memset needed).  sort_keys != NULL ((T+1)*B <= 8192 keys of scratch):
-// the rows of a token are added in a fixed order by plain stores instead (LRCN_OPT_DETERMINISTIC); false = more than 8192 rows, nothing
-// was launched.
-void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out);
-bool k_embed_scatter_rm(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V, DropSpec d,
-                        float *stage, int64_t ld_s, float *dwembed, unsigned long long *sort_keys);
 
 // LSTM cell, one timestep (lrcn.jl:531-536).  G f32 [B][4H] = pre-activations incl. bias; c_prev f32 [B][H] or NULL.
 // Writes activated gates [f|i|o|g] (T), c_new (f32), h_new (T) and optionally h_new as f32.
@@ -39,26 +53,10 @@ void k_lstm_bwd(hipStream_t st, int dtype, const void *acts, int64_t ld_a, const
                 const float *dh_a, int64_t ld_dha, float *dh_b, int dh_b_read, float *dc, int dc_zero, int B, int H, void *dz,
                 int64_t ld_dz, int nslab = 0);   // nslab > 0: dh_b = [nslab][B][H] partial sums, summed here
 
-// Small-batch fused recurrent steps (lstm_fused.hip; bf16, B <= 64): one launch = the recurrent GEMM of a timestep + the cell
-// update (forward) / the dh GEMM of step s + the cell backward of step s-1.
-// batched beam search: histories = [bos, 0, ...], next input = bos, probabilities = 1 for all R hypotheses (lrcn.jl:608-611)
-void k_beam_init(hipStream_t st, int32_t *seq, int32_t *last, float *p, int R, int Lh, int bos);
-bool lstm_fused_eligible(int dtype, int B, int H, int64_t ldh, int64_t ld4);
-hipError_t launch_lstm_rec_fwd(hipStream_t st, const void *h_prev, int64_t ldh, const void *Wh, const float *Gx, const float *c_prev, int B,
-                               int H, void *acts, int64_t ld_a, float *c_new, void *h_new, const void *zero_page, bool alone = false);
-hipError_t launch_lstm_rec_bwd(hipStream_t st, const void *dz_s, int64_t ld4, const void *WhT, const void *acts, const float *c_prev,
-                               const float *c_new, const float *dh_ext, float *dc, int B, int H, void *dz_out, const void *zero_page,
-                               bool alone = false);
-// alone: nothing else runs on the GPU beside the LSTM step -- up to LRCN_LSTM_REC2 rows (default 64) the step kernels then take
-// their 8-units-per-workgroup forms (125 / 250 workgroups instead of 63; lstm_fused.hip)
-
 // X2[m][j<nl] *= mask ; X2[m][nl+j] = xcnn[b][j] * mask (j < nr); mask over nl+nr columns      (lrcn.jl:546-547: nl = nr = h;
 // LRCN-1f: nl = E, nr = h)
 void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B,
                  int nl, int nr, DropSpec d);
-// dX2[m][j] *= mask (all nl+nr columns, in place);  dxcnn[b][j] = sum_s dX2[s*B+b][nl+j]
-void k_dx2_mask_reduce(hipStream_t st, int dtype, void *dx2, int64_t ld, int S, int B, int nl, int nr, DropSpec d,
-                       float *dxcnn, int64_t ld_dxc);
 
 // Row-wise log-softmax + target pick + (optional) dlogits = (softmax - onehot) * scale   (lrcn.jl:562-567 and dual).
 // logits f32 [M][ld_l]; accumulates sum of log p(target) into *logp_sum (double).  dlog (T) may be NULL.
@@ -66,10 +64,6 @@ void k_dx2_mask_reduce(hipStream_t st, int dtype, void *dx2, int64_t ld, int S, 
 // fixed order, instead of M double atomics.
 void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
                     float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
-// prob[v] = exp(logp) for one row each (beam search, lrcn.jl:652).
-void k_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *prob, int64_t ld_p);
-// out[v] = (x[v] - max) - log(sum exp(x - max)) for one row each (the n-best beam above k_softmax_topk_rows' V limit)
-void k_log_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *out, int64_t ld_o);
 
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)
@@ -77,6 +71,50 @@ void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t 
                  int64_t ld_out, int shift);
 // out_f32[c][r] = in[r][c], f32 -> f32 (boundary layout changes)
 void k_transpose_f32(hipStream_t st, const float *in, int64_t ld_in, int R, int C, float *out, int64_t ld_out);
+// out[r][c] = (T) in[r*ld_in + c]  (f32 -> T copy of a sub-matrix; pads [C, ld_out) with zeros)
+void k_cast_rows(hipStream_t st, int dtype, const float *in, int64_t ld_in, int R, int C, void *out, int64_t ld_out);
+
+// db[n] = sum_m Z[m][n]   (Z is T [M][ld]); f32 output, overwritten.
+// deterministic: one slab of rows per column block (no atomics between slabs)
+void k_colsum(hipStream_t st, int dtype, const void *z, int64_t ld, int M, int N, float *out, bool deterministic = false);
+// Several T -> T transposes in one launch: dst[c][shift + r] = src[r][c]; columns [0, shift) and [R + shift, ld_dst) of every
+// destination row are written as zeros (K padding of the GEMM that consumes it).  R == 0 zero-fills the C destination rows.
+#define TR_MAX 4
+struct TrDesc {
+    const void *src;
+    void *dst;
+    int64_t ld_src, ld_dst;
+    int R, C, shift, tile0;
+};
+struct TrPlan {
+    TrDesc d[TR_MAX];
+    int n;
+};
+void k_transpose_multi(hipStream_t st, int dtype, TrPlan &plan);
+
+// xavier-uniform / constant fill (initweights, lrcn.jl:489-510)
+void k_init_uniform(hipStream_t st, float *w, int64_t n, float scale, uint64_t seed, int tensor);
+void k_fill(hipStream_t st, float *w, int64_t n, float v);
+
+// ---- train_kernels.hip: the training step (lrcn_api.hip) ----
+// tok_in[s][b] = bos (s==0) | tokens[s-1][b];  tok_tgt[s][b] = tokens[s][b] (s<T) | eos.   (lrcn.jl:556,565,569,576)
+void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc);
+// dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32).
+void k_embed_scatter(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E,
+                     int V, DropSpec d, float *dwembed);
+// The same through an E-contiguous staging array stage[V][ld_s] (f32, all zero on entry and on exit): coalesced atomics per token row,
+// then one dense transpose that writes EVERY element of dwembed (no memset needed).  sort_keys != NULL ((T+1)*B <= 8192 keys of scratch):
+// the rows of a token are added in a fixed order by plain stores instead (LRCN_OPT_DETERMINISTIC); false = more than 8192 rows, nothing
+// was launched.
+bool k_embed_scatter_rm(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V, DropSpec d,
+                        float *stage, int64_t ld_s, float *dwembed, unsigned long long *sort_keys);
+// the rows of dXemb (dropout multiplier applied) E-contiguous into out [S*B][E]: a rank's share of the sparse embedding-gradient exchange
+void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out);
+
+// dX2[m][j] *= mask (all nl+nr columns, in place);  dxcnn[b][j] = sum_s dX2[s*B+b][nl+j]
+void k_dx2_mask_reduce(hipStream_t st, int dtype, void *dx2, int64_t ld, int S, int B, int nl, int nr, DropSpec d,
+                       float *dxcnn, int64_t ld_dxc);
+
 // One launch for all shadow weights: parameter memory image src[R][C] (f32, C contiguous) -> direct copies split at column cs
 // (dA[r][c] | dB[r][c - cs]) and transposed copies (tA[c][r] | tB[c - cs][r]) in T; NULL destinations are skipped.  Padding
 // columns of the destinations are left as they are (zero since allocation).
@@ -111,31 +149,6 @@ void k_prepare_weights(hipStream_t st, int dtype, PrepPlan &plan);
 // updated exactly as k_adam does (same arithmetic, element by element) and the new values are written to the descriptor's shadow
 // destinations.  Descriptors without destinations (the biases: R = 1) are plain Adam.
 void k_adam_shadows(hipStream_t st, int dtype, PrepPlan &plan, int step, float lr, float b1, float b2, float eps);
-// out[r][c] = (T) in[r*ld_in + c]  (f32 -> T copy of a sub-matrix; pads [C, ld_out) with zeros)
-void k_cast_rows(hipStream_t st, int dtype, const float *in, int64_t ld_in, int R, int C, void *out, int64_t ld_out);
-// out[r][c] = (T) act(in[r][c] + bias[c])  (epilogue of a split-K GEMM whose partial sums were combined in f32)
-void k_bias_act_cast(hipStream_t st, int dtype, const float *in, int64_t ld_in, const float *bias, int relu, int R, int C, void *out,
-                     int64_t ld_out);
-// out_f32[r][c] = in[r][c] (T -> f32)
-void k_uncast_rows(hipStream_t st, int dtype, const void *in, int64_t ld_in, int R, int C, float *out, int64_t ld_out);
-
-// db[n] = sum_m Z[m][n]   (Z is T [M][ld]); f32 output, overwritten.
-// deterministic: one slab of rows per column block (no atomics between slabs)
-void k_colsum(hipStream_t st, int dtype, const void *z, int64_t ld, int M, int N, float *out, bool deterministic = false);
-// Several T -> T transposes in one launch: dst[c][shift + r] = src[r][c]; columns [0, shift) and [R + shift, ld_dst) of every
-// destination row are written as zeros (K padding of the GEMM that consumes it).  R == 0 zero-fills the C destination rows.
-#define TR_MAX 4
-struct TrDesc {
-    const void *src;
-    void *dst;
-    int64_t ld_src, ld_dst;
-    int R, C, shift, tile0;
-};
-struct TrPlan {
-    TrDesc d[TR_MAX];
-    int n;
-};
-void k_transpose_multi(hipStream_t st, int dtype, TrPlan &plan);
 
 struct AdamTensors {
     float *w[9];
@@ -146,11 +159,45 @@ struct AdamTensors {
 };
 // update! with Adam (lrcn.jl:394; Knet defaults), all 9 tensors in one launch.
 void k_adam(hipStream_t st, const AdamTensors &t, int step, float lr, float b1, float b2, float eps);
-// xavier-uniform / constant fill (initweights, lrcn.jl:489-510)
-void k_init_uniform(hipStream_t st, float *w, int64_t n, float scale, uint64_t seed, int tensor);
-void k_fill(hipStream_t st, float *w, int64_t n, float v);
+// out[i] = a[i] * b[i]
+void k_mul_f32(hipStream_t st, const float *a, const float *b, int64_t n, float *out);
 
-// ---- VGG side ----
+// ---- decode_kernels.hip: beam search (lrcn.jl:644-678) and the batched decode step (decode.hip) ----
+// batched beam search: histories = [bos, 0, ...], next input = bos, probabilities = 1 for all R hypotheses (lrcn.jl:608-611)
+void k_beam_init(hipStream_t st, int32_t *seq, int32_t *last, float *p, int R, int Lh, int bos);
+// One decode step of beam bookkeeping for N images (one workgroup each): see beam_update_kernel.  K <= 32.
+void k_beam_update(hipStream_t st, const int32_t *topi, const float *topv, const int32_t *seq_in, int32_t *seq_out, float *p,
+                   int32_t *parent, int32_t *last, int32_t *done, int32_t *ndone, int32_t *res_tok, int32_t *res_len, float *res_p, int N,
+                   int K, int L, int current, int nword, int eos);
+// For each of R rows of prob [R][ld]: the K largest entries in descending order, ties to the lower index.
+void k_topk_rows(hipStream_t st, const float *prob, int64_t ld, int R, int V, int K, int32_t *idx, float *val);
+// prob[v] = exp(logp) for one row each (beam search, lrcn.jl:652).
+void k_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *prob, int64_t ld_p);
+// out[v] = (x[v] - max) - log(sum exp(x - max)) for one row each (the n-best beam above k_softmax_topk_rows' V limit)
+void k_log_softmax_rows(hipStream_t st, const float *logits, int64_t ld_l, int M, int V, float *out, int64_t ld_o);
+// softmax + top-K of every row in one pass (false: V too large for the register-resident form, use the two kernels)
+// logp: log-probabilities (x - max) - log(sum exp(x - max)) instead of probabilities (the n-best beam), same order
+bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val, bool logp = false);
+// second half of the logits GEMM's softmax / top-K epilogue (gemm.h SmaxEpi): records [R][nrec][SMAX_REC] -> idx / val [R][K] as k_softmax_topk_rows;
+// false = not applicable (K >= SMAX_KC, too many records)
+bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val, bool logp = false);
+// out[i][r][:] = in[i][parent[r]][:] for the four recurrent states (row stride C[i]); hT[i] != NULL also receives a T copy (ld ldT[i])
+void k_gather_state(hipStream_t st, int dtype, const float *const in[4], float *const out[4], void *const hT[4], const int64_t ldT[4],
+                    const int C[4], const int32_t *parent, int R);
+// bf16 batched decode, one launch per step: embedding of each hypothesis' last token + h1 / h2 of its parent into the [x | h] operands
+void k_decode_prep(hipStream_t st, const void *wembT, int64_t ld_w, const int32_t *last, const int32_t *parent, int R, int E, const void *h1,
+                   int64_t ld_h1, int H1, const void *h2, int64_t ld_h2, int H2, void *xh1, int64_t ld_xh1, int64_t off_h1, void *xh2, int64_t ld_xh2,
+                   int64_t off_h2);
+// decode step with input-projection tables: the parents' bf16 h into the gate GEMMs' operands; out[r] = r / K (the image of a hypothesis row)
+void k_decode_prep_h(hipStream_t st, const int32_t *parent, int R, const void *h1, int64_t ld_h1, int H1, const void *h2, int64_t ld_h2, int H2,
+                     void *a1, int64_t ld_a1, void *a2, int64_t ld_a2, int64_t off_h2);
+void k_row_div(hipStream_t st, int32_t *out, int R, int K);
+// out[r][0..C) = in[r / K][0..C): every image row repeated K times (rows ld apart in both)
+void k_repeat_rows(hipStream_t st, int dtype, const void *in, int64_t ld, int N, int K, int C, void *out);
+// out[r][0..C) = in[src_row[r]][0..C)  (beam search parent-state gather, lrcn.jl:673-676); in != out.
+void k_gather_rows_f32(hipStream_t st, const float *in, int64_t ld, const int32_t *src_row, int R, int C, float *out);
+
+// ---- image_kernels.hip: the VGG side (vgg.hip, conv64.hip, conv64f.hip) ----
 // conv weight (3,3,Cin,Cout) column-major f32 -> [Cout][tap = b*3+a][Cin_pad] T (zero padded channels)
 void k_repack_conv_w(hipStream_t st, int dtype, const float *w, int Cin, int Cout, int Cin_pad, void *out);
 // conv1_1 weight -> [64][ld] T with k = tap*3 + c (27 real, rest zero)
@@ -181,42 +228,6 @@ void k_preprocess_u8(hipStream_t st, const uint8_t *img, int N, int S, float m0,
 void k_ref_to_nhwc(hipStream_t st, int dtype, const float *x, int W, int H, int C, int N, void *out, int C_ld);
 void k_nhwc_to_ref(hipStream_t st, int dtype, const void *in, int W, int H, int C, int N, int C_ld, float *out);
 
-// ---- beam search (lrcn.jl:644-678) ----
-// For each of R rows of prob [R][ld]: the K largest entries in descending order, ties to the lower index.
-void k_topk_rows(hipStream_t st, const float *prob, int64_t ld, int R, int V, int K, int32_t *idx, float *val);
-// One decode step of beam bookkeeping for N images (one workgroup each): see beam_update_kernel.  K <= 32.
-void k_beam_update(hipStream_t st, const int32_t *topi, const float *topv, const int32_t *seq_in, int32_t *seq_out, float *p,
-                   int32_t *parent, int32_t *last, int32_t *done, int32_t *ndone, int32_t *res_tok, int32_t *res_len, float *res_p, int N,
-                   int K, int L, int current, int nword, int eos);
-// out[r][0..C) = in[r / K][0..C): every image row repeated K times (rows ld apart in both)
-void k_repeat_rows(hipStream_t st, int dtype, const void *in, int64_t ld, int N, int K, int C, void *out);
-// out[r][0..C) = in[src_row[r]][0..C)  (beam search parent-state gather, lrcn.jl:673-676); in != out.
-void k_gather_rows_f32(hipStream_t st, const float *in, int64_t ld, const int32_t *src_row, int R, int C, float *out);
-// out[i] = a[i] * b[i]
-void k_mul_f32(hipStream_t st, const float *a, const float *b, int64_t n, float *out);
-// conv1_1 + preprocessing fused, bf16 (conv11.hip): src = uint8 crops img[n][row][col][3] or float (S,S,3,N);
-// w [64][32] bf16 (k = tap*3+c), out NHWC bf16 [n][y][x][64] with bias + ReLU.
-void k_conv11_fused(hipStream_t st, int src_is_u8, const void *src, int N, int S, float m0, float m1, float m2, const void *w,
-                    const float *bias, void *out);
-
-// softmax + top-K of every row in one pass (false: V too large for the register-resident form, use the two kernels)
-// logp: log-probabilities (x - max) - log(sum exp(x - max)) instead of probabilities (the n-best beam), same order
-bool k_softmax_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, int32_t *idx, float *val, bool logp = false);
-// out[i][r][:] = in[i][parent[r]][:] for the four recurrent states (row stride C[i]); hT[i] != NULL also receives a T copy (ld ldT[i])
-// second half of the logits GEMM's softmax / top-K epilogue (gemm.h SmaxEpi): records [R][nrec][SMAX_REC] -> idx / val [R][K] as k_softmax_topk_rows;
-// false = not applicable (K >= SMAX_KC, too many records)
-bool k_softmax_topk_merge(hipStream_t st, const float *part, int nrec, int R, int K, int32_t *idx, float *val, bool logp = false);
-// bf16 batched decode, one launch per step: embedding of each hypothesis' last token + h1 / h2 of its parent into the [x | h] operands
-void k_decode_prep(hipStream_t st, const void *wembT, int64_t ld_w, const int32_t *last, const int32_t *parent, int R, int E, const void *h1,
-                   int64_t ld_h1, int H1, const void *h2, int64_t ld_h2, int H2, void *xh1, int64_t ld_xh1, int64_t off_h1, void *xh2, int64_t ld_xh2,
-                   int64_t off_h2);
-// decode step with input-projection tables: the parents' bf16 h into the gate GEMMs' operands; out[r] = r / K (the image of a hypothesis row)
-void k_decode_prep_h(hipStream_t st, const int32_t *parent, int R, const void *h1, int64_t ld_h1, int H1, const void *h2, int64_t ld_h2, int H2,
-                     void *a1, int64_t ld_a1, void *a2, int64_t ld_a2, int64_t off_h2);
-void k_row_div(hipStream_t st, int32_t *out, int R, int K);
-void k_gather_state(hipStream_t st, int dtype, const float *const in[4], float *const out[4], void *const hT[4], const int64_t ldT[4],
-                    const int C[4], const int32_t *parent, int R);
-
 // ---- sample.hip: the per-step draw of the sampled decode (lrcn_sample_batch) ----
 // Device state of R independent rows: histories seq [R][L] (bos first), next input last[R], log-likelihood logp[R], done[R] / len[R],
 // ndone = number of finished rows.  A row stops after eos or at current > nword.
@@ -231,6 +242,20 @@ void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V
 // from GEMM_OUT_SMAX_GUMBEL records (top_k = 0) resp. GEMM_OUT_SMAX_TOPK records (1 <= top_k < SMAX_KC); false = not applicable
 bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s);
 bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
+
+// ---- score.hip: the per-pair steps of caption scoring (lrcn_score_matrix / lrcn_score_pairs) ----
+// A2 (T) row r < R: columns [0, h) = P row row_cap[r] (P: this step's [caption][ldP] block of h1 Wproj), columns [h2_off, h2_off + zero_h2) = 0
+// (the first step's zero h2); tgt_row[r] = tgt_cap[row_cap[r]]
+void k_score_prep(hipStream_t st, int dtype, void *A2, int64_t ldA2, const void *P, int64_t ldP, const int32_t *row_cap, int R, int h, int zero_h2,
+                  int64_t h2_off, const int32_t *tgt_cap, int32_t *tgt_row);
+// dst f32 [R][C] = table rows idx[r] (C % 4 == 0)
+void k_score_gather_rows(hipStream_t st, const float *table, int C, const int32_t *idx, int R, float *dst);
+// acc[r] += z[tgt] - max - log(sum exp) from the row's GEMM_OUT_SMAX_PICK records; false = too many records
+bool k_score_pick_merge(hipStream_t st, const float *part, int nrec, int R, double *acc);
+void k_score_acc(hipStream_t st, const double *terms, int R, double *acc);                        // acc[r] += terms[r]
+// rows r0 .. r0+R of the N x M matrix, caption-major over the sorted captions ord[]: image r % N, sorted caption r / N, slot n + ord[j] * N
+void k_score_matrix_rows(hipStream_t st, int64_t r0, int R, int N, const int32_t *ord, int32_t *img, int32_t *cap, int32_t *out);
+void k_score_scatter(hipStream_t st, const double *acc, const int32_t *out_idx, int R, float *scores);  // scores[out_idx[r]] = acc[r]
 
 // ---- nbest.hip: the per-step bookkeeping of the n-best beam (lrcn_beam_nbest_batch, include/lrcn_nbest.h) ----
 // Device state of N images x K slots (row r = n * K + k): live histories (ping-pong) and their cumulative log-probabilities (-inf: dead
@@ -253,26 +278,3 @@ struct NbestState {
 void k_nbest_init(hipStream_t st, const NbestState &s, int N, int bos);
 // one step for N images (one workgroup each) from this step's log-probability top-K topi / topv [N*K][K]; K <= 32
 void k_nbest_update(hipStream_t st, const int32_t *topi, const float *topv, const NbestState &s, int N);
-
-// ---- score.hip: the per-pair steps of caption scoring (lrcn_score_matrix / lrcn_score_pairs) ----
-// A2 (T) row r < R: columns [0, h) = P row row_cap[r] (P: this step's [caption][ldP] block of h1 Wproj), columns [h2_off, h2_off + zero_h2) = 0
-// (the first step's zero h2); tgt_row[r] = tgt_cap[row_cap[r]]
-void k_score_prep(hipStream_t st, int dtype, void *A2, int64_t ldA2, const void *P, int64_t ldP, const int32_t *row_cap, int R, int h, int zero_h2,
-                  int64_t h2_off, const int32_t *tgt_cap, int32_t *tgt_row);
-// dst f32 [R][C] = table rows idx[r] (C % 4 == 0)
-void k_score_gather_rows(hipStream_t st, const float *table, int C, const int32_t *idx, int R, float *dst);
-// acc[r] += z[tgt] - max - log(sum exp) from the row's GEMM_OUT_SMAX_PICK records; false = too many records
-bool k_score_pick_merge(hipStream_t st, const float *part, int nrec, int R, double *acc);
-void k_score_acc(hipStream_t st, const double *terms, int R, double *acc);                        // acc[r] += terms[r]
-// rows r0 .. r0+R of the N x M matrix, caption-major over the sorted captions ord[]: image r % N, sorted caption r / N, slot n + ord[j] * N
-void k_score_matrix_rows(hipStream_t st, int64_t r0, int R, int N, const int32_t *ord, int32_t *img, int32_t *cap, int32_t *out);
-void k_score_scatter(hipStream_t st, const double *acc, const int32_t *out_idx, int R, float *scores);  // scores[out_idx[r]] = acc[r]
-
-// ---- fp8.hip: OCP e4m3 plumbing of the VGG convolution stack ----
-void k_quant_conv_w_fp8(hipStream_t st, const float *w, int Cin, int Cout, void *out, float *sw);
-void k_amax(hipStream_t st, int in_f32, const void *x, int64_t n, float *out);  // atomic max of |x| into *out (caller zeroes)
-void k_cast_bf16_fp8(hipStream_t st, const void *x, int64_t n, float inv_scale, void *out);  // n % 8 == 0
-void k_cast_fp8_bf16(hipStream_t st, const void *x, int64_t n, float scale, void *out);
-void k_fp8_epilogue_params(hipStream_t st, const float *b, const float *sw, int Cout, float sa_in, float sa_out, float *escale, float *ebias);
-void k_ref_to_nhwc_fp8(hipStream_t st, const float *x, int W, int H, int C, int N, float inv_scale, void *out);
-void k_nhwc_fp8_to_ref(hipStream_t st, const void *in, int W, int H, int C, int N, float scale, float *out);

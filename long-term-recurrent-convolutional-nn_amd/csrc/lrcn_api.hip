@@ -543,7 +543,7 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
             k_embed_rows_export(st, c->dXemb, c->ldX1, S, B, E, two ? d1 : none, c->emb_rows_out);
             HIPCHK(c, hipMemcpyAsync(c->emb_tok_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
         } else {
-            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (kernels.hip);
+            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (train_kernels.hip);
             // where that kernel declines, the direct scatter (one float atomic per element, 64 cache lines per wave instruction).
             if (!c->dWe_rm) DALLOC(c, c->dWe_rm, sizeof(float) * (size_t)V * c->ldE);
             unsigned long long *keys = nullptr;

@@ -106,7 +106,7 @@ def test_5120_hypotheses_beside_a_concurrent_vgg_forward(monkeypatch):
 @pytest.mark.parametrize("smax", ["1", "0"])
 def test_fused_softmax_topk_follows_probabilities_in_a_tie_group_across_records(smax, monkeypatch):
     """Round 6: from 256 hypotheses the logits GEMM reduces its tiles to per-row records {max, sum exp, 6 best logits} of 128 columns each and
-    a merge kernel ranks them (gemm_8p.hip GEMM_OUT_SMAX_TOPK, kernels.hip softmax_topk_merge_kernel) -- the f32 logits are never written.
+    a merge kernel ranks them (gemm_8p.hip GEMM_OUT_SMAX_TOPK, decode_kernels.hip softmax_topk_merge_kernel) -- the f32 logits are never written.
     The reference ranks float32 PROBABILITIES with a stable sort (lrcn.jl:652-656), so distinct logits whose probabilities round to one
     float form a tie group whose LOWEST column wins.  Wout = 0 makes the logits = bout exactly; columns 300 < 400 < 500 (two different
     128-column records) get x, nextafter(x), nextafter(nextafter(x)): a logit-ranked top-1 returns 500, the reference 300 -- at every step
