@@ -15,6 +15,7 @@ SAMPLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sampl
 SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.h"))    # lrcn_score_matrix / _pairs (not in lrcn.h)
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
+VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -166,11 +167,21 @@ ACTIVITY_SIGNATURES = {
     "lrcn_act_predict": (C.c_int, [C.c_void_p, P4, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_varlen.h declares (bound by lib() as well)
+VARLEN_SIGNATURES = {
+    "lrcn_loss_var": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.POINTER(Dropout),
+                                C.POINTER(C.c_double)]),
+    "lrcn_loss_grad_var": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64,
+                                     C.POINTER(Dropout), P9, C.POINTER(C.c_double)]),
+    "lrcn_train_step_var": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64,
+                                      C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER,
-                                                                                                   ACTIVITY_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -191,7 +202,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()):
+                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

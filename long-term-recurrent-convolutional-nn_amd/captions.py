@@ -216,6 +216,43 @@ def batches(sequence, input_ids, lengths, batch_size, max_len=28):
         yield ids, (np.asarray(block, dtype=np.int32).reshape(T, batch_size) - 1)
 
 
+class VarlenBatches(list):
+    """minibatch_varlen's result: a list of (image ids, tokens [Tmax][B] int32 0-based padded with 0, lens int32 [B]) with what the
+    batcher did on the side: `skipped` captions (longer than max_len), `rows` = sum of (Tmax + 1) * B over the batches, `padded_rows` of
+    them past their caption's end, `padded_share` = padded_rows / rows."""
+    skipped = 0
+    rows = 0
+    padded_rows = 0
+
+    @property
+    def padded_share(self):
+        return self.padded_rows / self.rows if self.rows else 0.0
+
+
+def minibatch_varlen(caps, word_to_index, batch_size, max_len=28):
+    """Padded batches for the variable-length loss (include/lrcn_varlen.h): `caps` keeps its length-sorted order and is cut into
+    consecutive windows of `batch_size` captions (the last may be shorter), each padded to its longest caption.  Captions longer than
+    `max_len` words are skipped one by one (the reference skips their whole batch, lrcn.jl:353-355); every other caption appears exactly
+    once, nothing is forced to batch 10.  -> VarlenBatches."""
+    B = int(batch_size)
+    if B <= 0:
+        raise ValueError("batch_size must be positive")
+    kept = [c for c in caps if c[1] <= max_len]
+    out = VarlenBatches()
+    out.skipped = len(caps) - len(kept)
+    for i in range(0, len(kept), B):
+        group = kept[i:i + B]
+        lens = np.asarray([g[1] for g in group], dtype=np.int32)
+        Tmax = int(lens.max())
+        toks = np.zeros((Tmax, len(group)), dtype=np.int32)
+        for b, g in enumerate(group):
+            toks[:g[1], b] = [word_to_index.get(w, UNK) - 1 for w in g[0][1]]
+        out.append(([g[0][0] for g in group], toks, lens))
+        out.rows += (Tmax + 1) * len(group)
+        out.padded_rows += int((Tmax - lens).sum())
+    return out
+
+
 def caption_text(token_ids, idx2word):
     """generate()'s output line (lrcn.jl:634-640): words after bos up to the first eos, space separated, then '.'.
     `token_ids` are 0-based ABI ids as returned by lrcn_beam_search (bos first)."""

@@ -87,6 +87,13 @@ struct lrcn_ctx {
     void *vgg_ws = nullptr;   // same for fc6/fc7: the VGG forward may run on another stream, concurrently with the LSTM step
     size_t gemm_ws_bytes = 0;
     int last_norm = 1, last_S = 1;
+    int64_t last_tokens = 0;  // > 0: the last loss call was a variable-length one (include/lrcn_varlen.h) and this is its norm_tokens
+    // per-row lengths of the variable-length entry points: device [maxB], uploaded through kLenSlots pinned slots [maxB] each, used in
+    // turn (a slot is rewritten once the upload that last read it has run: the host may queue kLenSlots steps ahead of the device)
+    static constexpr int kLenSlots = 4;
+    int32_t *lens_dev = nullptr, *lens_pin = nullptr;
+    hipEvent_t lens_up[kLenSlots] = {};
+    int lens_slot = 0;
     int cur_B = 0;  // rows of the loss / lossgradient call in flight (gemm() picks its "beside the convolutions" hint by it)
     // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
     float *st_f32[4] = {nullptr, nullptr, nullptr, nullptr};   // h1,c1,h2,c2 [B][H]

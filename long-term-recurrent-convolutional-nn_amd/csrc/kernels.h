@@ -64,6 +64,10 @@ void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float
 // fixed order, instead of M double atomics.
 void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
                     float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
+// The same with inactive rows (tgt[m] < 0, written by k_build_tokens_var): such a row adds no loss term, gets logp_rows[m] = 0 and an
+// all-zero dlog row, and its logits are not read.  The variable-length entry points of include/lrcn_varlen.h.
+void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
+                           float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
 
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)
@@ -99,6 +103,11 @@ void k_fill(hipStream_t st, float *w, int64_t n, float v);
 // ---- train_kernels.hip: the training step (lrcn_api.hip) ----
 // tok_in[s][b] = bos (s==0) | tokens[s-1][b];  tok_tgt[s][b] = tokens[s][b] (s<T) | eos.   (lrcn.jl:556,565,569,576)
 void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc);
+// Per-row lengths (device int32 [B], 0 <= lens[b] <= T): row b's step s is active for s <= lens[b] -- tok_in / tok_tgt as above with
+// lens[b] in T's place.  An inactive step gets tok_in = eos (a valid row of the embedding gather) and tok_tgt = -1, the marker
+// k_softmax_xent_masked skips by; tokens[t][b] at t >= lens[b] is never read, so padding cannot raise the sticky flag.
+void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *lens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt,
+                        double *zero_acc);
 // dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32).
 void k_embed_scatter(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E,
                      int V, DropSpec d, float *dwembed);

@@ -89,11 +89,36 @@ __global__ void concat_x2_kernel(T *x2, int64_t ld_x2, const float *xcnn, int64_
     }
 }
 
+// A row that the length-aware token builder marked inactive (target < 0: a step past its caption's end, include/lrcn_varlen.h) has no
+// loss term: its logp_rows slot becomes exactly 0 and its dlog row all zeros (16-byte stores where the row allows), and its logits are
+// never read.  The marker is uniform over the workgroup (one row per workgroup), so the early return crosses no barrier.
 template <typename T>
+__device__ __forceinline__ void softmax_xent_inactive_row(int m, int V, T *dlog, int64_t ld_d, double *logp_rows) {
+    if (threadIdx.x == 0 && logp_rows) logp_rows[m] = 0.0;
+    if (!dlog) return;
+    T *drow = dlog + (int64_t)m * ld_d;
+    constexpr int PER = 16 / (int)sizeof(T);
+    int v = 0;
+    if ((reinterpret_cast<uintptr_t>(drow) & 15) == 0) {
+        const int nv = V / PER;
+        for (int i = threadIdx.x; i < nv; i += blockDim.x) reinterpret_cast<uint4 *>(drow)[i] = make_uint4(0u, 0u, 0u, 0u);
+        v = nv * PER;
+    }
+    for (int i = v + threadIdx.x; i < V; i += blockDim.x) drow[i] = from_f32<T>(0.0f);
+}
+
+// MASKED: the variable-length entry points' form (k_softmax_xent_masked); the equal-length launcher instantiates MASKED = false only.
+template <typename T, bool MASKED = false>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M,
                                                            int V, float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows) {
     __shared__ float sh[8];
     const int m = blockIdx.x;
+    if constexpr (MASKED) {
+        if (tgt[m] < 0) {
+            softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
+            return;
+        }
+    }
     const float *row = logits + (int64_t)m * ld_l;
     float mx = -INFINITY;
     for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, row[v]);
@@ -118,11 +143,17 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, 
 
 // The same for V <= 1024 Q with the row held in registers: one expf per element (e = expf(x - max), p = e / sum) instead of
 // two, 16-byte loads; the log-likelihood term is unchanged (x[t] - (max + logf(sum))).
-template <typename T, int Q>
+template <typename T, int Q, bool MASKED = false>
 __global__ __launch_bounds__(256) void softmax_xent_reg_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
                                                                float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows) {
     __shared__ float sh[8];
     const int m = blockIdx.x;
+    if constexpr (MASKED) {
+        if (tgt[m] < 0) {
+            softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
+            return;
+        }
+    }
     const float *row = logits + (int64_t)m * ld_l;  // ld_l % 4 == 0, 16-byte aligned rows
     float x[Q][4];
 #pragma unroll
@@ -337,14 +368,16 @@ void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float
     DISPATCH_T(dtype, hipLaunchKernelGGL(concat_x2_kernel<T>, dim3(S * B), dim3(256), 0, st, (T *)x2, ld_x2, xcnn, ld_xc, S,
                                          B, nl, nr, d));
 }
-void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                    float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
+namespace {
+template <bool MASKED>
+void launch_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
+                         double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
     const bool reg = V <= 16384 && (ld_l % 4) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(dlog) & 15) == 0;
     if (reg) {
         const int q = (V + 1023) / 1024;
-#define SX_LAUNCH(QQ)                                                                                                              \
-    DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale, \
+#define SX_LAUNCH(QQ)                                                                                                                      \
+    DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale, \
                                          logp_sum, (T *)dlog, ld_d, logp_rows))
         if (q <= 2) SX_LAUNCH(2);
         else if (q <= 4) SX_LAUNCH(4);
@@ -353,10 +386,19 @@ void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l
         else SX_LAUNCH(16);
 #undef SX_LAUNCH
     } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL(softmax_xent_kernel<T>, dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,
+        DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_kernel<T, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,
                                              logp_sum, (T *)dlog, ld_d, logp_rows));
     }
     if (logp_rows) hipLaunchKernelGGL(sum_rows_f64_kernel, dim3(1), dim3(256), 0, st, logp_rows, M, logp_sum);
+}
+}  // namespace
+void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
+                    float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
+    launch_softmax_xent<false>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows);
+}
+void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
+                           float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
+    launch_softmax_xent<true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows);
 }
 void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t ld_in, int R, int C, void *out,
                  int64_t ld_out, int shift) {

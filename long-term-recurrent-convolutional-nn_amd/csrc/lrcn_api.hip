@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "../../include/lrcn_varlen.h"
 
 static thread_local std::string g_create_err;
 using namespace lrcn_impl;
@@ -343,11 +344,36 @@ int check_shapes(lrcn_ctx *c, int T, int B, int norm_B) {
     return LRCN_OK;
 }
 
+// lens (host, [B]) -> c->lens_dev on the context's stream, through the next pinned slot
+int upload_lens(lrcn_ctx *c, const int32_t *lens, int B) {
+    // each piece on its own guard: a call that failed half-way through here leaves the next one to create what is still missing
+    if (!c->lens_dev) DALLOC(c, c->lens_dev, sizeof(int32_t) * (size_t)c->maxB);
+    if (!c->lens_pin)
+        HIPCHK(c, hipHostMalloc((void **)&c->lens_pin, sizeof(int32_t) * (size_t)c->maxB * lrcn_ctx::kLenSlots, hipHostMallocDefault));
+    for (auto &e : c->lens_up)
+        if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int k = c->lens_slot;
+    c->lens_slot = (k + 1) % lrcn_ctx::kLenSlots;
+    HIPCHK(c, hipEventSynchronize(c->lens_up[k]));  // returns at once for an event never recorded
+    int32_t *slot = c->lens_pin + (size_t)k * c->maxB;
+    std::memcpy(slot, lens, sizeof(int32_t) * (size_t)B);
+    HIPCHK(c, hipMemcpyAsync(c->lens_dev, slot, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->lens_up[k], c->stream));
+    return LRCN_OK;
+}
+
 // loss / lossgradient on internal buffers. feats: B x 4096 column-major f32 (device).
+// lens != NULL (host, [B]): the variable-length form of include/lrcn_varlen.h -- row b has lens[b] + 1 loss terms, the scale is
+// 1 / norm_tokens and norm_B is not used.  Only the token builder and the softmax-NLL kernel differ; every launch in between is the same.
 int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
-              const lrcn_dropout *drop, float *const grads[9], float *logits_out) {
+              const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens = nullptr, int64_t norm_tokens = 0) {
     int r = check_shapes(c, T, B, norm_B);
     if (r) return r;
+    if (lens) {
+        if (norm_tokens < 1) FAIL(c, LRCN_EINVAL, "norm_tokens=%lld must be >= 1", (long long)norm_tokens);
+        for (int b = 0; b < B; ++b)
+            if (lens[b] < 0 || lens[b] > T) FAIL(c, LRCN_EINVAL, "lens[%d]=%d outside [0,%d]", b, lens[b], T);
+    }
     if (drop && (drop->pdrop < 0.0f || drop->pdrop >= 1.0f)) FAIL(c, LRCN_EINVAL, "pdrop=%g outside [0,1)", drop->pdrop);
     if (drop && c->nl == 2 && ((drop->mask1 == nullptr) != (drop->mask2 == nullptr))) FAIL(c, LRCN_EINVAL, "mask1/mask2 must both be set");
     const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V, X1 = c->X1;
@@ -364,7 +390,12 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
     const bool epi = lstm_epi_on(c, B) && !lstm_fused_on(c->dt, B, H1, c->ldH1, c->ld4H1);
     r = prepare_weights(c, p, bwd, false, epi);
     if (r) return r;
-    k_build_tokens(st, tokens, T, B, V, c->tok_in, c->tok_tgt, c->logp);  // reads the caller's (T, B) ids once (T = 0: never)
+    if (lens) {
+        if ((r = upload_lens(c, lens, B))) return r;
+        k_build_tokens_var(st, tokens, c->lens_dev, T, B, V, c->tok_in, c->tok_tgt, c->logp);
+    } else {
+        k_build_tokens(st, tokens, T, B, V, c->tok_in, c->tok_tgt, c->logp);  // reads the caller's (T, B) ids once (T = 0: never)
+    }
     // input = input * param[end-3]   lrcn.jl:558.  The two-layer model needs x_cnn only at LSTM-2's input, after the whole first
     // recurrence: its three launches (transpose, split-K GEMM, reduce: ~20 us at 32 rows) run on the weight-gradient stream beside that
     // chain and are joined before the concat (round 5).  Not beside the capped VGG forward from 256 rows (as the weight gradients:
@@ -422,11 +453,13 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
         for (int s = 0; s < S; ++s)
             k_transpose_f32(st, c->Logits + (int64_t)s * B * c->ldV, c->ldV, B, V, logits_out + (int64_t)s * B * V, B);
     }
-    const float scale = (float)(1.0 / ((double)norm_B * (double)S));
+    const float scale = (float)(1.0 / (lens ? (double)norm_tokens : (double)norm_B * (double)S));
     if (c->opt_det && !c->logp_rows) DALLOC(c, c->logp_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
-    k_softmax_xent(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, bwd ? c->dLog : nullptr, c->ldV, c->opt_det ? c->logp_rows : nullptr);
+    (lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, bwd ? c->dLog : nullptr, c->ldV,
+                                                    c->opt_det ? c->logp_rows : nullptr);
     c->last_norm = norm_B;
     c->last_S = S;
+    c->last_tokens = lens ? norm_tokens : 0;
     KCHK(c, "forward");
     if (!bwd) return LRCN_OK;
 
@@ -585,7 +618,7 @@ int fetch_loss(lrcn_ctx *c, double *out) {
         HIPCHK(c, hipMemsetAsync(c->logp + 1, 0, sizeof(double), c->stream));
         FAIL(c, LRCN_EINVAL, "a token id was outside [0, V=%d) (ids are 0-based at the ABI: eos=0, bos=1, unk=2; the reference raises BoundsError, lrcn.jl:556/569)", c->V);
     }
-    if (out) *out = -s[0] / ((double)c->last_norm * (double)c->last_S);
+    if (out) *out = -s[0] / (c->last_tokens > 0 ? (double)c->last_tokens : (double)c->last_norm * (double)c->last_S);
     return LRCN_OK;
 }
 
@@ -824,6 +857,9 @@ void lrcn_destroy(lrcn_ctx *c) {
     if (c->xc_fork) (void)hipEventDestroy(c->xc_fork);
     if (c->xc_done) (void)hipEventDestroy(c->xc_done);
     if (c->pin) (void)hipHostFree(c->pin);
+    if (c->lens_pin) (void)hipHostFree(c->lens_pin);
+    for (auto &e : c->lens_up)
+        if (e) (void)hipEventDestroy(e);
     if (c->wg_stream && c->wg_stream_owned) (void)hipStreamDestroy(c->wg_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (int j = 0; j < lrcn_ctx::kStage; ++j) {
@@ -1056,6 +1092,27 @@ int lrcn_loss_grad(lrcn_ctx *c, const float *const p[9], const float *feats, con
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
 }
 
+// ---- include/lrcn_varlen.h: per-row caption lengths ----
+int lrcn_loss_var(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, int T, int B,
+                  int64_t norm_tokens, const lrcn_dropout *drop, double *loss_host) {
+    DeviceGuard dg(c);
+    if (!c || !p || !feats || (!tokens && T > 0)) return LRCN_EINVAL;
+    if (!lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
+    int r = loss_impl(c, p, feats, tokens, T, B, 1, drop, nullptr, nullptr, lens, norm_tokens);
+    if (r) return r;
+    return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
+int lrcn_loss_grad_var(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, int T, int B,
+                       int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host) {
+    DeviceGuard dg(c);
+    if (!c || !p || !feats || (!tokens && T > 0) || !grads) return LRCN_EINVAL;
+    if (!lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
+    int r = loss_impl(c, p, feats, tokens, T, B, 1, drop, grads, nullptr, lens, norm_tokens);
+    if (r) return r;
+    return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
 int lrcn_grad_group_wait(lrcn_ctx *c, int group, void *stream) {
     DeviceGuard dg(c);
     if (!c || group < 0 || group >= LRCN_GRAD_GROUPS) return LRCN_EINVAL;
@@ -1203,6 +1260,18 @@ int lrcn_train_step(lrcn_ctx *c, float *const p[9], float *const g[9], float *co
     DeviceGuard dg(c);
     if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
     int r = lrcn_loss_grad(c, p, feats, tokens, T, B, norm_B, drop, g, nullptr);
+    if (r) return r;
+    r = lrcn_adam_update(c, p, g, m, v, step, lr, b1, b2, eps);
+    if (r) return r;
+    return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
+int lrcn_train_step_var(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                        const int32_t *tokens, const int32_t *lens, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, int step,
+                        float lr, float b1, float b2, float eps, double *loss_host) {
+    DeviceGuard dg(c);
+    if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
+    int r = lrcn_loss_grad_var(c, p, feats, tokens, lens, T, B, norm_tokens, drop, g, nullptr);
     if (r) return r;
     r = lrcn_adam_update(c, p, g, m, v, step, lr, b1, b2, eps);
     if (r) return r;

@@ -24,6 +24,32 @@ __global__ void build_tokens_kernel(const int32_t *tokens, int T, int B, int V, 
     tok_tgt[i] = tg;
 }
 
+// The length-aware sibling (include/lrcn_varlen.h): step s of row b is active for s <= lens[b].  Active steps are built exactly as above
+// (with lens[b] in T's place); an inactive step gets the input eos and the target -1, and reads nothing from `tokens`.
+__global__ void build_tokens_var_kernel(const int32_t *tokens, const int32_t *lens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt,
+                                        double *zero_acc) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && zero_acc) *zero_acc = 0.0;
+    const int S = T + 1;
+    if (i >= S * B) return;
+    const int s = i / B, b = i - s * B;
+    const int len = lens[b];
+    if (s > len) {
+        tok_in[i] = 0;
+        tok_tgt[i] = -1;
+        return;
+    }
+    int in = (s == 0) ? 1 : tokens[(s - 1) * B + b];
+    int tg = (s < len) ? tokens[s * B + b] : 0;
+    if ((unsigned)in >= (unsigned)V || (unsigned)tg >= (unsigned)V) {  // as build_tokens_kernel: clamp to unk, raise the sticky flag
+        if (zero_acc) zero_acc[1] = 1.0;
+        if ((unsigned)in >= (unsigned)V) in = 2;
+        if ((unsigned)tg >= (unsigned)V) tg = 2;
+    }
+    tok_in[i] = in;
+    tok_tgt[i] = tg;
+}
+
 __global__ void embed_scatter_kernel(const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V,
                                      DropSpec d, float *dwembed) {
     const int m = blockIdx.x;
@@ -349,6 +375,11 @@ __global__ void mul_f32_kernel(const float *a, const float *b, int64_t n, float 
 void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc) {
     const int n = (T + 1) * B;
     hipLaunchKernelGGL(build_tokens_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, tokens, T, B, V, tok_in, tok_tgt, zero_acc);
+}
+void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *lens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt,
+                        double *zero_acc) {
+    const int n = (T + 1) * B;
+    hipLaunchKernelGGL(build_tokens_var_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, tokens, lens, T, B, V, tok_in, tok_tgt, zero_acc);
 }
 void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out) {
     hipLaunchKernelGGL(embed_rows_export_kernel, dim3(S * B), dim3(256), 0, st, dxemb, ld_dx, S, B, E, d, out);

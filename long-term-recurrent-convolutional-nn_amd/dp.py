@@ -119,9 +119,10 @@ class HipOps:
         # host crops are uploaded through the staging buffers first
         return L.convnet_u8(self.ctx, img_u8, mean=self.mean, feats=feats, normalize=normalize)
 
-    def loss(self, param, feats, tokens):
-        """Forward-only loss of one batch (average_loss's body, lrcn.jl:452-475): pdrop 0, normalised by the batch's own size."""
-        return L.avg_loss_batch(self.ctx, param, feats, tokens)
+    def loss(self, param, feats, tokens, lens=None):
+        """Forward-only loss of one batch (average_loss's body, lrcn.jl:452-475): pdrop 0, normalised by the batch's own size (a padded
+        batch with `lens`: by its own token count)."""
+        return L.avg_loss_batch(self.ctx, param, feats, tokens, lens=lens)
 
     def vgg_blocks(self, img_u8, rows, feats=None, normalize=False):
         """One forward for the crops of several batches -> list of rows x 4096 feature blocks (lrcn_vgg_forward_u8_blocks)."""
@@ -144,9 +145,9 @@ class HipOps:
     def set_vgg_wg_cap(self, cap):
         self.ctx._call("lrcn_vgg_set_wg_cap", int(cap))
 
-    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads):
+    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None):
         L.lossgradient(self.ctx, param, feats, tokens, norm_B=norm_B, pdrop=pdrop, seed=seed, grads=grads,
-                       want_loss=False)
+                       want_loss=False, lens=lens, norm_tokens=norm_tokens)
 
     def update(self, param, grads, optim):
         L.update(self.ctx, param, grads, optim)
@@ -626,7 +627,7 @@ class DataParallelTrainer:
             return staged
         return self.ops.upload(img)
 
-    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None):
+    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None):
         """One synchronous-SGD step on this rank's shard.  img_u8: this rank's uint8 crops (or feats given);
         next_img_u8: the crops of the NEXT step(s), whose VGG forward runs beside this step's LSTM work and all-reduce.
         img_u8 is IGNORED when an earlier step() already produced this batch's features through its next_img_u8.
@@ -641,7 +642,11 @@ class DataParallelTrainer:
         (lrcn.jl:369-376); here the copy runs on the library's copy stream.  prefetch_img_u8: the chunk AFTER next_img_u8 (the tensor
         that will be passed as next_img_u8 once this one has been consumed): its upload starts when next_img_u8 is consumed, a whole
         chunk before the VGG forward that reads it, so the forward never waits for PCIe.  A host buffer handed over must stay unchanged
-        until its forward has been queued AND the copy has run (lrcn.upload_wait) -- a loader rotates at least three pinned buffers."""
+        until its forward has been queued AND the copy has run (lrcn.upload_wait) -- a loader rotates at least three pinned buffers.
+
+        lens: this rank's rows are a padded batch (include/lrcn_varlen.h) of these caption lengths; norm_tokens: the GLOBAL batch's
+        sum(lens + 1), which every rank computes from the full batch (train.shard_block) -- one rank may leave it out.  The ranks'
+        gradients then sum to the single-device gradient, as with B_global for equal lengths.  Not with the "abi" backend."""
         rows = int(tokens.shape[1])
         self._cur_M = (int(tokens.shape[0]) + 1) * rows
         if feats is None:
@@ -673,6 +678,8 @@ class DataParallelTrainer:
         # rank-dependent dropout stream: masks differ per shard like rows of one big batch would
         seed = (self.seed + self.step_no) * 65536 + self.rank
         if self.backend == "abi" and self._multi:
+            if lens is not None:
+                raise L.LrcnError("the \"abi\" data-parallel backend (lrcn_train_step_dp) takes equal-length batches only; use backend=\"torch\"")
             if not self._abi_stream_set and hasattr(self.ops, "comm_set_stream"):
                 self.ops.comm_set_stream(avoid=[self._side])
                 self._abi_stream_set = True
@@ -680,7 +687,14 @@ class DataParallelTrainer:
             self.ops.train_step_dp(self.param, self.grads, self.optim, feats, tokens, self.B_global, self.pdrop, seed)
             inorder_vgg()
             return consumed
-        self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)
+        if lens is not None:
+            if norm_tokens is None:
+                if self.world > 1:
+                    raise L.LrcnError("a padded batch over %d ranks needs the global batch's token count (norm_tokens)" % self.world)
+                norm_tokens = int(np.asarray(lens, dtype=np.int64).sum()) + len(lens)
+            self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens))
+        else:
+            self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)
         if self.gclip > 0:
             if self.world > 1:
                 dist.all_reduce(self.flat_grads, op=dist.ReduceOp.SUM, group=self.group)

@@ -159,6 +159,16 @@ def _tokens(tokens, device):
     return t.to(device=device, dtype=torch.int32).contiguous()
 
 
+def _lens(lens, T, B, norm_tokens):
+    """Per-row caption lengths of the variable-length calls (include/lrcn_varlen.h) -> (host int32 array, its ctypes pointer, norm_tokens);
+    norm_tokens None = this batch's own count sum(lens + 1)."""
+    a = np.ascontiguousarray(np.asarray(lens.cpu() if torch.is_tensor(lens) else lens, dtype=np.int32).reshape(-1))
+    if a.shape[0] != B:
+        raise LrcnError("lens has %d entries, the batch has %d rows" % (a.shape[0], B))
+    n = int(a.astype(np.int64).sum()) + B if norm_tokens is None else int(norm_tokens)
+    return a, a.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int64(n)
+
+
 # ------------------------------------------------------------------------------------------------ model
 def initweights(ctx, seed=42):
     """initweights(atype, hidden, vocab, embed) (lrcn.jl:489-510) -> list of 9 column-major tensors."""
@@ -210,13 +220,20 @@ def lrcn(ctx, w, s, x_cnn, x_lstm, mask1=None, mask2=None):
     return logits
 
 
-def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None):
+def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None):
     """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
-    tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B)."""
+    tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
+    lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
+    norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if lens is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        ctx._call("lrcn_loss_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None, C.byref(out))
+        del keep, la
+        return out.value
     ctx._call("lrcn_loss", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), T, B, norm_B or B,
               C.byref(d) if d else None, C.byref(out))
     del keep
@@ -224,14 +241,20 @@ def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, 
 
 
 def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
-                 want_loss=True):
-    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list."""
+                 want_loss=True, lens=None, norm_tokens=None):
+    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens: as loss()."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     if grads is None:
         grads = [jl_empty(*t.shape) for t in param]
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if lens is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        ctx._call("lrcn_loss_grad_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None,
+                  _p9(grads), C.byref(out) if want_loss else None)
+        del keep, la
+        return grads, (out.value if want_loss else None)
     ctx._call("lrcn_loss_grad", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), T, B, norm_B or B,
               C.byref(d) if d else None, _p9(grads), C.byref(out) if want_loss else None)
     del keep
@@ -295,13 +318,20 @@ def refresh_shadows_group(ctx, param, group, stream=None):
     ctx._call("lrcn_refresh_shadows_group", _p9(param), int(group), C.c_void_p(stream.cuda_stream) if stream is not None else None)
 
 
-def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False):
-    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call."""
+def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None):
+    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens: as loss()."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     d, keep = _dropout(pdrop, seed, None, None)
+    la = _lens(lens, T, B, norm_tokens) if lens is not None else None   # checked before the step counter moves
     optim.t += 1
     out = C.c_double()
+    if la is not None:
+        ctx._call("lrcn_train_step_var", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()),
+                  la[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps,
+                  C.byref(out) if want_loss else None)
+        del keep, la
+        return out.value if want_loss else None
     ctx._call("lrcn_train_step", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()),
               T, B, norm_B or B, C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps,
               C.byref(out) if want_loss else None)
@@ -397,8 +427,11 @@ def average_loss(ctx, param, batches):
     return total / max(count, 1)
 
 
-def avg_loss_batch(ctx, param, feats, tokens):
-    """The body of average_loss's batch loop (lrcn.jl:452-475): pdrop 0, the loss divided by the batch's own size (lrcn_avg_loss_batch)."""
+def avg_loss_batch(ctx, param, feats, tokens, lens=None):
+    """The body of average_loss's batch loop (lrcn.jl:452-475): pdrop 0, the loss divided by the batch's own size (lrcn_avg_loss_batch).
+    lens: the padded batch of include/lrcn_varlen.h, divided by its own token count sum(lens + 1)."""
+    if lens is not None:
+        return loss(ctx, param, feats, tokens, lens=lens)
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     out = C.c_double()

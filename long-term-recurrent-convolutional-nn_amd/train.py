@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from . import dp
+from . import lrcn as L
 
 
 def epoch_order(n_blocks, seed, epoch):
@@ -22,8 +23,20 @@ def epoch_order(n_blocks, seed, epoch):
     return np.random.default_rng([int(seed) & 0x7FFFFFFF, int(epoch)]).permutation(n_blocks)
 
 
+def block_tokens(lens):
+    """Loss terms of a padded batch: sum(lens + 1)."""
+    return int(np.asarray(lens, dtype=np.int64).sum()) + len(lens)
+
+
 def shard_block(block, world, rank):
-    """(image ids, tokens [T][B]) of a full batch -> this rank's contiguous rows of it."""
+    """(image ids, tokens [T][B]) of a full batch -> this rank's contiguous rows of it.  A padded batch (ids, tokens [Tmax][B], lens)
+    (captions.minibatch_varlen) -> (ids, tokens, lens) of this rank's rows and the GLOBAL batch's token count, the normaliser every rank
+    passes; a split's last window may be short, and must still divide by the ranks."""
+    if len(block) == 3:
+        ids, toks, lens = block
+        rows = dp.shard_rows(len(ids), world, rank)
+        return (list(ids[rows.start:rows.stop]), np.ascontiguousarray(np.asarray(toks)[:, rows.start:rows.stop]),
+                np.ascontiguousarray(np.asarray(lens, dtype=np.int32)[rows.start:rows.stop]), block_tokens(lens))
     ids, toks = block
     rows = dp.shard_rows(len(ids), world, rank)
     return list(ids[rows.start:rows.stop]), np.ascontiguousarray(np.asarray(toks)[:, rows.start:rows.stop])
@@ -43,8 +56,13 @@ def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1):
     n = 0
     shards = [shard_block(blocks[k], W, r) for k in order]
     nxt_pos, nxt = 1, None          # position (in `order`) of the first batch whose crops have not been handed to the trainer yet
-    for pos, (ids, toks) in enumerate(shards):
-        if crops_of is None:
+    for pos, shard in enumerate(shards):
+        ids, toks = shard[0], shard[1]
+        if len(shard) == 4:   # a padded batch: precomputed features only (the crops' pipeline counts on one row count per step)
+            if crops_of is not None:
+                raise L.LrcnError("variable-length batches train on precomputed features (feats_of)")
+            trainer.step(None, toks, feats=feats_of(ids), lens=shard[2], norm_tokens=shard[3])
+        elif crops_of is None:
             trainer.step(None, toks, feats=feats_of(ids))
         else:
             nxt_pos = max(nxt_pos, pos + 1)
@@ -64,12 +82,17 @@ def average_loss(trainer, blocks, feats_of):
     Whole batches are dealt round-robin to the ranks (the parameters are replicated); (total, count) are summed over ranks."""
     W, r = trainer.world, trainer.rank
     total, count = 0.0, 0
-    for ids, toks in blocks[r::W]:
-        toks = np.asarray(toks)
+    for blk in blocks[r::W]:
+        ids, toks = blk[0], np.asarray(blk[1])
         T, B = toks.shape
-        val = trainer.ops.loss(trainer.param, feats_of(list(ids)), toks)   # -sum logp / (B (T+1))
-        total += val * B * (T + 1)
-        count += B * (T + 1)
+        if len(blk) == 3:   # a padded batch: -sum logp / sum(lens + 1)
+            n = block_tokens(blk[2])
+            val = trainer.ops.loss(trainer.param, feats_of(list(ids)), toks, lens=blk[2])
+        else:
+            n = B * (T + 1)
+            val = trainer.ops.loss(trainer.param, feats_of(list(ids)), toks)   # -sum logp / (B (T+1))
+        total += val * n
+        count += n
     if W > 1:
         t = torch.tensor([total, float(count)], dtype=torch.float64, device=trainer.param[0].device if dist.get_backend(trainer.group) == "nccl" else "cpu")
         dist.all_reduce(t, group=trainer.group)
@@ -78,7 +101,8 @@ def average_loss(trainer, blocks, feats_of):
 
 
 def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feats_of=None, save=None, log=print, sync=None, lookahead=1):
-    """train! (lrcn.jl:223-246).  splits: [(blocks of the training split), (blocks of the dev split)?], blocks = [(ids, tokens)].
+    """train! (lrcn.jl:223-246).  splits: [(blocks of the training split), (blocks of the dev split)?], blocks = [(ids, tokens)] or the
+    padded [(ids, tokens, lens)] of captions.minibatch_varlen.
     feats_of / crops_of: the training inputs (one of them); eval_feats_of[i](ids): features of split i for average_loss (default:
     feats_of).  save(epoch): called on every rank after each epoch (rank 0 writes; a sharded update gathers its moments first).
     Returns the list of per-epoch loss tuples."""

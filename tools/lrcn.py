@@ -13,6 +13,7 @@
 
 Training runs on dp.DataParallelTrainer (train.py = train! / train1 / average_loss, lrcn.jl:223-246, 330-397, 407-486): every bucketed
 batch is split by rows over the ranks (same T everywhere, the global batch as normaliser, gradients summed over RCCL, identical Adam).
+`--varlen` batches captions of mixed lengths (padded, masked loss) instead of the reference's equal-length batches: nothing is dropped.
 `--gpus N` starts the ranks itself from a parent that never touches the GPU; the torchrun form works too.  `--cnn --train --imagedir`
 trains end to end from images: the VGG forward of the next batch runs beside the LSTM step of the current one.
 
@@ -81,6 +82,9 @@ def build_parser():
     p.add_argument("--gpus", type=int, default=1, help="--train: ranks of the data-parallel job (one per GPU); batches are split by rows")
     p.add_argument("--dp_backend", default="torch", choices=["torch", "abi"], help="collectives through torch.distributed's RCCL group or the library's own")
     p.add_argument("--shard_adam", action="store_true", help="N > 1: reduce-scatter -> Adam on 1/N of the parameters -> all-gather (dp.py)")
+    p.add_argument("--varlen", action="store_true",
+                   help="--train: padded batches of mixed caption lengths (include/lrcn_varlen.h) for the training and the evaluation splits: the "
+                        "length-sorted captions cut into windows of --batchsize, none dropped, no forced batch 10 (needs --features)")
     p.add_argument("--no_normalize", action="store_true", help="--cnn --train: do not divide fc7 features by their sum (lrcn.jl:595-597 does)")
     return p
 
@@ -107,6 +111,8 @@ def tokenize_all(o, cap):
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     o = build_parser().parse_args(argv)
+    if o.varlen and not o.train:
+        raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
     world_env = os.environ.get("WORLD_SIZE")
     if o.gpus > 1 and world_env is None:   # before any torch / HIP import: this parent only starts the ranks and passes their output on
         if not o.train:
@@ -327,9 +333,31 @@ def main(argv=None):
     # ---------------------------------------------------------------- train! (lrcn.jl:223-246) on dp.DataParallelTrainer
     if lists and o.train:
         say("Batching starts")
-        seqs = [cap.minibatch(c, vocab, o.batchsize) for c in lists]
+        if o.varlen:
+            if o.cnn and not o.features:
+                raise SystemExit("--varlen trains on precomputed features (--features)")
+            if o.dp_backend == "abi" and world > 1:
+                raise SystemExit("--varlen needs --dp_backend torch")
+            vb = [cap.minibatch_varlen(c, vocab, o.batchsize) for c in lists[:2]]
+            splits = [list(v) for v in vb]
+            cut = 0
+            if world > 1 and splits[0] and len(splits[0][-1][0]) % world:   # the short last window must divide by the ranks
+                ids_, toks_, lens_ = splits[0].pop()
+                keep = len(ids_) - len(ids_) % world
+                cut = len(ids_) - keep
+                if keep:
+                    splits[0].append((ids_[:keep], np.ascontiguousarray(toks_[:, :keep]), lens_[:keep]))
+            for name, c, v, lost in zip(("train", "dev"), lists, vb, (cut, 0)):
+                say("%s: %d captions, %d dropped, %d longer than 28 words skipped, %d batches of up to %d, %.1f%% of the rows are padding"
+                    % (name, len(c), lost, v.skipped, len(v), o.batchsize, 100.0 * v.padded_share))
+            B_global = o.batchsize
+        else:
+            seqs = [cap.minibatch(c, vocab, o.batchsize) for c in lists]
+            for name, c, sq in zip(("train", "dev"), lists, seqs[:2]):   # cap.batches skips the batches of captions longer than 28 words
+                say("%s: %d captions, %d dropped, %d longer than 28 words skipped, batches of %d"
+                    % (name, len(c), len(c) - len(sq[2]), sum(1 for n in sq[2] if n > 28), sq[3]))
+            B_global = seqs[0][3]   # splits with <= 30000 captions are forced to batch 10 (lrcn.jl:260-270)
         say("Batching finished")
-        B_global = seqs[0][3]   # splits with <= 30000 captions are forced to batch 10 (lrcn.jl:260-270)
         if B_global % world:
             raise SystemExit("the batch of %d captions does not split over %d ranks" % (B_global, world))
         optim = L.initparams(param)
@@ -344,7 +372,8 @@ def main(argv=None):
                                          gclip=o.gclip)
         if adam_state is not None:   # resume: moments and step count (the reference never saved them)
             trainer.restore(adam=(adam_state["m"], adam_state["v"], adam_state["step"]))
-        splits = [list(cap.batches(sq[0], sq[1], sq[2], sq[3])) for sq in seqs[:2]]
+        if not o.varlen:
+            splits = [list(cap.batches(sq[0], sq[1], sq[2], sq[3])) for sq in seqs[:2]]
 
         def image_path(i):
             return os.path.join(o.imagedir, "%s%012d.jpg" % (o.prefix, i) if o.prefix else "%d.jpg" % i)
