@@ -18,12 +18,19 @@ VGG_COUT = (64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512)
 VGG_POOL_AFTER = (0, 1, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 1)
 
 _fp = C.POINTER(C.c_float)
+_dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 
 
 class _Model(C.Structure):
     _fields_ = [("E", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("V", C.c_int)] + [
         (n, _fp) for n in PARAM_NAMES
+    ]
+
+
+class _Model64(C.Structure):   # orc_model of the double-storage build
+    _fields_ = [("E", C.c_int), ("H1", C.c_int), ("H2", C.c_int), ("V", C.c_int)] + [
+        (n, _dp) for n in PARAM_NAMES
     ]
 
 
@@ -34,7 +41,8 @@ class _Vgg(C.Structure):
 
 def build(force=False):
     """Compile the oracle's shared libraries (gcc). Building the checker is not using it."""
-    libs = [os.path.join(HERE, n) for n in ("liblrcn_oracle.so", "liblrcn_oracle_f32.so", "liblrcn_cpu.so", "liblrcn_cpu_f32.so")]
+    libs = [os.path.join(HERE, n) for n in ("liblrcn_oracle.so", "liblrcn_oracle_f64.so", "liblrcn_oracle_f32.so", "liblrcn_cpu.so",
+                                              "liblrcn_cpu_f32.so")]
     src = [os.path.join(HERE, n) for n in ("lrcn_oracle.c", "lrcn_oracle.h", "lrcn_cpu_abi.c", "Makefile")] + [
         os.path.join(HERE, "..", "include", "lrcn.h")]
     stale = force or any(
@@ -112,9 +120,32 @@ def lib(fast=False):
     return _LIBS[key]
 
 
+def lib64():
+    """The double-storage build of the same source (lrcn_oracle.h, orc_real): only the loss, its gradients and the per-step logits
+    are bound.  loss() and forward_logits() run on it whenever the checker is not emulating bf16."""
+    if "f64" not in _LIBS:
+        path = os.path.join(HERE, "liblrcn_oracle_f64.so")
+        if not os.path.exists(path):   # as lib(): built when missing; build() (__graft_entry__.build, make) is what refreshes a stale one,
+            build()                    # and it makes all the libraries together, so this one is never older than the float checker
+        L = C.CDLL(path)
+        M = C.POINTER(_Model64)
+        L.orc_loss.restype = C.c_double
+        L.orc_loss.argtypes = [M, _dp, _ip, C.c_int, C.c_int, C.c_int, _dp, _dp, M]
+        L.orc_forward_logits.restype = None
+        L.orc_forward_logits.argtypes = [M, _dp, _ip, C.c_int, C.c_int, _dp]
+        L.orc1_loss.restype = C.c_double
+        L.orc1_loss.argtypes = [M, _dp, _ip, C.c_int, C.c_int, C.c_int, _dp, M]
+        L.orc1_forward_logits.restype = None
+        L.orc1_forward_logits.argtypes = [M, _dp, _ip, C.c_int, C.c_int, _dp]
+        L.orc_set_num_threads.restype = None
+        L.orc_set_num_threads.argtypes = [C.c_int]
+        _LIBS["f64"] = L
+    return _LIBS["f64"]
+
+
 class emulate_bf16:
     """`with orc.emulate_bf16():` -- the checker rounds to bfloat16 wherever the HIP library's bf16 arithmetic does
-    (ORC_EMULATE_BF16, lrcn_oracle.h).  Outside the block the oracle is the plain fp32-storage restatement again."""
+    (ORC_EMULATE_BF16, lrcn_oracle.h).  Outside the block loss() and forward_logits() are the double-storage restatement again (lib64)."""
 
     def __init__(self, on=True):
         self.on = bool(on)
@@ -142,6 +173,22 @@ def bf16_round(a):
 
 def _f(a):
     return a.ctypes.data_as(_fp) if a is not None else None
+
+
+def _d(a):
+    return a.ctypes.data_as(_dp) if a is not None else None
+
+
+def _wide(a):
+    """The float32 array widened to float64, same (Fortran / C) layout; None stays None."""
+    return None if a is None else a.astype(np.float64, order="K")
+
+
+def _cstruct64(model, arrays):
+    m = _Model64(model.E, model.H1, model.H2, model.V)
+    for n in PARAM_NAMES:
+        setattr(m, n, _d(arrays[n]))
+    return m
 
 
 def fa(x, shape=None):
@@ -204,10 +251,12 @@ def _tok(tokens):
     return t
 
 
-def loss(model, feats, tokens, norm_B=None, mask1=None, mask2=None, want_grad=False, fast=False):
+def loss(model, feats, tokens, norm_B=None, mask1=None, mask2=None, want_grad=False, fast=False, wide=True):
     """loss / lossgradient (lrcn.jl:553-583). feats: B x 4096; tokens: [T][B] int (0-based).
     mask1: [(T+1)] x (B x E), mask2: [(T+1)] x (B x H2) dropout multipliers, as arrays of shape (T+1, B, E) /
-    (T+1, B, H2) (each block is stored column-major)."""
+    (T+1, B, H2) (each block is stored column-major).
+    wide=False: the float-storage build even when not emulating (what bf16 emulation and fast= run on), for the test that pins it
+    to the double-storage one."""
     tokens = _tok(tokens)
     T, B = tokens.shape
     feats = fa(feats)
@@ -217,6 +266,18 @@ def loss(model, feats, tokens, norm_B=None, mask1=None, mask2=None, want_grad=Fa
         m1 = np.ascontiguousarray(np.stack([np.asfortranarray(b).ravel(order="F") for b in mask1]), dtype=np.float32)
     if mask2 is not None:
         m2 = np.ascontiguousarray(np.stack([np.asfortranarray(b).ravel(order="F") for b in mask2]), dtype=np.float32)
+    if wide and not fast and not lib().orc_get_emulate_bf16():
+        # the checker proper: the same source with double storage, on the float32 inputs widened; gradients returned as float32
+        w = {n: _wide(model.p[n]) for n in PARAM_NAMES}
+        gw = {n: np.zeros_like(w[n]) for n in PARAM_NAMES} if want_grad else None
+        cs, gs = _cstruct64(model, w), (_cstruct64(model, gw) if want_grad else None)
+        f64, m1, m2 = _wide(feats), _wide(m1), _wide(m2)
+        t, gp = tokens.ctypes.data_as(_ip), (C.byref(gs) if want_grad else None)
+        if model.n_layers == 1:
+            val = lib64().orc1_loss(C.byref(cs), _d(f64), t, T, B, norm_B or B, _d(m1), gp)
+        else:
+            val = lib64().orc_loss(C.byref(cs), _d(f64), t, T, B, norm_B or B, _d(m1), _d(m2), gp)
+        return (val, Model(model.E, model.H1, model.H2, model.V, gw, model.n_layers)) if want_grad else val
     cs = model.cstruct()
     g = model.zeros_like() if want_grad else None
     gs = g.cstruct() if want_grad else None
@@ -233,6 +294,13 @@ def forward_logits(model, feats, tokens):
     tokens = _tok(tokens)
     T, B = tokens.shape
     feats = fa(feats)
+    if not lib().orc_get_emulate_bf16():   # double storage, as loss()
+        out = np.zeros((T + 1, model.V, B), dtype=np.float64)
+        w, f64 = {n: _wide(model.p[n]) for n in PARAM_NAMES}, _wide(feats)
+        cs = _cstruct64(model, w)
+        (lib64().orc1_forward_logits if model.n_layers == 1 else lib64().orc_forward_logits)(
+            C.byref(cs), _d(f64), tokens.ctypes.data_as(_ip), T, B, _d(out))
+        return np.transpose(out, (0, 2, 1)).astype(np.float32)
     out = np.zeros((T + 1, model.V, B), dtype=np.float32)  # each block B x V column-major == [V][B] C-order
     cs = model.cstruct()
     (lib().orc1_forward_logits if model.n_layers == 1 else lib().orc_forward_logits)(C.byref(cs), _f(feats), tokens.ctypes.data_as(_ip),
@@ -424,3 +492,5 @@ def effective_cpus():
 def set_num_threads(n, fast=None):
     for f in ((False, True) if fast is None else (fast,)):
         lib(f).orc_set_num_threads(int(n))
+    if not fast:
+        lib64().orc_set_num_threads(int(n))

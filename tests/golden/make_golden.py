@@ -3,18 +3,19 @@
 
 The reference is Julia/Knet and cannot run in this container (no julia), so these vectors
 are NOT outputs of the reference: they come from an independent torch-CPU float64 *autograd* transcription of
-lrcn.jl written below (forward only is transcribed; every gradient is torch autograd's, not hand-derived), and
+lrcn.jl (tests/torch_ref.py: forward only is transcribed; every gradient is torch autograd's, not hand-derived), and
 serve to pin the C oracle (oracle/lrcn_oracle.c, hand-derived backward) and the HIP path against a second
 statement of the same algorithm.  Run from the repo root:  python tests/golden/make_golden.py
 """
 import os
+import sys
 
 import numpy as np
 import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-EOS, BOS, UNK = 0, 1, 2
-torch.set_default_dtype(torch.float64)
+sys.path.insert(0, os.path.dirname(HERE))
+from torch_ref import adam_ref, beam_search_ref, beam_search_ref1, loss, loss1  # noqa: E402  (tests/torch_ref.py: the transcription)
 
 
 def xavier(rng, rows, cols):
@@ -31,86 +32,6 @@ def init_model(rng, E, H1, H2, V, F=4096):
     return {"W1": xavier(rng, E + H1, 4 * H1), "b1": b1, "W2": xavier(rng, 2 * H2, 4 * H2), "b2": b2,
             "Wproj": xavier(rng, H1, h), "Wcnn": xavier(rng, F, h), "Wembed": xavier(rng, V, E),
             "Wout": xavier(rng, H2, V), "bout": (0.1 * rng.standard_normal((1, V))).astype(np.float32)}
-
-
-def lstm(W, b, h, c, x):  # lrcn.jl:528-538
-    gates = torch.cat([x, h], 1) @ W + b
-    H = h.shape[1]
-    f = torch.sigmoid(gates[:, :H])
-    i = torch.sigmoid(gates[:, H:2 * H])
-    o = torch.sigmoid(gates[:, 2 * H:3 * H])
-    g = torch.tanh(gates[:, 3 * H:])
-    c = c * f + i * g
-    h = o * torch.tanh(c)
-    return h, c
-
-
-def lrcn(p, s, x_cnn, x_lstm, m1=None, m2=None):  # lrcn.jl:540-551
-    x = x_lstm if m1 is None else x_lstm * m1
-    s[0], s[1] = lstm(p["W1"], p["b1"], s[0], s[1], x)
-    x = s[0] @ p["Wproj"]
-    x = torch.cat([x, x_cnn], 1)
-    if m2 is not None:
-        x = x * m2
-    s[2], s[3] = lstm(p["W2"], p["b2"], s[2], s[3], x)
-    return s[2] @ p["Wout"] + p["bout"]
-
-
-def loss(p, feats, tokens, norm_B, mask1=None, mask2=None, collect=None):  # lrcn.jl:553-581
-    T, B = tokens.shape
-    H1 = p["Wproj"].shape[0]
-    H2 = p["Wout"].shape[0]
-    s = [torch.zeros(B, H1), torch.zeros(B, H1), torch.zeros(B, H2), torch.zeros(B, H2)]
-    total = 0.0
-    count = 0
-    x_lstm = p["Wembed"][torch.full((B,), BOS, dtype=torch.long)]
-    x_cnn = feats @ p["Wcnn"]
-    for t in range(T + 1):
-        ypred = lrcn(p, s, x_cnn, x_lstm, None if mask1 is None else mask1[t], None if mask2 is None else mask2[t])
-        if collect is not None:
-            collect.append(ypred.detach().numpy().astype(np.float32))
-        ynorm = torch.log_softmax(ypred, 1)
-        tgt = torch.as_tensor(tokens[t], dtype=torch.long) if t < T else torch.full((B,), EOS, dtype=torch.long)
-        total = total + ynorm[torch.arange(B), tgt].sum()
-        count += norm_B
-        if t < T:
-            x_lstm = p["Wembed"][tgt]
-    return -total / count
-
-
-def adam_ref(w, g, m, v, t, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):  # Knet Adam defaults
-    m = b1 * m + (1 - b1) * g
-    v = b2 * v + (1 - b2) * g * g
-    w = w - lr * (m / (1 - b1 ** t)) / (np.sqrt(v / (1 - b2 ** t)) + eps)
-    return w, m, v
-
-
-def beam_search_ref(p, feat, K, nword):  # lrcn.jl:585-678 / SURVEY A.3, float32 probabilities like the reference
-    with torch.no_grad():
-        H1 = p["Wproj"].shape[0]
-        H2 = p["Wout"].shape[0]
-        x_cnn = feat @ p["Wcnn"]
-        x = [([BOS], np.float32(1.0)) for _ in range(K)]
-        states = [[torch.zeros(1, H1), torch.zeros(1, H1), torch.zeros(1, H2), torch.zeros(1, H2)] for _ in range(K)]
-        current = 1
-        while True:
-            new_x = []
-            for i in range(K):
-                last = x[i][0][-1]
-                yp = lrcn(p, states[i], x_cnn, p["Wembed"][last:last + 1])
-                prob = torch.softmax(yp, 1).numpy().astype(np.float32).reshape(-1)
-                top = np.argsort(-prob, kind="stable")[:K]
-                for j in range(K):
-                    new_x.append((x[i][0] + [int(top[j])], np.float32(prob[top[j]] * x[i][1])))
-                if current == 1:
-                    break
-            order = np.argsort(-np.array([c[1] for c in new_x], np.float32), kind="stable")
-            xs = [new_x[o] for o in order[:K]]
-            if xs[0][0][-1] == EOS or current > nword:
-                return xs
-            states = [[t.clone() for t in states[order[i] // K]] for i in range(K)]
-            x = xs
-            current += 1
 
 
 def make_lstm_case(name, seed, B, E, H1, H2, V, T, pdrop, norm_B=None, nadam=2, beam=None):
@@ -130,7 +51,7 @@ def make_lstm_case(name, seed, B, E, H1, H2, V, T, pdrop, norm_B=None, nadam=2, 
     L = loss(p, torch.tensor(feats, dtype=torch.float64), tokens, norm_B, tm1, tm2, collect=logits)
     L.backward()
     out = {"E": E, "H1": H1, "H2": H2, "V": V, "T": T, "B": B, "norm_B": norm_B, "pdrop": pdrop,
-           "feats": feats, "tokens": tokens, "loss": np.float64(L.item()), "logits": np.stack(logits)}
+           "feats": feats, "tokens": tokens, "loss": np.float64(L.item()), "logits": np.stack([y.numpy().astype(np.float32) for y in logits])}
     if mask1 is not None:
         out["mask1"], out["mask2"] = mask1, mask2
     for k in P:
@@ -179,62 +100,6 @@ def init_model1(rng, E, H, V, F=4096):
             "Wembed": xavier(rng, V, E), "Wout": xavier(rng, H, V), "bout": (0.1 * rng.standard_normal((1, V))).astype(np.float32)}
 
 
-def lrcn1(p, s, x_cnn, x_lstm, m=None):
-    x = torch.cat([x_lstm, x_cnn], 1)
-    if m is not None:
-        x = x * m
-    s[0], s[1] = lstm(p["W1"], p["b1"], s[0], s[1], x)
-    return s[0] @ p["Wout"] + p["bout"]
-
-
-def loss1(p, feats, tokens, norm_B, mask=None, collect=None):  # lrcn.jl:553-581 around lrcn1
-    T, B = tokens.shape
-    H = p["Wout"].shape[0]
-    s = [torch.zeros(B, H), torch.zeros(B, H)]
-    total = 0.0
-    count = 0
-    x_lstm = p["Wembed"][torch.full((B,), BOS, dtype=torch.long)]
-    x_cnn = feats @ p["Wcnn"]
-    for t in range(T + 1):
-        ypred = lrcn1(p, s, x_cnn, x_lstm, None if mask is None else mask[t])
-        if collect is not None:
-            collect.append(ypred.detach().numpy().astype(np.float32))
-        ynorm = torch.log_softmax(ypred, 1)
-        tgt = torch.as_tensor(tokens[t], dtype=torch.long) if t < T else torch.full((B,), EOS, dtype=torch.long)
-        total = total + ynorm[torch.arange(B), tgt].sum()
-        count += norm_B
-        if t < T:
-            x_lstm = p["Wembed"][tgt]
-    return -total / count
-
-
-def beam_search_ref1(p, feat, K, nword):
-    with torch.no_grad():
-        H = p["Wout"].shape[0]
-        x_cnn = feat @ p["Wcnn"]
-        x = [([BOS], np.float32(1.0)) for _ in range(K)]
-        states = [[torch.zeros(1, H), torch.zeros(1, H)] for _ in range(K)]
-        current = 1
-        while True:
-            new_x = []
-            for i in range(K):
-                last = x[i][0][-1]
-                yp = lrcn1(p, states[i], x_cnn, p["Wembed"][last:last + 1])
-                prob = torch.softmax(yp, 1).numpy().astype(np.float32).reshape(-1)
-                top = np.argsort(-prob, kind="stable")[:K]
-                for j in range(K):
-                    new_x.append((x[i][0] + [int(top[j])], np.float32(prob[top[j]] * x[i][1])))
-                if current == 1:
-                    break
-            order = np.argsort(-np.array([c[1] for c in new_x], np.float32), kind="stable")
-            xs = [new_x[o] for o in order[:K]]
-            if xs[0][0][-1] == EOS or current > nword:
-                return xs
-            states = [[t.clone() for t in states[order[i] // K]] for i in range(K)]
-            x = xs
-            current += 1
-
-
 def make_lstm1_case(name, seed, B, E, H, V, T, pdrop, norm_B=None, nadam=2, beam=None):
     rng = np.random.default_rng(seed)
     norm_B = norm_B or B
@@ -250,7 +115,7 @@ def make_lstm1_case(name, seed, B, E, H, V, T, pdrop, norm_B=None, nadam=2, beam
     L = loss1(p, torch.tensor(feats, dtype=torch.float64), tokens, norm_B, tm, collect=logits)
     L.backward()
     out = {"E": E, "H1": H, "H2": H, "V": V, "T": T, "B": B, "norm_B": norm_B, "pdrop": pdrop, "n_layers": 1,
-           "feats": feats, "tokens": tokens, "loss": np.float64(L.item()), "logits": np.stack(logits)}
+           "feats": feats, "tokens": tokens, "loss": np.float64(L.item()), "logits": np.stack([y.numpy().astype(np.float32) for y in logits])}
     if mask is not None:
         out["mask1"] = mask
     for k in P:

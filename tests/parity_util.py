@@ -20,6 +20,11 @@ against the PLAIN f32 oracle (no emulation, nothing taken from the HIP sources):
     gradients   ||g - g_f32|| <= 2e-2 ||g_f32||   per tensor
                 (the emulating oracle itself sits at 3e-3 .. 6e-3 of the f32 oracle at E = H = 1000: bf16 operands of 12-step recurrences;
                  an extra rounding of a whole operand class adds ~4e-3 per occurrence in quadrature, a dropped / doubled term >= 5e-2)
+
+THE SHARP REGIME (tests/production_width.py: max |logit| 32 .. 51, 121 in c4-rows64, mean p(target) >= 0.4, saturating gates).  There the elementwise constants
+fail for the emulation itself: the oracle's double- and float-accumulating builds, both emulating, differ by 8e-6 .. 1.2e-4 on the loss and
+4e-4 .. 3.2e-3 per tensor in norm (one flipped bf16 of h moves a logit by ~0.1).  tests/test_gpu_production_width.py therefore holds the HIP
+result (measured 2e-6 .. 8e-5 on the loss, 1.9e-4 .. 3.4e-3 per tensor) to twice the distance of those two orders, computed in the test.
 """
 import numpy as np
 

@@ -33,7 +33,7 @@ class Grads:
         self.f32 = None
 
 
-def loss(model, feats, tokens, lens, norm_tokens=None, mask1=None, mask2=None, want_grad=False, row_norms=None):
+def loss(model, feats, tokens, lens, norm_tokens=None, mask1=None, mask2=None, want_grad=False, row_norms=None, fast=False):
     """tokens [Tmax][B] (entries at t >= lens[b] are never looked at), lens [B], masks (Tmax + 1, B, .) as orc.loss takes them."""
     tokens = np.asarray(tokens, dtype=np.int32)
     feats = np.asarray(feats, dtype=np.float32)
@@ -49,7 +49,7 @@ def loss(model, feats, tokens, lens, norm_tokens=None, mask1=None, mask2=None, w
             kw["mask1"] = np.asarray(mask1)[:n + 1, b:b + 1]
         if mask2 is not None:
             kw["mask2"] = np.asarray(mask2)[:n + 1, b:b + 1]
-        r = orc.loss(model, feats[b:b + 1], tokens[:n, b:b + 1].reshape(n, 1), norm_B=nb, want_grad=want_grad, **kw)
+        r = orc.loss(model, feats[b:b + 1], tokens[:n, b:b + 1].reshape(n, 1), norm_B=nb, want_grad=want_grad, fast=fast, **kw)
         val, g = r if want_grad else (r, None)
         total += w * float(val)
         if want_grad:
