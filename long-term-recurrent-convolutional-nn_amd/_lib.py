@@ -16,6 +16,7 @@ SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
+GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -39,6 +40,13 @@ class Config(C.Structure):
 class ActConfig(C.Structure):   # lrcn_act_config of include/lrcn_activity.h
     _fields_ = [("device", C.c_int), ("F", C.c_int), ("H", C.c_int), ("C", C.c_int), ("max_B", C.c_int), ("max_T", C.c_int),
                 ("dtype", C.c_int), ("deterministic", C.c_int)]
+
+
+class GemmDebug(C.Structure):   # lrcn_gemm_debug of include/lrcn_gemm_debug.h
+    _fields_ = [("dtype", C.c_int), ("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("bias", C.c_void_p),
+                ("lda", C.c_int64), ("ldb", C.c_int64), ("ldc", C.c_int64), ("M", C.c_int), ("N", C.c_int), ("K", C.c_int),
+                ("c_f32", C.c_int), ("beta", C.c_int), ("relu", C.c_int), ("c_is_zero", C.c_int), ("deterministic", C.c_int),
+                ("free_cus", C.c_int), ("bg_cus", C.c_int), ("wg_cap", C.c_int)]
 
 
 class Dropout(C.Structure):
@@ -177,11 +185,16 @@ VARLEN_SIGNATURES = {
                                       C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_gemm_debug.h declares (bound by lib() as well)
+GEMM_DEBUG_SIGNATURES = {
+    "lrcn_debug_gemm": (C.c_int, [C.c_void_p, C.POINTER(GemmDebug)]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -202,7 +215,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()):
+                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -110,8 +110,11 @@ hipError_t launch_gemm(hipStream_t stream, const GemmArgs &g);
 // gemm.hip: the register-staged kernel for any shape that passed the router's argument checks (f32 or bf16)
 hipError_t launch_gemm_nt(hipStream_t stream, const GemmArgs &g);
 
-// Test / development aid: the kernel family the most recent launch on this thread took ("8p:0" = 256x256 tile, "8p:1" = 256x128,
-// "8p:2" = 512x128, "8p-splitk:N", "glds", "skinny", "gemm_nt", "conv64", "conv64-fused11", ...).  lrcn_debug_last_route() returns it.
+// Test / development aid: the rung of gemm_route.hip's ladder the most recent launch_gemm on this thread took, with a ":suffix" only
+// where gemm_8p.hip ran: "8p:0" = 256x256 tile, "8p:1" = 256x128, "8p:2" = 512x128, "8p-bg:1" (the same tile configs), "8p-f8:<cfg>",
+// "8p-splitk:<K slices>"; "skinny", "glds", "skinny-last", "glds-small" and "gemm_nt" carry none (their tile config and K-slice count
+// are not reported).  The convolution side notes its own families ("conv64", "conv64-fused11", ...).  lrcn_debug_route(ctx, 0) returns it;
+// it is written even when the launch is refused ("?" when no rung was reached).
 void gemm_debug_note_route(const char *route, int cfg);
 const char *gemm_debug_last_route();
 

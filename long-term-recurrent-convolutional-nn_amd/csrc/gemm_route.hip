@@ -1,13 +1,14 @@
 // gemm_route.hip -- launch_gemm: which engine a contraction runs on (gemm.h).  No kernel lives here.  The ladder below is tried top to bottom
-// and the first rung that fits takes the launch; its name is what lrcn_debug_route reports:
+// and the first rung that fits takes the launch; its name is what lrcn_debug_route reports, followed by ":<tile config>" (0 = 256 x 256,
+// 1 = 256 x 128, 2 = 512 x 128) on the 8p-f8 / 8p / 8p-bg rungs and ":<K slices>" on 8p-splitk, and by nothing on the others:
 //   8p-f8       e4m3 convolutions: gemm_8p.hip or nothing
 //   8p          gemm_8p.hip when its grid fills the chip (or the CUs free beside the capped convolution grids)
 //   8p-bg       gemm_8p.hip on few 256 x 128 tiles, for kBgMinRows..kBgMaxRows rows beside the capped convolution grids
-//   skinny      gemm_skinny.hip, M <= 128
+//   skinny      gemm_skinny.hip, M <= 128 (with its own slab split-K for long K and few column tiles, not named in the route)
 //   8p-splitk   gemm_8p.hip with K cut into slices
 //   glds        gemm_glds.hip when its grid fills the chip
 //   skinny-last gemm_skinny.hip, whatever M it accepts
-//   glds-small  gemm_glds.hip on few tiles (still far ahead of gemm_nt)
+//   glds-small  gemm_glds.hip on few tiles (still far ahead of gemm_nt); glds and glds-small count tiles x atomic K-slices
 //   gemm_nt     gemm.hip's register-staged kernel: every other shape, f32 included
 #include <cstdio>
 

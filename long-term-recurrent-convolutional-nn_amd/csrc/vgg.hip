@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "../../include/lrcn_gemm_debug.h"
 
 using namespace lrcn_impl;
 
@@ -428,6 +429,45 @@ int lrcn_bench_gemm(lrcn_ctx *c, int M, int N, int K, int iters, double *ms_out)
     cleanup();
     if (r) return r;
     *ms_out = ms / iters;
+    return LRCN_OK;
+}
+
+// Test entry (include/lrcn_gemm_debug.h): ONE contraction through launch_gemm on the caller's operands, filled as lrcn_impl::gemm fills its
+// own -- except K, which goes to the engines as given, and the router inputs lrcn_impl::gemm derives from a capped VGG grid, which the
+// caller states.  No allocation, no conversion; the stream is drained before the call returns.
+int lrcn_debug_gemm(lrcn_ctx *c, const lrcn_gemm_debug *d) {
+    DeviceGuard dg(c);
+    if (!c || !d) return LRCN_EINVAL;
+    if (d->dtype != LRCN_F32 && d->dtype != LRCN_BF16) FAIL(c, LRCN_EINVAL, "debug_gemm: dtype %d is neither f32 nor bf16", d->dtype);
+    GemmArgs g{};
+    g.dtype = d->dtype == LRCN_BF16 ? GEMM_T_BF16 : GEMM_T_F32;
+    g.A = d->A;
+    g.lda = d->lda;
+    g.B = d->B;
+    g.ldb = d->ldb;
+    g.C = d->C;
+    g.ldc = d->ldc;
+    g.M = d->M;
+    g.N = d->N;
+    g.K = d->K;
+    g.bias = d->bias;
+    g.c_f32 = d->c_f32 != 0;
+    g.beta = d->beta != 0;
+    g.c_is_zero = d->c_is_zero != 0;
+    g.relu = d->relu != 0;
+    g.a_mode = GEMM_A_PLAIN;
+    g.out_mode = GEMM_OUT_PLAIN;
+    g.zero_page = c->zero_page;
+    g.deterministic = d->deterministic != 0;
+    g.ws = c->gemm_ws;
+    g.ws_bytes = c->gemm_ws_bytes;
+    g.free_cus = d->free_cus;
+    g.bg_cus = d->bg_cus;
+    g.wg_cap = d->wg_cap;
+    const hipError_t e = launch_gemm(c->stream, g);
+    if (e != hipSuccess)
+        FAIL(c, e == hipErrorInvalidValue ? LRCN_EINVAL : LRCN_EHIP, "debug_gemm M=%d N=%d K=%d: %s", d->M, d->N, d->K, hipGetErrorString(e));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return LRCN_OK;
 }
 

@@ -751,6 +751,26 @@ def debug_route(ctx, which=0):
     return r.decode() if r else ""
 
 
+def debug_gemm(ctx, dtype, A, B, Cmat, M, N, K, lda, ldb, ldc, bias=None, c_f32=False, beta=False, relu=False, c_is_zero=False,
+               deterministic=False, free_cus=0, bg_cus=0, wg_cap=0):
+    """C[M][N] (+)= A[M][K] B[N][K]^T (+ bias) (ReLU) through the GEMM router on the caller's device operands (lrcn_debug_gemm,
+    include/lrcn_gemm_debug.h): A, B, Cmat, bias are device tensors already in their element type (sub-views welcome: data_ptr() is what
+    goes down) or raw addresses (int / None); leading dimensions in elements.  Returns the route that ran (debug_route(ctx, 0))."""
+    def addr(t):
+        if t is None:
+            return None
+        if torch.is_tensor(t):
+            if not t.is_cuda:
+                raise LrcnError("expected a CUDA (HIP) tensor")
+            return C.c_void_p(t.data_ptr())
+        return C.c_void_p(int(t))
+    g = _lib.GemmDebug(int(dtype), addr(A), addr(B), addr(Cmat), addr(bias), int(lda), int(ldb), int(ldc), int(M), int(N), int(K),
+                       int(bool(c_f32)), int(bool(beta)), int(bool(relu)), int(bool(c_is_zero)), int(bool(deterministic)),
+                       int(free_cus), int(bg_cus), int(wg_cap))
+    ctx._call("lrcn_debug_gemm", C.byref(g))
+    return debug_route(ctx, 0)
+
+
 def synthetic_vgg_weights(seed=1, device="cuda", bias_std=0.0):
     """He-normal(fan_in) VGG-16 weights (no pretrained file offline); biases zero, or N(0, bias_std)
     so that every bias path of the kernels sees non-zero values (parity tests)."""
