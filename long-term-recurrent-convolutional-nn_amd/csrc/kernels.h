@@ -108,10 +108,8 @@ void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, 
 // k_softmax_xent_masked skips by; tokens[t][b] at t >= lens[b] is never read, so padding cannot raise the sticky flag.
 void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *lens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt,
                         double *zero_acc);
-// dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32).
-void k_embed_scatter(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E,
-                     int V, DropSpec d, float *dwembed);
-// The same through an E-contiguous staging array stage[V][ld_s] (f32, all zero on entry and on exit): coalesced atomics per token row,
+// dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32),
+// through an E-contiguous staging array stage[V][ld_s] (f32, all zero on entry and on exit): coalesced atomics per token row,
 // then one dense transpose that writes EVERY element of dwembed (no memset needed).  sort_keys != NULL ((T+1)*B <= 8192 keys of scratch):
 // the rows of a token are added in a fixed order by plain stores instead (LRCN_OPT_DETERMINISTIC); false = more than 8192 rows, nothing
 // was launched.

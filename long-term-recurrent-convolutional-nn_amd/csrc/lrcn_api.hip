@@ -576,20 +576,16 @@ int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const in
             k_embed_rows_export(st, c->dXemb, c->ldX1, S, B, E, two ? d1 : none, c->emb_rows_out);
             HIPCHK(c, hipMemcpyAsync(c->emb_tok_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
         } else {
-            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (train_kernels.hip);
-            // where that kernel declines, the direct scatter (one float atomic per element, 64 cache lines per wave instruction).
+            // dWembed: per-token sums in an E-contiguous staging array, then one transpose into the column-major gradient (train_kernels.hip).
             if (!c->dWe_rm) DALLOC(c, c->dWe_rm, sizeof(float) * (size_t)V * c->ldE);
             unsigned long long *keys = nullptr;
             if (c->opt_det) {
                 if (!c->sort_keys) DALLOC(c, c->sort_keys, sizeof(unsigned long long) * (size_t)c->maxS * c->maxB);
                 keys = c->sort_keys;
             }
-            const bool done = k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, grads[6], keys);
-            if (!done && c->opt_det) FAIL(c, LRCN_EINVAL, "LRCN_OPT_DETERMINISTIC supports (T+1)*B <= 8192 rows per call (got %d)", M);
-            if (!done) {
-                HIPCHK(c, hipMemsetAsync(grads[6], 0, sizeof(float) * (size_t)V * E, st));
-                k_embed_scatter(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, grads[6]);
-            }
+            // declines only with sort keys: more rows than the counting sort ranks
+            if (!k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, grads[6], keys))
+                FAIL(c, LRCN_EINVAL, "LRCN_OPT_DETERMINISTIC supports (T+1)*B <= 8192 rows per call (got %d)", M);
         }
         HIPCHK(c, hipEventRecord(c->grad_ev[4], st));  // group 4: Wembed
         return LRCN_OK;

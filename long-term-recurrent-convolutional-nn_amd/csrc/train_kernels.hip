@@ -50,18 +50,6 @@ __global__ void build_tokens_var_kernel(const int32_t *tokens, const int32_t *le
     tok_tgt[i] = tg;
 }
 
-__global__ void embed_scatter_kernel(const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V,
-                                     DropSpec d, float *dwembed) {
-    const int m = blockIdx.x;
-    const int s = m / B, b = m - s * B;
-    const int tok = tok_in[m];
-    const float *src = dxemb + (int64_t)m * ld_dx;
-    for (int e = threadIdx.x; e < E; e += blockDim.x) {
-        const float v = src[e] * drop_mult(d, s, b, e, B, E);
-        if (v != 0.0f) atomicAdd(dwembed + (int64_t)e * V + tok, v);
-    }
-}
-
 // ---- embedding gradient, E-contiguous form (dual of the gather, lrcn.jl:556/569 under AutoGrad) ----
 // The Wembed gradient of the ABI is V x E column-major (memory [E][V]): a row of dXemb scattered straight into it touches E different
 // cache lines per token (64 lanes -> 64 lines per wave instruction).  Instead: (1) rows are summed per token into a ROW-MAJOR f32
@@ -383,10 +371,6 @@ void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *le
 }
 void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out) {
     hipLaunchKernelGGL(embed_rows_export_kernel, dim3(S * B), dim3(256), 0, st, dxemb, ld_dx, S, B, E, d, out);
-}
-void k_embed_scatter(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V,
-                     DropSpec d, float *dwembed) {
-    hipLaunchKernelGGL(embed_scatter_kernel, dim3(S * B), dim3(256), 0, st, dxemb, ld_dx, tok_in, S, B, E, V, d, dwembed);
 }
 bool k_embed_scatter_rm(hipStream_t st, const float *dxemb, int64_t ld_dx, const int32_t *tok_in, int S, int B, int E, int V, DropSpec d,
                         float *stage, int64_t ld_s, float *dwembed, unsigned long long *sort_keys) {

@@ -25,6 +25,7 @@ import os
 import numpy as np
 import torch
 
+import dropout_ref as dr
 import torch_ref as tr
 import varlen_ref as vr
 from oracle import oracle as orc
@@ -36,13 +37,17 @@ CASES = {
     "c1": dict(C1, B=16, T=11),                              # fused small-batch recurrence, skinny GEMMs
     "c4-slice": dict(C4, B=8, T=3),                          # H = 1000 tails, V = 10640 softmax
     "c1-masks": dict(C1, B=16, T=5, keep=0.6, norm_B=64),    # explicit dropout masks, a global batch of 4 B
+    "c1-seeded": dict(C1, B=16, T=5, pdrop=0.4, seed=0xC0FFEE0000000123, norm_B=64),   # c1-masks' shape, the DEVICE-generated masks
     "1f": dict(C1, B=16, T=5, n_layers=1),                   # LRCN-1f
     "varlen": dict(C1, B=13, T=7, lens=(7, 0, 3, 1, 7, 3, 0, 1, 3, 7, 1, 3, 7)),   # sum(lens + 1) = 56, a multiple of every len + 1
     "c1-rows256": dict(C1, B=256, T=3),                      # GEMM + cell kernel, >= 256-row xent and embedding scatter
     "c4-rows64": dict(C4, B=64, T=1),                        # the 64-row boundary of the fused forms
 }
-CPU_CASES = ("c1", "c4-slice", "c1-masks", "1f", "varlen")
-GPU_CASES = ("c1", "c1-rows256", "c4-slice", "c4-rows64", "1f", "varlen")
+CPU_CASES = ("c1", "c4-slice", "c1-masks", "1f", "varlen", "c1-seeded")
+GPU_CASES = ("c1", "c1-rows256", "c4-slice", "c4-rows64", "1f", "varlen", "c1-seeded")
+# A case's inputs are seeded by its number.  Cases added after the first seven take the next numbers, so that the earlier ones keep theirs.
+_LATER = ("c1-seeded",)
+CASE_NUMBER = {n: i for i, n in enumerate(sorted(set(CASES) - set(_LATER)) + list(_LATER))}
 SHARP_SCALE = {"W1": 4.0, "W2": 4.0, "Wcnn": 12.0}
 SHARP_RMS = {"Wembed": 1.3}
 SHARP_WOUT_RMS = (1.0, 1.25, 1.5, 2.0, 3.0, 4.0, 6.0)   # rungs of Wout's rms: a case takes the first at which mean p(target) reaches P_TARGET_MIN
@@ -123,13 +128,14 @@ def p_target(c, logits):
 
 @functools.lru_cache(maxsize=None)
 def case(name, regime):
-    """The inputs of one case: model (orc.Model), feats, tokens [T][B], mask1 / mask2, lens / norm_tokens, norm_B."""
+    """The inputs of one case: model (orc.Model), feats, tokens [T][B], mask1 / mask2, lens / norm_tokens, norm_B, pdrop / seed (None unless
+    the masks are the device's own, which the GPU test then asks for by (pdrop, seed) and every reference takes as mask1 / mask2)."""
     d = CASES[name]
     c = Case()
     c.name, c.regime = name, regime
     c.E = c.H = d["E"]
     c.V, c.B, c.T, c.n_layers = d["V"], d["B"], d["T"], d.get("n_layers", 2)
-    seed = 1000 + 10 * sorted(CASES).index(name) + REGIMES.index(regime)
+    seed = 1000 + 10 * CASE_NUMBER[name] + REGIMES.index(regime)
     for wout_rms in (SHARP_WOUT_RMS if regime == "sharp" else (None,)):   # the mildest rung that reaches the regime: sharp, and no sharper
         c = _build(c, d, seed, wout_rms)
         if wout_rms is None or p_target(c, _forward(c)) >= P_TARGET_MIN:
@@ -152,6 +158,9 @@ def _build(c, d, seed, wout_rms):
     c.tokens = rng.integers(3, c.V, size=(c.T, c.B)).astype(np.int32)
     c.mask1 = c.mask2 = c.lens = c.norm_tokens = None
     c.norm_B = d.get("norm_B", c.B)
+    c.pdrop, c.seed = d.get("pdrop"), d.get("seed")
+    if c.pdrop is not None:   # tests/dropout_ref.py: the host transcription of the device's counter hash
+        c.mask1, c.mask2 = dr.masks(c.seed, c.pdrop, c.T, c.B, c.E, c.H, c.n_layers)
     if "keep" in d:
         keep = d["keep"]
         c.mask1 = ((rng.random((c.T + 1, c.B, c.E)) < keep) / keep).astype(np.float32)

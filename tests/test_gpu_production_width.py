@@ -1,6 +1,8 @@
 """GPU: liblrcn_hip.so at the caption model's real widths, DIRECTLY against the float64 autograd transcription (tests/torch_ref.py), not
 against the C oracle.  Cases by the route the row count selects, each in the `init` and the `sharp` regime (tests/production_width.py), in
-f32 and bf16; each reference is computed once per process and shared between the types.
+f32 and bf16; each reference is computed once per process and shared between the types.  c1-seeded runs with the DEVICE-generated dropout
+masks (pdrop, seed): its references take the host transcription of the counter hash (tests/dropout_ref.py) as explicit masks, so a mask
+that differs from the transcription in one stream, one index or one comparison fails the same bounds; its logits are not compared.
 
 f32: the constants of the existing f32 parity tests -- loss 1e-5 relative, gradients rtol 1e-3 + atol 1e-5, per-step logits rtol 1e-5 +
 atol 1e-5 max|ref| -- and, because at init whole tensors (dW1, dWproj, dWembed: max|g| 2e-6 .. 6e-5) sit under that atol, each gradient
@@ -42,6 +44,9 @@ def run(c, dtype, logits=False):
     ctx = L.Context(c.E, c.H, c.H, c.V, max_B=c.B, max_T=c.T, lstm_dtype=dtype, n_layers=c.n_layers)
     param = L.model_from_arrays(c.model.p)
     kw = dict(lens=c.lens, norm_tokens=c.norm_tokens) if c.lens is not None else dict(norm_B=c.norm_B)
+    if c.pdrop is not None:   # the device's own masks, by (pdrop, seed): the references got the host transcription of them as mask1 / mask2
+        kw.update(pdrop=c.pdrop, seed=c.seed)
+        logits = False        # the logits entry point takes no dropout
     grads, val = L.lossgradient(ctx, param, L.to_jl(c.feats), c.tokens, **kw)
     route = L.debug_route(ctx)
     g = {n: L.from_jl(t).astype(np.float64) for n, t in zip(orc.PARAM_NAMES, grads) if n in pw.live(c.model)}
@@ -57,16 +62,18 @@ def test_f32_loss_gradients_and_logits_vs_float64_autograd(name, regime):
     got, route = run(c, F32, logits=True)
     d, dl = pw.distances(got, ref)
     fd, fdl = pw.distances(pw.reference_f32(name, regime), ref)
-    print("%s %s f32: route %s; loss rel %.1e (float32 floor %.1e); per tensor HIP / floor: %s; logits max|d| / max|ref| %.1e" % (
+    print("%s %s f32: route %s; loss rel %.1e (float32 floor %.1e); per tensor HIP / floor: %s; logits max|d| / max|ref| %s" % (
         name, regime, route, dl, fdl, " ".join("%s %.1e/%.1e" % (n, d[n], fd[n]) for n in d),
-        np.abs(got.logits - ref.logits).max() / np.abs(ref.logits).max()))
+        "not compared (dropout)" if got.logits is None else "%.1e" % (np.abs(got.logits - ref.logits).max() / np.abs(ref.logits).max())))
     assert dl <= 1e-5
     for n in ref.g:
         # per tensor in norm first: at init max|dW1|, max|dWproj|, max|dWembed| are below the elementwise atol of 1e-5, which alone would
         # let an all-zero gradient (distance 1) or a wrong partial sum pass.  The elementwise rtol, taken over the whole tensor, has no atol.
         assert d[n] <= F32_GRAD_NORM, (n, d[n], fd[n])
         np.testing.assert_allclose(got.g[n], ref.g[n], rtol=1e-3, atol=1e-5, err_msg=n)
-    np.testing.assert_allclose(got.logits, ref.logits, rtol=1e-5, atol=1e-5 * np.abs(ref.logits).max())
+    assert (got.logits is None) == (c.pdrop is not None)
+    if got.logits is not None:
+        np.testing.assert_allclose(got.logits, ref.logits, rtol=1e-5, atol=1e-5 * np.abs(ref.logits).max())
 
 
 @pytest.mark.parametrize("name,regime", PAIRS, ids=ids)

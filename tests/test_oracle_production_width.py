@@ -71,7 +71,7 @@ def test_float_storage_build_stays_on_the_double_storage_one(name, regime):
         assert v <= FLOAT_STORAGE_NORM, (n, v)
 
 
-LOGIT_PAIRS = [p for p in PAIRS if p[0] != "c1-masks"]   # the logits entry point takes no masks
+LOGIT_PAIRS = [p for p in PAIRS if p[0] not in ("c1-masks", "c1-seeded")]   # the logits entry point takes no masks
 
 
 @pytest.mark.parametrize("name,regime", LOGIT_PAIRS, ids=["%s-%s" % p for p in LOGIT_PAIRS])
