@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("LRCN_HIP_LIB") or os.path.join(CSRC, "liblrcn_hip.so"
 HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn.h"))
 SAMPLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sample.h"))  # lrcn_sample_batch (not in lrcn.h)
 SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.h"))    # lrcn_score_matrix / _pairs (not in lrcn.h)
+NUCLEUS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nucleus.h"))  # lrcn_sample_batch_p / lrcn_sample_logits (not in lrcn.h)
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
@@ -148,6 +149,14 @@ SAMPLE_SIGNATURES = {
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_nucleus.h declares (bound by lib() as well)
+NUCLEUS_SIGNATURES = {
+    "lrcn_sample_batch_p": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_uint64,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int32)]),
+    "lrcn_sample_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                     C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # name -> (restype, argtypes); exactly the symbols include/lrcn_score.h declares (bound by lib() as well)
 SCORE_SIGNATURES = {
     "lrcn_score_matrix": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_void_p]),
@@ -193,7 +202,7 @@ GEMM_DEBUG_SIGNATURES = {
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, SCORE_HEADER, NBEST_HEADER,
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER,
                                                                                                    ACTIVITY_HEADER, VARLEN_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
@@ -214,7 +223,7 @@ def lib():
         # the one this process uses: import torch BEFORE the library so the dynamic linker binds to that instance.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
+        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res

@@ -110,6 +110,7 @@ struct lrcn_ctx {
     int32_t *bs_seq[2] = {nullptr, nullptr}, *bs_last = nullptr, *bs_done = nullptr, *bs_ndone = nullptr, *bs_res_tok = nullptr,
             *bs_res_len = nullptr;
     float *bs_p = nullptr, *bs_res_p = nullptr;
+    int32_t *smp_count = nullptr;   // lrcn_sample_batch_p (include/lrcn_nucleus.h), lazily: the admitted-set sizes [maxB][LRCN_BEAM_MAXLEN - 1]
     // lrcn_beam_nbest_batch (include/lrcn_nbest.h), lazily on its first call: the pool's token storage [maxB][2][LRCN_BEAM_MAXLEN] (2K rows per
     // image), the pool [maxB] {score, logp, storage row, length}, per image {live slots, pool count, done}, live cum [maxB], scores out
     int32_t *nb_store = nullptr;

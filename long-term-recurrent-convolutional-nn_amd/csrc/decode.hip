@@ -1,10 +1,11 @@
-// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nbest.h, lrcn_score.h): the batched decode's routes,
+// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_score.h): the batched decode's routes,
 // tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best beam and caption scoring.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "../../include/lrcn_nbest.h"
+#include "../../include/lrcn_nucleus.h"
 #include "../../include/lrcn_sample.h"
 #include "../../include/lrcn_score.h"
 #include "ctx.h"
@@ -647,26 +648,28 @@ int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *fe
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, N, Lh, out_tokens, out_len, out_prob);
 }
 
+}  // extern "C"
+namespace {
+
 // Sampled generation (include/lrcn_sample.h; the sample() path of lrcn.jl:613-621, 680-687): the batched decode of lrcn_beam_search_batch
 // (decode_begin / decode_step on the route decode_route picks) with R = N*S independent rows instead of N*K beams: the parent index is the
 // identity, and the per-step choice is a Gumbel-max draw per row (sample.hip) instead of top-K and a beam reorder.  Where the beam's logits
 // GEMM reduces to top-K records (decode_smax_on), top_k = 0 reduces to Gumbel records instead (GEMM_OUT_SMAX_GUMBEL) and 1 <= top_k < SMAX_KC
 // draws among the top-K records' best columns; otherwise the logits reach st_logits and one workgroup per row draws (LRCN_DECODE_SMAX=0
 // forces that form).
-int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k,
-                      uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp) {
-    DeviceGuard dg(c);
-    if (!c || !p || !feats || !out_tokens || !out_len) return LRCN_EINVAL;
-    if (N < 1 || S < 1 || (int64_t)N * S > c->maxB) FAIL(c, LRCN_EINVAL, "N*S = %d*%d must be in [1, max_B = %d]", N, S, c->maxB);
-    if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
-    if (top_k < 0 || top_k > 32 || top_k > c->V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, min(32, V=%d)]", top_k, c->V);
-    if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
+// nucleus (include/lrcn_nucleus.h; top_p < 1 or top_k > 32): the selection needs the whole row -- a record keeps SMAX_KC columns of its 128,
+// the Gumbel record one -- so the records tail is off whatever the router says (the cell epilogue and the tables stay as it picks them), the
+// logits reach st_logits and sample_nucleus_kernel selects and draws; d_count [R][nword + 1] (may be NULL) takes its admitted-set sizes.
+int sample_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k, float top_p,
+                bool nucleus, uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp, int32_t *d_count) {
     const int R = N * S, Lh = nword + 2, nrec = smax_nrec(c);
     hipStream_t st = c->stream;
-    const DecodeRoute rt = decode_route(c, R, top_k);   // smax: top_k < SMAX_KC
+    DecodeRoute rt = decode_route(c, R, nucleus ? 0 : top_k);   // smax: top_k < SMAX_KC
+    if (nucleus) rt.smax = false;
     int r = decode_begin(c, p, feats, N, S, rt);
     if (r) return r;
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
+    if (nucleus && d_count) HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(int32_t) * (size_t)R * (nword + 1), st));
     SampleState ss{c->bs_seq[0], c->bs_last, c->bs_done, c->bs_res_len, c->bs_ndone, c->bs_p, Lh, 0, nword, LRCN_EOS};
     k_sample_init(st, ss, R, LRCN_BOS);   // histories = [bos], log-likelihoods 0, next input = bos
     k_row_div(st, c->st_parent, R, 1);    // every row continues its own state: the plain step's in-place update needs no gather
@@ -688,6 +691,9 @@ int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, 
             if (!k_sample_gumbel_merge(st, c->smax_part, nrec, R, ss)) FAIL(c, LRCN_EINVAL, "sample merge: %d records per row", nrec);
         } else if (tail.kind == DecodeTail::RECORDS) {
             if (!k_sample_topk_merge(st, c->smax_part, nrec, R, top_k, temperature, seed, S, ss)) FAIL(c, LRCN_EINVAL, "sample top-k merge: top_k = %d, %d records", top_k, nrec);
+        } else if (nucleus) {
+            k_sample_nucleus(st, c->st_logits, c->ldV, R, c->V, S, current, temperature, top_k, top_p, seed, &ss,
+                             d_count ? d_count + (current - 1) : nullptr, nword + 1, nullptr, nullptr);
         } else {
             k_sample_rows(st, c->st_logits, c->ldV, R, c->V, top_k, temperature, seed, S, ss);
         }
@@ -697,6 +703,66 @@ int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, 
     }
     KCHK(c, "sample_batch");
     return decode_results_to_host(c, c->bs_seq[0], c->bs_res_len, c->bs_p, R, Lh, out_tokens, out_len, out_logp);
+}
+}  // namespace
+extern "C" {
+
+int lrcn_sample_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k,
+                      uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp) {
+    DeviceGuard dg(c);
+    if (!c || !p || !feats || !out_tokens || !out_len) return LRCN_EINVAL;
+    if (N < 1 || S < 1 || (int64_t)N * S > c->maxB) FAIL(c, LRCN_EINVAL, "N*S = %d*%d must be in [1, max_B = %d]", N, S, c->maxB);
+    if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
+    if (top_k < 0 || top_k > 32 || top_k > c->V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, min(32, V=%d)]", top_k, c->V);
+    if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
+    return sample_impl(c, p, feats, N, S, nword, temperature, top_k, 1.0f, false, seed, out_tokens, out_len, out_logp, nullptr);
+}
+
+// include/lrcn_nucleus.h.  top_p == 1 with top_k <= 32, and every greedy call (T = 0: neither cut has an effect), are lrcn_sample_batch's
+// own path; their admitted-set sizes (|A_k| at every live step) are filled in on the host from the lengths.
+int lrcn_sample_batch_p(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int S, int nword, float temperature, int top_k,
+                        float top_p, uint64_t seed, int32_t *out_tokens, int *out_len, float *out_logp, int32_t *out_count) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
+    if (N < 1 || S < 1 || (int64_t)N * S > c->maxB) FAIL(c, LRCN_EINVAL, "N*S = %d*%d must be in [1, max_B = %d]", N, S, c->maxB);
+    if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
+    if (top_k < 0 || top_k > c->V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, V=%d]", top_k, c->V);
+    if (!(top_p > 0.0f && top_p <= 1.0f)) FAIL(c, LRCN_EINVAL, "top_p=%g must be in (0, 1]", (double)top_p);
+    if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
+    const int R = N * S, nstep = nword + 1;
+    const bool greedy = temperature == 0.0f, nucleus = !greedy && (top_p < 1.0f || top_k > 32);
+    if (nucleus && out_count && !c->smp_count) DALLOC(c, c->smp_count, sizeof(int32_t) * (size_t)c->maxB * (LRCN_BEAM_MAXLEN - 1));
+    int r = sample_impl(c, p, feats, N, S, nword, temperature, greedy ? 0 : top_k, top_p, nucleus, seed, out_tokens, out_len, out_logp,
+                    nucleus && out_count ? c->smp_count : nullptr);
+    if (r || !out_count) return r;
+    if (!nucleus) {
+        const int nk = greedy || top_k == 0 ? c->V : top_k;
+        for (int row = 0; row < R; ++row)
+            for (int t = 0; t < nstep; ++t) out_count[(size_t)row * nstep + t] = t < out_len[row] - 1 ? nk : 0;
+        return LRCN_OK;
+    }
+    const size_t nb = sizeof(int32_t) * (size_t)R * nstep;
+    if ((r = pin_reserve(c, nb))) return r;
+    HIPCHK(c, hipMemcpyAsync(c->pin, c->smp_count, nb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out_count, c->pin, nb);
+    return LRCN_OK;
+}
+
+int lrcn_sample_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int S, int current, float temperature, int top_k, float top_p,
+                       uint64_t seed, int32_t *out_tok, float *out_logp, int32_t *out_count) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!logits || !out_tok) FAIL(c, LRCN_EINVAL, "null argument");
+    if (R < 1 || V < 1 || S < 1 || ld < V) FAIL(c, LRCN_EINVAL, "R=%d, V=%d, S=%d must be >= 1 and ld=%lld >= V", R, V, S, (long long)ld);
+    if (current < 0) FAIL(c, LRCN_EINVAL, "current=%d must be >= 0", current);
+    if (!std::isfinite(temperature) || temperature < 0.0f) FAIL(c, LRCN_EINVAL, "temperature=%g must be finite and >= 0", (double)temperature);
+    if (top_k < 0 || top_k > V) FAIL(c, LRCN_EINVAL, "top_k=%d must be in [0, V=%d]", top_k, V);
+    if (!(top_p > 0.0f && top_p <= 1.0f)) FAIL(c, LRCN_EINVAL, "top_p=%g must be in (0, 1]", (double)top_p);
+    k_sample_nucleus(c->stream, logits, ld, R, V, S, current, temperature, top_k, top_p, seed, nullptr, out_count, 1, out_tok, out_logp);
+    KCHK(c, "sample_logits");
+    return LRCN_OK;
 }
 
 // The n-best beam search (include/lrcn_nbest.h): the batched decode of lrcn_beam_search_batch (decode_begin / decode_step on the route

@@ -249,6 +249,11 @@ void k_sample_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V
 // from GEMM_OUT_SMAX_GUMBEL records (top_k = 0) resp. GEMM_OUT_SMAX_TOPK records (1 <= top_k < SMAX_KC); false = not applicable
 bool k_sample_gumbel_merge(hipStream_t st, const float *part, int nrec, int R, const SampleState &s);
 bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int top_k, float temp, uint64_t seed, int S, const SampleState &s);
+// the selection of include/lrcn_nucleus.h (any top_k <= V, top_p in (0, 1]) and the draw, from f32 logits [R][ld], one workgroup per row, any
+// V >= 1.  s given: step s->current of the batched decode (commits to the state, skips finished rows); s NULL: step `current` into
+// out_tok / out_logp [R] (out_logp may be NULL).  count (may be NULL): row r's admitted-set size to count[r * count_ld].
+void k_sample_nucleus(hipStream_t st, const float *logits, int64_t ld, int R, int V, int S, int current, float temp, int top_k, float top_p,
+                      uint64_t seed, const SampleState *s, int32_t *count, int64_t count_ld, int32_t *out_tok, float *out_logp);
 
 // ---- score.hip: the per-pair steps of caption scoring (lrcn_score_matrix / lrcn_score_pairs) ----
 // A2 (T) row r < R: columns [0, h) = P row row_cap[r] (P: this step's [caption][ldP] block of h1 Wproj), columns [h2_off, h2_off + zero_h2) = 0

@@ -1,10 +1,12 @@
 // sample.hip -- the per-step choice of the sampled decode (lrcn_sample_batch, include/lrcn_sample.h; the sample() path of lrcn.jl:613-621,
 // 680-687).  Every row r = i * S + s of the batched step is its own hypothesis: it draws tok = argmax_j (z_j / T + g_j) over the whole
 // vocabulary or its top_k largest logits (Gumbel-max: the draw has the distribution softmax(z / T)), appends it to its history and adds
-// log softmax(z)[tok] (temperature 1) to its log-likelihood.  g_j comes from philox.h.  Three forms, one per route of the step:
+// log softmax(z)[tok] (temperature 1) to its log-likelihood.  g_j comes from philox.h.  One form per route of the step:
 //   sample_rows_kernel          -- from the f32 logits of a plain logits GEMM (any T, top_k <= 32, f32 contexts, LRCN_DECODE_SMAX=0)
 //   sample_topk_merge_kernel    -- from the GEMM_OUT_SMAX_TOPK records (top_k < SMAX_KC): the row's top_k columns, noise for those only
 //   sample_gumbel_merge_kernel  -- from the GEMM_OUT_SMAX_GUMBEL records (top_k = 0): the records already hold each 128 columns' winner
+//   sample_nucleus_kernel       -- from f32 logits, with the exact selection of include/lrcn_nucleus.h in front of the draw: any top_k, top_p < 1
+//                                  (lrcn_sample_batch_p where lrcn_sample_batch does not serve, and every lrcn_sample_logits call)
 #include "kernels.h"
 
 #include "common.h"
@@ -250,6 +252,216 @@ __global__ __launch_bounds__(256) void sample_topk_merge_kernel(const float *par
     if (lane == 0) sample_commit(s, row, bc, bz - lse);
 }
 
+// ------------------------------------------------------------------------------------------- nucleus / any top_k (include/lrcn_nucleus.h)
+// The order-preserving key of a float: a > b <=> okey(a) > okey(b), and -0 / +0 share one key (they are equal in the rank order).
+__device__ __forceinline__ uint32_t okey(float x) {
+    const uint32_t u = __float_as_uint(x == 0.0f ? 0.0f : x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ int block_sum_int(int v, int *sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// A prefix of the rank order: column j with key k belongs to it iff k > key, or k == key and j <= col.  {0, INT_MAX} is the whole row.
+struct RankCut {
+    uint32_t key;
+    int col;
+};
+__device__ __forceinline__ bool in_cut(uint32_t k, int j, const RankCut &c) { return k > c.key || (k == c.key && j <= c.col); }
+
+// The column of the need-th (1-based) column, in column order, whose key equals `key` (there are at least `need`).  Each thread counts a
+// contiguous range of columns, a block-wide exclusive prefix count finds the range that holds it, and that range's thread walks to it.
+__device__ int tie_column(const float *z, int V, uint32_t key, int need, int *shi, int *shcol) {
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int per = (V + 255) / 256, j0 = min(V, tid * per), j1 = min(V, j0 + per);
+    int cnt = 0;
+    for (int j = j0; j < j1; ++j) cnt += okey(z[j]) == key;
+    int inc = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(inc, o);
+        if (lane >= o) inc += t;
+    }
+    __syncthreads();
+    if (lane == 63) shi[w] = inc;
+    __syncthreads();
+    int before = inc - cnt;
+    for (int q = 0; q < w; ++q) before += shi[q];
+    if (before < need && need <= before + cnt) {   // exactly one thread
+        int left = need - before, col = j0;
+        for (int j = j0; j < j1; ++j)
+            if (okey(z[j]) == key && --left == 0) { col = j; break; }
+        *shcol = col;
+    }
+    __syncthreads();
+    return *shcol;
+}
+
+struct NucleusArgs {
+    const float *logits;
+    int64_t ld;
+    int V, top_k;
+    float top_p, temp;
+    uint32_t k0, k1;
+    int S, current, stage;
+    int32_t *count;       // row r's admitted-set size goes to count[r * count_ld] (NULL: not wanted)
+    int64_t count_ld;
+    int32_t *out_tok;     // without a SampleState (s.seq == NULL): token and log-probability of row r
+    float *out_logp;
+};
+
+// One 256-thread workgroup per row, the row staged in LDS up to V = 15360 as in sample_rows_kernel.  The selection is bisection on the
+// 32-bit key, most significant bit first: the largest key K with #{key_j >= K} >= top_k is the top_k boundary value (32 block-wide counts),
+// the largest K with sum{w_j : j in A_k, key_j >= K} >= top_p * W the nucleus' (32 block-wide sums; w_j recomputed every round: there is no
+// room for a second row).  Both conditions are monotone in K -- the f32 sum too, as its order is fixed and every rounding is monotone --
+// so the bit-by-bit search finds them.  One more pass counts the columns above and at the boundary value; where only some of the tied
+// columns are needed, tie_column picks them by column.  Every sum: per-thread partials in column order, then block_reduce's tree.
+__global__ __launch_bounds__(256) void sample_nucleus_kernel(NucleusArgs a, SampleState s) {
+    extern __shared__ float srow[];
+    __shared__ float shf[4];
+    __shared__ float shv[4];
+    __shared__ int shi[4];
+    __shared__ int shcol;
+    const int r = blockIdx.x, tid = threadIdx.x, V = a.V;
+    if (s.seq && s.done[r]) return;   // block-uniform
+    const float *g = a.logits + (int64_t)r * a.ld;
+    const float *z = a.stage ? srow : g;
+    const float temp = a.temp;
+    float m = -INFINITY;
+    for (int j = tid; j < V; j += 256) {
+        const float x = g[j];
+        if (a.stage) srow[j] = x;
+        m = fmaxf(m, x);
+    }
+    m = block_reduce(m, shf, true);   // (its barriers also publish srow)
+    float se = 0.0f;
+    for (int j = tid; j < V; j += 256) se += __expf(z[j] - m);
+    se = block_reduce(se, shf, false);
+    const float lse = m + logf(se);
+
+    RankCut cut{0u, 0x7FFFFFFF};
+    int n = V;
+    if (temp > 0.0f && a.top_k > 0 && a.top_k < V) {
+        uint32_t K = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = K | (1u << bit);
+            int c = 0;
+            for (int j = tid; j < V; j += 256) c += okey(z[j]) >= cand;
+            if (block_sum_int(c, shi) >= a.top_k) K = cand;
+        }
+        int cg = 0, ce = 0;
+        for (int j = tid; j < V; j += 256) {
+            const uint32_t k = okey(z[j]);
+            cg += k > K;
+            ce += k == K;
+        }
+        cg = block_sum_int(cg, shi);
+        ce = block_sum_int(ce, shi);
+        const int need = a.top_k - cg;   // 1 <= need <= ce
+        cut.key = K;
+        cut.col = need >= ce ? 0x7FFFFFFF : tie_column(z, V, K, need, shi, &shcol);
+        n = a.top_k;
+    }
+    if (temp > 0.0f && a.top_p < 1.0f) {
+        const float invT = 1.0f / temp;
+        const RankCut ak = cut;
+        float W = 0.0f;
+        for (int j = tid; j < V; j += 256) {
+            const float x = z[j];
+            if (in_cut(okey(x), j, ak)) W += __expf((x - m) * invT);
+        }
+        W = block_reduce(W, shf, false);
+        const float target = a.top_p * W;
+        uint32_t K = 0;
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = K | (1u << bit);
+            float sw = 0.0f;
+            for (int j = tid; j < V; j += 256) {
+                const float x = z[j];
+                const uint32_t k = okey(x);
+                if (k >= cand && in_cut(k, j, ak)) sw += __expf((x - m) * invT);
+            }
+            if (block_reduce(sw, shf, false) >= target) K = cand;
+        }
+        // K is the key of a column of A_k (the row's maximum satisfies the condition with its own key, and between two present keys the
+        // sum does not change).  Above it: mass sg in cg columns; at it: ce columns of A_k, each of weight we
+        float sg = 0.0f, we = 0.0f;
+        int cg = 0, ce = 0;
+        for (int j = tid; j < V; j += 256) {
+            const float x = z[j];
+            const uint32_t k = okey(x);
+            if (!in_cut(k, j, ak)) continue;
+            const float w = __expf((x - m) * invT);
+            if (k > K) { sg += w; ++cg; }
+            else if (k == K) { we = w; ++ce; }
+        }
+        sg = block_reduce(sg, shf, false);
+        we = block_reduce(we, shf, true);
+        cg = block_sum_int(cg, shi);
+        ce = block_sum_int(ce, shi);
+        // the smallest e >= 1 with sg + e * we >= target (block-uniform arithmetic), at most the ce there are
+        int e = we > 0.0f ? (int)fminf(ceilf((target - sg) / we), (float)ce) : ce;
+        e = max(1, min(e, ce));
+        while (e > 1 && sg + (float)(e - 1) * we >= target) --e;
+        while (e < ce && sg + (float)e * we < target) ++e;
+        n = cg + e;
+        if (e < ce) {
+            cut.key = K;
+            cut.col = tie_column(z, V, K, e, shi, &shcol);
+        } else if (K != ak.key) {
+            cut.key = K;
+            cut.col = 0x7FFFFFFF;
+        }   // else: all of A_k's columns at its own boundary value -- the nucleus is A_k
+    }
+
+    const float thr = temp > 0.0f ? m - GUMBEL_PRUNE * temp : m;
+    const int current = s.seq ? s.current : a.current;
+    const uint32_t si = (uint32_t)(r % a.S), ii = (uint32_t)(r / a.S);
+    float bs = -INFINITY, bz = -INFINITY;
+    int bc = 0x7FFFFFFF;
+    for (int q = tid; 4 * q < V; q += 256) {
+        float x[4];
+        bool ok[4], any = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int j = 4 * q + k;
+            x[k] = j < V ? z[j] : -INFINITY;
+            ok[k] = j < V && x[k] >= thr && in_cut(okey(x[k]), j, cut);
+            any |= ok[k];
+        }
+        if (!any) continue;
+        if (temp > 0.0f) {
+            const Philox4 rnd = philox4x32_10((uint32_t)q, (uint32_t)current, si, ii, a.k0, a.k1);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k]) {
+                    const float sc = x[k] / temp + gumbel_of(rnd.x[k]);
+                    if (beats(sc, 4 * q + k, bs, bc)) { bs = sc; bc = 4 * q + k; bz = x[k]; }
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k] && beats(x[k], 4 * q + k, bs, bc)) { bs = x[k]; bc = 4 * q + k; bz = x[k]; }
+        }
+    }
+    float wv = bs;
+    int wc = bc;
+    block_best(wv, wc, shv, shi);
+    if (bc == wc && bs == wv) {   // exactly one thread holds the winning column
+        if (a.count) a.count[(int64_t)r * a.count_ld] = n;
+        if (s.seq) {
+            sample_commit(s, r, wc, bz - lse);
+        } else {
+            a.out_tok[r] = wc;
+            if (a.out_logp) a.out_logp[r] = bz - lse;
+        }
+    }
+}
+
 }  // namespace
 
 void k_sample_init(hipStream_t st, const SampleState &s, int R, int bos) {
@@ -278,4 +490,10 @@ bool k_sample_topk_merge(hipStream_t st, const float *part, int nrec, int R, int
     else if (nrec <= 256) hipLaunchKernelGGL(sample_topk_merge_kernel<4>, grid, dim3(256), 0, st, part, nrec, R, top_k, temp, k0, k1, S, s);
     else return false;
     return true;
+}
+void k_sample_nucleus(hipStream_t st, const float *logits, int64_t ld, int R, int V, int S, int current, float temp, int top_k, float top_p,
+                      uint64_t seed, const SampleState *s, int32_t *count, int64_t count_ld, int32_t *out_tok, float *out_logp) {
+    const int stage = V <= 15360;   // as k_sample_rows
+    const NucleusArgs a{logits, ld, V, top_k, top_p, temp, (uint32_t)seed, (uint32_t)(seed >> 32), S, current, stage, count, count_ld, out_tok, out_logp};
+    hipLaunchKernelGGL(sample_nucleus_kernel, dim3(R), dim3(256), stage ? sizeof(float) * V : 0, st, a, s ? *s : SampleState{});
 }

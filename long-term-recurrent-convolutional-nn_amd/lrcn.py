@@ -475,16 +475,42 @@ def beam_search_batch(ctx, param, feats, beam_width, nword):
     return [(list(out[i * L:i * L + n[i]]), p[i]) for i in range(N)]
 
 
-def sample_batch(ctx, param, feats, nsamples, nword, temperature=1.0, top_k=0, seed=0):
+def sample_batch(ctx, param, feats, nsamples, nword, temperature=1.0, top_k=0, seed=0, top_p=1.0, return_counts=False):
     """Sampled generation for N images in one device-resident decode (lrcn_sample_batch, include/lrcn_sample.h; the sample() path of
     lrcn.jl:613-621, 680-687): feats N x 4096 -> per image nsamples x (token ids incl. bos, log-likelihood); N * nsamples <= max_B.
-    temperature 0 = greedy (beam width 1); top_k 0 = the whole vocabulary.  The draws of image i depend only on (seed, i, sample, step)."""
+    temperature 0 = greedy (beam width 1); top_k 0 = the whole vocabulary.  The draws of image i depend only on (seed, i, sample, step).
+    top_p < 1 (nucleus sampling: the most probable words that together hold that share of the mass, after the top_k cut) or top_k > 32 go
+    through lrcn_sample_batch_p (include/lrcn_nucleus.h), as does return_counts: then the result is (that list, counts) with counts a numpy
+    [N][nsamples][nword + 1] array of the admitted set's size at every step (0 after a row's end)."""
     N, S, L = feats.shape[0], nsamples, nword + 2
     out = (C.c_int32 * (N * S * L))()
     n = (C.c_int * (N * S))()
     lp = (C.c_float * (N * S))()
-    ctx._call("lrcn_sample_batch", _p9(param), _ptr(feats), N, S, nword, float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, out, n, lp)
-    return [[(list(out[r * L:r * L + n[r]]), lp[r]) for r in range(i * S, (i + 1) * S)] for i in range(N)]
+    cnt = None
+    if top_p < 1.0 or top_k > 32 or return_counts or top_p != top_p:
+        cnt = np.zeros((N, S, nword + 1), np.int32) if return_counts else None
+        ctx._call("lrcn_sample_batch_p", _p9(param), _ptr(feats), N, S, nword, float(temperature), int(top_k), float(top_p),
+                  int(seed) & 0xFFFFFFFFFFFFFFFF, out, n, lp, cnt.ctypes.data_as(C.POINTER(C.c_int32)) if return_counts else None)
+    else:
+        ctx._call("lrcn_sample_batch", _p9(param), _ptr(feats), N, S, nword, float(temperature), int(top_k), int(seed) & 0xFFFFFFFFFFFFFFFF, out, n, lp)
+    res = [[(list(out[r * L:r * L + n[r]]), lp[r]) for r in range(i * S, (i + 1) * S)] for i in range(N)]
+    return (res, cnt) if return_counts else res
+
+
+def sample_logits(ctx, logits, S, current, temperature=1.0, top_k=0, top_p=1.0, seed=0):
+    """One step of the sampler's selection and draw on the caller's own logits (lrcn_sample_logits, include/lrcn_nucleus.h): logits numpy
+    [R][V] f32, row r = image r // S, sample r % S, step `current` of the noise counter -> numpy (tokens [R] int32, log softmax(z)[token] [R]
+    f32, admitted-set sizes [R] int32).  Independent of the context's model sizes."""
+    z = torch.from_numpy(np.ascontiguousarray(logits, dtype=np.float32)).to("cuda:%d" % ctx.device)
+    R, V = z.shape
+    tok = torch.empty(R, dtype=torch.int32, device=z.device)
+    lp = torch.empty(R, dtype=torch.float32, device=z.device)
+    cnt = torch.empty(R, dtype=torch.int32, device=z.device)
+    torch.cuda.synchronize(z.device)   # the upload has landed whichever stream the context runs on
+    ctx._call("lrcn_sample_logits", C.c_void_p(z.data_ptr()), V, R, V, int(S), int(current), float(temperature), int(top_k), float(top_p),
+              int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(tok.data_ptr()), C.c_void_p(lp.data_ptr()), C.c_void_p(cnt.data_ptr()))
+    ctx.sync()
+    return tok.cpu().numpy(), lp.cpu().numpy(), cnt.cpu().numpy()
 
 
 def beam_nbest_batch(ctx, param, feats, beam_width, nword, alpha=0.0):
@@ -520,13 +546,13 @@ def _caption(seq, index_to_word):
     return " ".join(words + ["."])
 
 
-def sample_captions(ctx, param, feats, index_to_word, nsamples, nword, temperature=1.0, top_k=0, seed=0, normalize=False):
+def sample_captions(ctx, param, feats, index_to_word, nsamples, nword, temperature=1.0, top_k=0, seed=0, normalize=False, top_p=1.0):
     """sample_batch as caption text (as generate): per image the nsamples captions, highest log-likelihood first (ties: sample order)."""
     if normalize:
         f = from_jl(feats)
         feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
     res = []
-    for samples in sample_batch(ctx, param, feats, nsamples, nword, temperature, top_k, seed):
+    for samples in sample_batch(ctx, param, feats, nsamples, nword, temperature, top_k, seed, top_p=top_p):
         order = sorted(range(len(samples)), key=lambda s: -samples[s][1])
         res.append([_caption(samples[s][0], index_to_word) for s in order])
     return res

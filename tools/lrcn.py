@@ -60,7 +60,9 @@ def build_parser():
     p.add_argument("--beam_width", type=int, default=3)
     p.add_argument("--sample", type=int, default=0, help="--generate: draw this many captions per image instead of beam search (0 = beam search)")
     p.add_argument("--temperature", type=float, default=1.0, help="--sample: softmax temperature (0 = greedy)")
-    p.add_argument("--topk", type=int, default=0, help="--sample: draw among the k most probable words only (0 = all)")
+    p.add_argument("--topk", type=int, default=0, help="--sample: draw among the k most probable words only (0 = all; any k up to the vocabulary)")
+    p.add_argument("--topp", type=float, default=1.0, help="--sample: nucleus sampling -- draw among the most probable words that together hold "
+                                                            "this share of the mass (after the --topk cut; 1.0 = off)")
     p.add_argument("--nbest", action="store_true",
                    help="--generate: n-best beam search in log space (include/lrcn_nbest.h) at --beam_width; writes <out>/nbest with "
                         "--beam_width lines per image (id, score, logp, caption), candidates / ids keep each image's best")
@@ -226,7 +228,7 @@ def main(argv=None):
                 L.vgg_calibrate(ctx, crop, mean=mean)
             f = L.convnet_u8(ctx, crop, mean=mean, normalize=True)  # input = input / sum(input)  (lrcn.jl:595-597)
             if o.sample > 0:  # the S draws, highest log-likelihood first
-                for line in L.sample_captions(ctx, param, f, idx2word, o.sample, o.generate, o.temperature, o.topk, sample_seed)[0]:
+                for line in L.sample_captions(ctx, param, f, idx2word, o.sample, o.generate, o.temperature, o.topk, sample_seed, top_p=o.topp)[0]:
                     print(line)
                 return 0
             if o.nbest:   # the n-best list, best score first: score<TAB>logp<TAB>caption
@@ -259,7 +261,7 @@ def main(argv=None):
                     # candidates / ids keep one line per image (the best log-likelihood of the S draws); `samples` holds all of them:
                     # "id<TAB>log-likelihood<TAB>caption", the image's draws in sample order.  The draws of an image depend on its index in the
                     # call, so every chunk takes its own seed
-                    drawn = L.sample_batch(ctx, param, feature_rows(table, chunk), o.sample, o.generate, o.temperature, o.topk, sample_seed + s0)
+                    drawn = L.sample_batch(ctx, param, feature_rows(table, chunk), o.sample, o.generate, o.temperature, o.topk, sample_seed + s0, top_p=o.topp)
                     for i, rows in zip(chunk, drawn):
                         best = max(range(len(rows)), key=lambda s: (rows[s][1], -s))
                         ido.write("%d\n" % i)
