@@ -17,6 +17,7 @@ NUCLEUS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nucl
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
+CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
@@ -194,6 +195,31 @@ VARLEN_SIGNATURES = {
                                       C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
 }
 
+class ClipStats(C.Structure):
+    """lrcn_clip_stats_t (include/lrcn_clip.h)."""
+    _fields_ = [("last_norm", C.c_double), ("last_scale", C.c_float), ("last_skipped", C.c_int32), ("steps", C.c_int64),
+                ("clipped", C.c_int64), ("skipped", C.c_int64)]
+
+
+# name -> (restype, argtypes); exactly the symbols include/lrcn_clip.h declares (bound by lib() as well)
+CLIP_SIGNATURES = {
+    "lrcn_grad_sumsq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "lrcn_grad_sumsq_model": (C.c_int, [C.c_void_p, P9, C.c_int, C.c_void_p]),
+    "lrcn_clip_slots": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lrcn_clip_set": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "lrcn_adam_update_clipped": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float]),
+    "lrcn_adam_update_group_clipped": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                 C.c_void_p]),
+    "lrcn_adam_update_flat_clipped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float,
+                                                C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    "lrcn_train_step_clip": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Dropout),
+                                       C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
+    "lrcn_train_step_var_clip": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                           C.c_int64, C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                           C.POINTER(C.c_double)]),
+    "lrcn_clip_stats": (C.c_int, [C.c_void_p, C.POINTER(ClipStats)]),
+}
+
 # name -> (restype, argtypes); exactly the symbols include/lrcn_gemm_debug.h declares (bound by lib() as well)
 GEMM_DEBUG_SIGNATURES = {
     "lrcn_debug_gemm": (C.c_int, [C.c_void_p, C.POINTER(GemmDebug)]),
@@ -203,7 +229,7 @@ GEMM_DEBUG_SIGNATURES = {
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, GEMM_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -224,7 +250,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
+                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

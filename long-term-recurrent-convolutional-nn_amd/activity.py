@@ -153,24 +153,45 @@ class ActivityModel:
         self._call("lrcn_act_predict", self._p4(params or self.params), _ptr(feats), plen, T, B, _ptr(cp), _ptr(fp) if fp is not None else None)
         return (cp, fp) if frame_probs else cp
 
-    def adam_step(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8):
-        """update! with one Adam per tensor (lrcn_adam_update_flat, the caption path's arithmetic) from self.grads.  That entry point takes
-        an lrcn_ctx: a minimal one (no VGG, a 8-unit caption shape) is made on first use and only ever runs this update."""
+    def _optimizer_ctx(self):
         if self._opt_ctx is None:
             from .lrcn import Context
             self._opt_ctx = Context(8, 8, 8, 8, max_B=1, max_T=1, device=self.device)
+        return self._opt_ctx
+
+    def adam_step(self, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, gclip=0.0):
+        """update! with one Adam per tensor (lrcn_adam_update_flat, the caption path's arithmetic) from self.grads.  That entry point takes
+        an lrcn_ctx: a minimal one (no VGG, a 8-unit caption shape) is made on first use and only ever runs this update.
+        gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h): tensor k's sum of squares into slot k,
+        lrcn_clip_set, then the clipped flat updates; self.grads keeps the unclipped gradient.  A model of more than nine tensors has no
+        slot for its tenth: LrcnError."""
+        ctx = self._optimizer_ctx()
+        gclip = float(gclip or 0.0)
         self.step += 1
         L = _lib.lib()
+        st = C.c_void_p(self._stream.cuda_stream)
+        if gclip > 0:
+            if len(self.grads) > 9:
+                raise LrcnError("gradient-norm clipping has 9 slots, the model has %d tensors" % len(self.grads))
+            for k, g in enumerate(self.grads):
+                ctx._call("lrcn_grad_sumsq", C.c_void_p(g.data_ptr()), g.numel(), k, st)
+            ctx._call("lrcn_clip_set", len(self.grads), gclip, st)
+        update = L.lrcn_adam_update_flat_clipped if gclip > 0 else L.lrcn_adam_update_flat
         for p, g, m, v in zip(self.params, self.grads, self.mom, self.var):
-            rc = L.lrcn_adam_update_flat(self._opt_ctx._h, C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()),
-                                         C.c_void_p(v.data_ptr()), p.numel(), self.step, lr, beta1, beta2, eps,
-                                         C.c_void_p(self._stream.cuda_stream))
+            rc = update(ctx._h, C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()),
+                        C.c_void_p(v.data_ptr()), p.numel(), self.step, lr, beta1, beta2, eps, st)
             if rc != 0:
                 raise LrcnError("lrcn_adam_update_flat error %d" % rc)
 
-    def train_step(self, feats, labels, lens=None, T=None, lr=1e-3):
+    def clip_stats(self):
+        """The counters of adam_step(gclip > 0) (lrcn_clip_stats; waits for the model's stream)."""
+        from . import lrcn
+        self._stream.synchronize()
+        return lrcn.clip_stats(self._optimizer_ctx())
+
+    def train_step(self, feats, labels, lens=None, T=None, lr=1e-3, gclip=0.0):
         loss = self.loss_grad(feats, labels, lens, T)
-        self.adam_step(lr)
+        self.adam_step(lr, gclip=gclip)
         return loss
 
     def predict_videos(self, video_feats, T=None, stride=8, batch=None):

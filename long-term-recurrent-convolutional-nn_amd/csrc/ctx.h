@@ -59,6 +59,9 @@ struct lrcn_ctx {
     unsigned fused_groups = 0;              // gradient groups whose fused Adam has been issued in the current step (bit per group)
     int fused_step = 0;                     // the `step` those bits belong to: a call with another step starts a new mask
     unsigned refresh_groups = 0;            // lrcn_refresh_shadows_group: groups whose shadows of the NEXT step have been issued
+    // gradient-norm clipping (include/lrcn_clip.h), lazily: the control block and k_sumsq's partial sums [9][kSumsqParts], one slice per slot
+    struct ClipCtl *clip_ctl = nullptr;
+    double *clip_parts = nullptr;
     bool shadow_valid = false;              // the current set holds the shadows (direct AND transposed) of the parameters at shadow_p
     const float *shadow_p[9] = {};
     float *dWe_rm = nullptr;                // [V][ldE] f32, all zero between calls: row-major staging of the embedding gradient

@@ -126,6 +126,7 @@ void k_dx2_mask_reduce(hipStream_t st, int dtype, void *dx2, int64_t ld, int S, 
 // (dA[r][c] | dB[r][c - cs]) and transposed copies (tA[c][r] | tB[c - cs][r]) in T; NULL destinations are skipped.  Padding
 // columns of the destinations are left as they are (zero since allocation).
 #define PREP_MAX 12
+struct ClipCtl;  // below: the control block of gradient-norm clipping
 struct PrepDesc {
     const float *src;
     // k_adam_shadows only: the tensor's gradient and Adam moments (memory images like src, which is then also written)
@@ -150,11 +151,14 @@ struct PrepPlan {
     int total;                      // tiles of all descriptors (set by the launchers)
     int grid_cap;                   // always 0 (a capped update grid lost its measurement, DESIGN_HISTORY.md); kept for the kernels' argument layout
     float lr, b1, b2, eps, c1, c2;  // k_adam_shadows
+    const ClipCtl *clip;            // k_adam_shadows: non-NULL = the clipped form (reads scale / skip; see ClipCtl)
 };
 void k_prepare_weights(hipStream_t st, int dtype, PrepPlan &plan);
 // update! (lrcn.jl:394) and the NEXT step's shadow weights in one pass over the parameters: every descriptor's src / g / m / v are
 // updated exactly as k_adam does (same arithmetic, element by element) and the new values are written to the descriptor's shadow
 // destinations.  Descriptors without destinations (the biases: R = 1) are plain Adam.
+// plan.clip != NULL: the clipped form -- every gradient element is multiplied by clip->scale first (its own float multiply); with
+// clip->skip set w, m and v are not written, and the shadows are still made, from the unchanged parameters.
 void k_adam_shadows(hipStream_t st, int dtype, PrepPlan &plan, int step, float lr, float b1, float b2, float eps);
 
 struct AdamTensors {
@@ -165,7 +169,34 @@ struct AdamTensors {
     int64_t n[9];
 };
 // update! with Adam (lrcn.jl:394; Knet defaults), all 9 tensors in one launch.
-void k_adam(hipStream_t st, const AdamTensors &t, int step, float lr, float b1, float b2, float eps);
+// clip != NULL: the clipped form (g[i] * clip->scale as its own float multiply; nothing is written when clip->skip is set).
+void k_adam(hipStream_t st, const AdamTensors &t, int step, float lr, float b1, float b2, float eps, const ClipCtl *clip = nullptr);
+
+// ---- global gradient-norm clipping (include/lrcn_clip.h) ----
+// The context's control block in device memory.  slot[k]: sum of squares of gradient tensor k (or of a rank's slice of group k);
+// k_clip_set turns the first n_slots of them into norm / scale / skip and bumps the counters.
+struct ClipCtl {
+    double slot[9];
+    double norm;
+    float scale;
+    int skip;
+    long long steps, clipped, skipped;
+};
+constexpr int kSumsqParts = 512;  // workgroups (= partial sums) per run of k_sumsq
+struct SumsqArgs {
+    const float *g[9];
+    int64_t n[9];
+    int slot[9];
+    int count;   // runs in this launch (<= 9), each into its own slot
+};
+// ctl->slot[a.slot[e]] = sum_i (double)g[e][i]^2 for every run e < a.count, in two stages: kSumsqParts workgroups per run own one fixed
+// contiguous chunk each (thread t of a workgroup adds the 4-element groups t, t + 256, ... of the chunk in that order, then a fixed
+// tree), then one workgroup per run adds the partials in index order.  No atomics: the result is a function of the data and n alone.
+// parts: [9][kSumsqParts] doubles, slice a.slot[e] is run e's.
+void k_sumsq(hipStream_t st, const SumsqArgs &a, double *parts, ClipCtl *ctl);
+// norm = sqrt(slot[0] + ... + slot[n_slots - 1]) (slot order, double); skip = !isfinite(norm);
+// scale = (!skip && norm > max_norm) ? (float)(max_norm / norm) : 1; steps += 1, clipped += scale applies, skipped += skip.
+void k_clip_set(hipStream_t st, ClipCtl *ctl, int n_slots, float max_norm);
 // out[i] = a[i] * b[i]
 void k_mul_f32(hipStream_t st, const float *a, const float *b, int64_t n, float *out);
 

@@ -17,6 +17,7 @@
 
 #include "ctx.h"
 #include "../../include/lrcn_varlen.h"
+#include "../../include/lrcn_clip.h"
 
 static thread_local std::string g_create_err;
 using namespace lrcn_impl;
@@ -164,7 +165,7 @@ const int kGradGroup[LRCN_GRAD_GROUPS][2] = {{7, 8}, {2, 3}, {4, 5}, {0, 1}, {6,
 // update! (lrcn.jl:394) of the tensors of gradient group `group` (-1: all nine) fused with the NEXT step's shadow pass (LRCN_OPT_FUSED_UPDATE):
 // the kernel writes the not-current shadow set; the caller swaps the sets once every group has been issued.
 int adam_fused(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group, int step, float lr,
-               float b1, float b2, float eps, hipStream_t st) {
+               float b1, float b2, float eps, hipStream_t st, const ClipCtl *clip = nullptr) {
     int r = ensure_alt_shadows(c);
     if (r) return r;
     int64_t sz[9];
@@ -188,6 +189,7 @@ int adam_fused(lrcn_ctx *c, float *const p[9], const float *const g[9], float *c
     }
     // (a group's update on its own stream runs beside the rest of the backward pass on an UNCAPPED grid: the groups' updates are on the step's
     // critical path, not beside it)
+    plan.clip = clip;  // non-NULL: the clipped form; a skipped step still writes this set, from the unchanged parameters
     k_adam_shadows(st, c->dt, plan, step, lr, b1, b2, eps);
     KCHK(c, "adam (fused with the shadow pass)");
     return LRCN_OK;
@@ -1129,10 +1131,41 @@ int lrcn_forward_logits(lrcn_ctx *c, const float *const p[9], const float *feats
     return loss_impl(c, p, feats, tokens, T, B, B, nullptr, nullptr, logits_out);
 }
 
+// ---- include/lrcn_clip.h: the control block ----
+namespace {
+int ensure_clip(lrcn_ctx *c) {
+    if (c->clip_ctl) return LRCN_OK;
+    double *parts = nullptr;
+    ClipCtl *ctl = nullptr;
+    DALLOC(c, parts, sizeof(double) * LRCN_CLIP_SLOTS * kSumsqParts);
+    DALLOC(c, ctl, sizeof(ClipCtl));
+    ClipCtl init{};
+    init.scale = 1.0f;  // an update that reads the block before any lrcn_clip_set is the plain update
+    HIPCHK(c, hipMemcpy(ctl, &init, sizeof(init), hipMemcpyHostToDevice));
+    c->clip_parts = parts;
+    c->clip_ctl = ctl;
+    return LRCN_OK;
+}
+inline hipStream_t stream_or_ctx(lrcn_ctx *c, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream; }
+
+// the bodies of lrcn_adam_update / _group / _flat and of their clipped namesakes (clip: NULL or the context's control block)
+int adam_update_impl(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int step, float lr,
+                     float b1, float b2, float eps, const ClipCtl *clip);
+int adam_update_group_impl(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group,
+                           int step, float lr, float b1, float b2, float eps, void *stream, const ClipCtl *clip);
+int adam_update_flat_impl(lrcn_ctx *c, float *w, const float *g, float *m, float *v, int64_t n, int step, float lr, float b1, float b2,
+                          float eps, void *stream, const ClipCtl *clip);
+}  // namespace
+
 int lrcn_adam_update(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int step,
                      float lr, float b1, float b2, float eps) {
     DeviceGuard dg(c);
     if (!c || !p || !g || !m || !v || step < 1) return LRCN_EINVAL;
+    return adam_update_impl(c, p, g, m, v, step, lr, b1, b2, eps, nullptr);
+}
+namespace {
+int adam_update_impl(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int step, float lr,
+                     float b1, float b2, float eps, const ClipCtl *clip) {
     c->fused_groups = 0;  // the whole-model update supersedes any per-group sequence left unfinished (an error between two groups)
     int64_t nparam = 0;
     {
@@ -1143,7 +1176,7 @@ int lrcn_adam_update(lrcn_ctx *c, float *const p[9], const float *const g[9], fl
     SegScope seg(c, LRCN_SEG_UPDATE, c->stream, 28.0 * (double)nparam);  // w, m, v read + written, g read: 28 B per parameter
     if (c->opt_fused) {  // LRCN_OPT_FUSED_UPDATE: the same update, and the next step's shadow weights in the same pass
         c->shadow_valid = false;
-        int r = adam_fused(c, p, g, m, v, -1, step, lr, b1, b2, eps, c->stream);
+        int r = adam_fused(c, p, g, m, v, -1, step, lr, b1, b2, eps, c->stream, clip);
         if (r) return r;
         fused_update_done(c, p);
         return LRCN_OK;
@@ -1159,16 +1192,22 @@ int lrcn_adam_update(lrcn_ctx *c, float *const p[9], const float *const g[9], fl
         t.v[k] = v[k];
         t.n[k] = sz[k];
     }
-    k_adam(c->stream, t, step, lr, b1, b2, eps);
+    k_adam(c->stream, t, step, lr, b1, b2, eps, clip);
     KCHK(c, "adam");
     return LRCN_OK;
 }
+}  // namespace
 
 int lrcn_adam_update_group(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group,
                            int step, float lr, float b1, float b2, float eps, void *stream) {
     DeviceGuard dg(c);
     if (!c || !p || !g || !m || !v || step < 1) return LRCN_EINVAL;
     if (group < 0 || group >= LRCN_GRAD_GROUPS) FAIL(c, LRCN_EINVAL, "group=%d outside [0,%d)", group, LRCN_GRAD_GROUPS);
+    return adam_update_group_impl(c, p, g, m, v, group, step, lr, b1, b2, eps, stream, nullptr);
+}
+namespace {
+int adam_update_group_impl(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group,
+                           int step, float lr, float b1, float b2, float eps, void *stream, const ClipCtl *clip) {
     int64_t szg[9];
     ctx_sizes(c, szg);
     SegScope seg(c, LRCN_SEG_UPDATE, stream ? reinterpret_cast<hipStream_t>(stream) : c->stream,
@@ -1181,7 +1220,7 @@ int lrcn_adam_update_group(lrcn_ctx *c, float *const p[9], const float *const g[
             c->fused_step = step;
         }
         c->shadow_valid = false;
-        int r = adam_fused(c, p, g, m, v, group, step, lr, b1, b2, eps, stream ? reinterpret_cast<hipStream_t>(stream) : c->stream);
+        int r = adam_fused(c, p, g, m, v, group, step, lr, b1, b2, eps, stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, clip);
         if (r) {
             c->fused_groups = 0;
             return r;
@@ -1205,10 +1244,11 @@ int lrcn_adam_update_group(lrcn_ctx *c, float *const p[9], const float *const g[
         t.v[k] = v[k];
         t.n[k] = in ? sz[k] : 0;
     }
-    k_adam(stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, t, step, lr, b1, b2, eps);
+    k_adam(stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, t, step, lr, b1, b2, eps, clip);
     KCHK(c, "adam (group)");
     return LRCN_OK;
 }
+}  // namespace
 
 int lrcn_refresh_shadows_group(lrcn_ctx *c, const float *const p[9], int group, void *stream) {
     DeviceGuard dg(c);
@@ -1241,14 +1281,20 @@ int lrcn_adam_update_flat(lrcn_ctx *c, float *w, const float *g, float *m, float
     if (!c || step < 1 || n < 0) return LRCN_EINVAL;
     if (n == 0) return LRCN_OK;
     if (!w || !g || !m || !v) return LRCN_EINVAL;
+    return adam_update_flat_impl(c, w, g, m, v, n, step, lr, b1, b2, eps, stream, nullptr);
+}
+namespace {
+int adam_update_flat_impl(lrcn_ctx *c, float *w, const float *g, float *m, float *v, int64_t n, int step, float lr, float b1, float b2,
+                          float eps, void *stream, const ClipCtl *clip) {
     c->shadow_valid = false;  // some parameter changed: the next call makes its shadow weights afresh
     SegScope seg(c, LRCN_SEG_UPDATE, stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, 28.0 * (double)n);
     AdamTensors t{};
     t.w[0] = w; t.g[0] = g; t.m[0] = m; t.v[0] = v; t.n[0] = n;
-    k_adam(stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, t, step, lr, b1, b2, eps);
+    k_adam(stream ? reinterpret_cast<hipStream_t>(stream) : c->stream, t, step, lr, b1, b2, eps, clip);
     KCHK(c, "adam (flat)");
     return LRCN_OK;
 }
+}  // namespace
 
 int lrcn_train_step(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                     const int32_t *tokens, int T, int B, int norm_B, const lrcn_dropout *drop, int step, float lr, float b1,
@@ -1272,6 +1318,145 @@ int lrcn_train_step_var(lrcn_ctx *c, float *const p[9], float *const g[9], float
     r = lrcn_adam_update(c, p, g, m, v, step, lr, b1, b2, eps);
     if (r) return r;
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
+// ---- include/lrcn_clip.h: global gradient-norm clipping ----
+int lrcn_grad_sumsq(lrcn_ctx *c, const float *g, int64_t n, int slot, void *stream) {
+    DeviceGuard dg(c);
+    if (!c || n < 0 || (!g && n > 0)) return LRCN_EINVAL;
+    if (slot < 0 || slot >= LRCN_CLIP_SLOTS) FAIL(c, LRCN_EINVAL, "slot=%d outside [0,%d)", slot, LRCN_CLIP_SLOTS);
+    int r = ensure_clip(c);
+    if (r) return r;
+    SumsqArgs a{};
+    a.g[0] = g; a.n[0] = n; a.slot[0] = slot; a.count = 1;
+    k_sumsq(stream_or_ctx(c, stream), a, c->clip_parts, c->clip_ctl);
+    KCHK(c, "sumsq");
+    return LRCN_OK;
+}
+
+int lrcn_grad_sumsq_model(lrcn_ctx *c, const float *const g[9], int group, void *stream) {
+    DeviceGuard dg(c);
+    if (!c || !g) return LRCN_EINVAL;
+    if (group < -1 || group >= LRCN_GRAD_GROUPS) FAIL(c, LRCN_EINVAL, "group=%d outside [-1,%d)", group, LRCN_GRAD_GROUPS);
+    int64_t sz[9];
+    ctx_sizes(c, sz);
+    SumsqArgs a{};
+    for (int k = 0; k < 9; ++k) {
+        if (group >= 0 && k != kGradGroup[group][0] && k != kGradGroup[group][1]) continue;
+        if (sz[k] > 0 && !g[k]) return LRCN_EINVAL;
+        a.g[a.count] = g[k]; a.n[a.count] = sz[k]; a.slot[a.count] = k;
+        ++a.count;
+    }
+    int r = ensure_clip(c);
+    if (r) return r;
+    k_sumsq(stream_or_ctx(c, stream), a, c->clip_parts, c->clip_ctl);
+    KCHK(c, "sumsq (model)");
+    return LRCN_OK;
+}
+
+int lrcn_clip_slots(lrcn_ctx *c, double **dev_ptr) {
+    DeviceGuard dg(c);
+    if (!c || !dev_ptr) return LRCN_EINVAL;
+    int r = ensure_clip(c);
+    if (r) return r;
+    *dev_ptr = c->clip_ctl->slot;  // (address arithmetic only: the block is never read from the host here)
+    return LRCN_OK;
+}
+
+int lrcn_clip_set(lrcn_ctx *c, int n_slots, float max_norm, void *stream) {
+    DeviceGuard dg(c);
+    if (!c) return LRCN_EINVAL;
+    if (n_slots < 1 || n_slots > LRCN_CLIP_SLOTS) FAIL(c, LRCN_EINVAL, "n_slots=%d outside [1,%d]", n_slots, LRCN_CLIP_SLOTS);
+    if (!(max_norm > 0.0f)) FAIL(c, LRCN_EINVAL, "max_norm=%g is not > 0", (double)max_norm);
+    int r = ensure_clip(c);
+    if (r) return r;
+    k_clip_set(stream_or_ctx(c, stream), c->clip_ctl, n_slots, max_norm);
+    KCHK(c, "clip_set");
+    return LRCN_OK;
+}
+
+int lrcn_adam_update_clipped(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int step,
+                             float lr, float b1, float b2, float eps) {
+    DeviceGuard dg(c);
+    if (!c || !p || !g || !m || !v || step < 1) return LRCN_EINVAL;
+    int r = ensure_clip(c);
+    if (r) return r;
+    return adam_update_impl(c, p, g, m, v, step, lr, b1, b2, eps, c->clip_ctl);
+}
+
+int lrcn_adam_update_group_clipped(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group,
+                                   int step, float lr, float b1, float b2, float eps, void *stream) {
+    DeviceGuard dg(c);
+    if (!c || !p || !g || !m || !v || step < 1) return LRCN_EINVAL;
+    if (group < 0 || group >= LRCN_GRAD_GROUPS) FAIL(c, LRCN_EINVAL, "group=%d outside [0,%d)", group, LRCN_GRAD_GROUPS);
+    int r = ensure_clip(c);
+    if (r) return r;
+    return adam_update_group_impl(c, p, g, m, v, group, step, lr, b1, b2, eps, stream, c->clip_ctl);
+}
+
+int lrcn_adam_update_flat_clipped(lrcn_ctx *c, float *w, const float *g, float *m, float *v, int64_t n, int step, float lr, float b1,
+                                  float b2, float eps, void *stream) {
+    DeviceGuard dg(c);
+    if (!c || step < 1 || n < 0) return LRCN_EINVAL;
+    if (n == 0) return LRCN_OK;
+    if (!w || !g || !m || !v) return LRCN_EINVAL;
+    int r = ensure_clip(c);
+    if (r) return r;
+    return adam_update_flat_impl(c, w, g, m, v, n, step, lr, b1, b2, eps, stream, c->clip_ctl);
+}
+
+namespace {
+// the nine sums of squares, norm / scale / skip and the clipped update of one training step, all on the context's stream
+int clip_and_update(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], int step, float lr, float b1,
+                    float b2, float eps, float max_norm) {
+    int r = lrcn_grad_sumsq_model(c, g, -1, nullptr);
+    if (r || (r = lrcn_clip_set(c, LRCN_CLIP_SLOTS, max_norm, nullptr))) return r;
+    return lrcn_adam_update_clipped(c, p, g, m, v, step, lr, b1, b2, eps);
+}
+}  // namespace
+
+int lrcn_train_step_clip(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                         const int32_t *tokens, int T, int B, int norm_B, const lrcn_dropout *drop, int step, float lr, float b1, float b2,
+                         float eps, float max_norm, double *loss_host) {
+    DeviceGuard dg(c);
+    if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
+    if (std::isnan(max_norm)) FAIL(c, LRCN_EINVAL, "max_norm is NaN");
+    if (!(max_norm > 0.0f)) return lrcn_train_step(c, p, g, m, v, feats, tokens, T, B, norm_B, drop, step, lr, b1, b2, eps, loss_host);
+    if (step < 1) return LRCN_EINVAL;
+    int r = lrcn_loss_grad(c, p, feats, tokens, T, B, norm_B, drop, g, nullptr);
+    if (r || (r = clip_and_update(c, p, g, m, v, step, lr, b1, b2, eps, max_norm))) return r;
+    return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
+int lrcn_train_step_var_clip(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                             const int32_t *tokens, const int32_t *lens, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop,
+                             int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
+    DeviceGuard dg(c);
+    if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
+    if (std::isnan(max_norm)) FAIL(c, LRCN_EINVAL, "max_norm is NaN");
+    if (!(max_norm > 0.0f))
+        return lrcn_train_step_var(c, p, g, m, v, feats, tokens, lens, T, B, norm_tokens, drop, step, lr, b1, b2, eps, loss_host);
+    if (step < 1) return LRCN_EINVAL;
+    int r = lrcn_loss_grad_var(c, p, feats, tokens, lens, T, B, norm_tokens, drop, g, nullptr);
+    if (r || (r = clip_and_update(c, p, g, m, v, step, lr, b1, b2, eps, max_norm))) return r;
+    return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
+}
+
+int lrcn_clip_stats(lrcn_ctx *c, lrcn_clip_stats_t *out) {
+    DeviceGuard dg(c);
+    if (!c || !out) return LRCN_EINVAL;
+    int r = ensure_clip(c);
+    if (r) return r;
+    ClipCtl h{};
+    HIPCHK(c, hipMemcpyAsync(&h, c->clip_ctl, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out->last_norm = h.norm;
+    out->last_scale = h.scale;
+    out->last_skipped = h.skip;
+    out->steps = h.steps;
+    out->clipped = h.clipped;
+    out->skipped = h.skipped;
+    return LRCN_OK;
 }
 
 int lrcn_comm_unique_id(void *id_out) {

@@ -1,5 +1,6 @@
 // train_kernels.hip -- the kernels only the training step (lrcn_api.hip) launches: token rows, the embedding gradient (scatter, sparse
-// export, ordered sums), dropout mask + reduce of dX2, the shadow-weight pass with and without Adam, multi-tensor Adam.
+// export, ordered sums), dropout mask + reduce of dX2, the shadow-weight pass with and without Adam, multi-tensor Adam, and the gradient-norm
+// clipping of include/lrcn_clip.h (sum of squares, control block, the clipped forms of both Adam kernels).
 #include "kernel_util.h"
 
 namespace {
@@ -220,9 +221,16 @@ __global__ void dx2_mask_reduce_kernel(T *dx2, int64_t ld, int S, int B, int nl,
 // All shadow weights of one model in ONE launch (was 8 cast_rows + 9 transpose launches per step): for every 32 x 32 tile of
 // a parameter's memory image [R][C] (f32) write the direct copy split at column `cs` (dA[r][c], dB[r][c - cs]) and / or the
 // transposed copy (tA[c][r], tB[c - cs][r]) in T.  Padding columns of the destinations are never touched (zero since allocation).
-template <typename T, bool ADAM = false> __global__ __launch_bounds__(256) void prepare_weights_kernel(const PrepPlan plan) {
+template <typename T, bool ADAM = false, bool CLIP = false> __global__ __launch_bounds__(256) void prepare_weights_kernel(const PrepPlan plan) {
     // 64 x 64 tiles, 16 bytes in / 8 bytes out per thread access (bf16); generic element-wise path for f32 shadows and edges
     __shared__ float tile[64][65];
+    // CLIP: a skipped step (non-finite norm) leaves w, m and v alone and STILL writes the shadows below, from the unchanged parameters
+    float clip_scale = 1.0f;
+    bool clip_skip = false;
+    if constexpr (CLIP) {
+        clip_scale = plan.clip->scale;
+        clip_skip = plan.clip->skip != 0;
+    }
     // plan.total tiles walked by gridDim.x workgroups (the launchers start one workgroup per tile)
     for (int bid = blockIdx.x; bid < plan.total; bid += gridDim.x) {
     if (bid != (int)blockIdx.x) __syncthreads();  // the previous tile's transposed stores have read `tile`
@@ -251,7 +259,7 @@ template <typename T, bool ADAM = false> __global__ __launch_bounds__(256) void 
                 for (int k = 0; k < 4; ++k)
                     if (c + k < P.C) v[k] = P.src[(int64_t)r * P.C + c + k];
             }
-            if constexpr (ADAM) {  // update! on the loaded values (the arithmetic of adam_kernel), written back before the shadows are made
+            if (ADAM && !(CLIP && clip_skip)) {  // update! on the loaded values (the arithmetic of adam_kernel), written back before the shadows are made
                 const int64_t o = (int64_t)r * P.C + c;
                 float gg[4] = {0.f, 0.f, 0.f, 0.f}, mm[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
                 const bool v4 = vec && c + 3 < P.C;
@@ -265,6 +273,10 @@ template <typename T, bool ADAM = false> __global__ __launch_bounds__(256) void 
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
                         if (c + k < P.C) { gg[k] = P.g[o + k]; mm[k] = P.m[o + k]; vv[k] = P.v[o + k]; }
+                }
+                if constexpr (CLIP) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) gg[k] = __fmul_rn(gg[k], clip_scale);
                 }
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
@@ -339,13 +351,19 @@ template <typename T, bool ADAM = false> __global__ __launch_bounds__(256) void 
     }
 }
 
-__global__ void adam_kernel(AdamTensors t, float lr, float b1, float b2, float eps, float c1, float c2) {
+template <bool CLIP>
+__global__ void adam_kernel(AdamTensors t, float lr, float b1, float b2, float eps, float c1, float c2, const ClipCtl *clip) {
+    float scale = 1.0f;
+    if constexpr (CLIP) {
+        if (clip->skip) return;  // a non-finite norm: w, m and v stay as they are
+        scale = clip->scale;
+    }
     const int k = blockIdx.y;
     const int64_t n = t.n[k];
     float *w = t.w[k], *m = t.m[k], *v = t.v[k];
     const float *g = t.g[k];
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
+        const float gi = CLIP ? __fmul_rn(g[i], scale) : g[i];
         const float mi = b1 * m[i] + (1.0f - b1) * gi;
         const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
         m[i] = mi;
@@ -356,6 +374,74 @@ __global__ void adam_kernel(AdamTensors t, float lr, float b1, float b2, float e
 
 __global__ void mul_f32_kernel(const float *a, const float *b, int64_t n, float *out) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] = a[i] * b[i];
+}
+
+// Stage 1 of k_sumsq: workgroup blockIdx.x of run blockIdx.y owns the 4-element groups [x cg, (x + 1) cg) of the run, cg = ceil(groups /
+// kSumsqParts).  A float's square is exact in double, so only the additions round.
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const SumsqArgs a, double *parts) {
+    __shared__ double red[256];
+    const int e = blockIdx.y, tid = threadIdx.x;
+    const float *__restrict__ g = a.g[e];
+    const int64_t n = a.n[e];
+    const int64_t groups = (n + 3) / 4, full = n / 4;
+    const int64_t cg = (groups + kSumsqParts - 1) / kSumsqParts;
+    const int64_t q0 = (int64_t)blockIdx.x * cg;
+    const int64_t q1 = q0 + cg < groups ? q0 + cg : groups, qf = q1 < full ? q1 : full;
+    const bool al = (reinterpret_cast<uintptr_t>(g) % 16) == 0;
+    double acc = 0.0;
+    if (al) {
+#pragma unroll 8
+        for (int64_t q = q0 + tid; q < qf; q += 256) {
+            const float4 x = *reinterpret_cast<const float4 *>(g + 4 * q);
+            const double d0 = x.x, d1 = x.y, d2 = x.z, d3 = x.w;
+            acc += d0 * d0; acc += d1 * d1; acc += d2 * d2; acc += d3 * d3;
+        }
+    } else {  // the same groups, the same order, element loads
+#pragma unroll 4
+        for (int64_t q = q0 + tid; q < qf; q += 256) {
+            const double d0 = g[4 * q], d1 = g[4 * q + 1], d2 = g[4 * q + 2], d3 = g[4 * q + 3];
+            acc += d0 * d0; acc += d1 * d1; acc += d2 * d2; acc += d3 * d3;
+        }
+    }
+    if (full < groups && full >= q0 && full < q1 && (full - q0) % 256 == tid) {  // the run's last, partial group: its owner's last one
+        for (int64_t i = 4 * full; i < n; ++i) {
+            const double d = g[i];
+            acc += d * d;
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) parts[(int64_t)a.slot[e] * kSumsqParts + blockIdx.x] = red[0];
+}
+// Stage 2: one workgroup per run, one lane adds the run's partials in index order.
+__global__ __launch_bounds__(256) void sumsq_final_kernel(const SumsqArgs a, const double *parts, ClipCtl *ctl) {
+    __shared__ double red[kSumsqParts];
+    const int slot = a.slot[blockIdx.x];
+    for (int i = threadIdx.x; i < kSumsqParts; i += 256) red[i] = parts[(int64_t)slot * kSumsqParts + i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < kSumsqParts; ++i) s += red[i];
+        ctl->slot[slot] = s;
+    }
+}
+__global__ void clip_set_kernel(ClipCtl *ctl, int n_slots, float max_norm) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double s = 0.0;
+    for (int k = 0; k < n_slots; ++k) s += ctl->slot[k];
+    const double norm = sqrt(s);
+    const int skip = isfinite(norm) ? 0 : 1;
+    const bool clip = !skip && norm > (double)max_norm;
+    ctl->norm = norm;
+    ctl->skip = skip;
+    ctl->scale = clip ? (float)((double)max_norm / norm) : 1.0f;
+    ctl->steps += 1;
+    ctl->clipped += clip ? 1 : 0;
+    ctl->skipped += skip;
 }
 
 }  // namespace
@@ -403,11 +489,26 @@ void k_adam_shadows(hipStream_t st, int dtype, PrepPlan &plan, int step, float l
     plan.c1 = (float)(1.0 - pow((double)b1, (double)step));
     plan.c2 = (float)(1.0 - pow((double)b2, (double)step));
     plan.total = tiles;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((prepare_weights_kernel<T, true>), dim3(tiles), dim3(256), 0, st, plan));
+    if (plan.clip) {
+        DISPATCH_T(dtype, hipLaunchKernelGGL((prepare_weights_kernel<T, true, true>), dim3(tiles), dim3(256), 0, st, plan));
+    } else {
+        DISPATCH_T(dtype, hipLaunchKernelGGL((prepare_weights_kernel<T, true>), dim3(tiles), dim3(256), 0, st, plan));
+    }
 }
-void k_adam(hipStream_t st, const AdamTensors &t, int step, float lr, float b1, float b2, float eps) {
+void k_adam(hipStream_t st, const AdamTensors &t, int step, float lr, float b1, float b2, float eps, const ClipCtl *clip) {
     const float c1 = (float)(1.0 - pow((double)b1, (double)step)), c2 = (float)(1.0 - pow((double)b2, (double)step));
-    hipLaunchKernelGGL(adam_kernel, dim3(1024, 9), dim3(256), 0, st, t, lr, b1, b2, eps, c1, c2);
+    if (clip)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3(1024, 9), dim3(256), 0, st, t, lr, b1, b2, eps, c1, c2, clip);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3(1024, 9), dim3(256), 0, st, t, lr, b1, b2, eps, c1, c2, clip);
+}
+void k_sumsq(hipStream_t st, const SumsqArgs &a, double *parts, ClipCtl *ctl) {
+    if (a.count <= 0) return;
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3(kSumsqParts, a.count), dim3(256), 0, st, a, parts);
+    hipLaunchKernelGGL(sumsq_final_kernel, dim3(a.count), dim3(256), 0, st, a, parts, ctl);
+}
+void k_clip_set(hipStream_t st, ClipCtl *ctl, int n_slots, float max_norm) {
+    hipLaunchKernelGGL(clip_set_kernel, dim3(1), dim3(64), 0, st, ctl, n_slots, max_norm);
 }
 void k_mul_f32(hipStream_t st, const float *a, const float *b, int64_t n, float *out) {
     hipLaunchKernelGGL(mul_f32_kernel, dim3(grid1d(n)), dim3(256), 0, st, a, b, n, out);

@@ -149,14 +149,27 @@ class HipOps:
         L.lossgradient(self.ctx, param, feats, tokens, norm_B=norm_B, pdrop=pdrop, seed=seed, grads=grads,
                        want_loss=False, lens=lens, norm_tokens=norm_tokens)
 
-    def update(self, param, grads, optim):
-        L.update(self.ctx, param, grads, optim)
+    def update(self, param, grads, optim, clipped=False):
+        L.update(self.ctx, param, grads, optim, clipped=clipped)
 
-    def update_group(self, param, grads, optim, group, stream):
-        L.update_group(self.ctx, param, grads, optim, group, stream)
+    def update_group(self, param, grads, optim, group, stream, clipped=False):
+        L.update_group(self.ctx, param, grads, optim, group, stream, clipped=clipped)
 
-    def update_flat(self, w, g, m, v, optim, stream):
-        L.update_flat(self.ctx, w, g, m, v, optim, stream)
+    def update_flat(self, w, g, m, v, optim, stream, clipped=False):
+        L.update_flat(self.ctx, w, g, m, v, optim, stream, clipped=clipped)
+
+    # global gradient-norm clipping on the device (include/lrcn_clip.h)
+    def grad_sumsq(self, g, slot=0, stream=None, group=-1):
+        L.grad_sumsq(self.ctx, g, slot=slot, stream=stream, group=group)
+
+    def clip_slots(self, n_slots):
+        return L.clip_slots(self.ctx, n_slots)
+
+    def clip_set(self, max_norm, n_slots=9, stream=None):
+        L.clip_set(self.ctx, max_norm, n_slots=n_slots, stream=stream)
+
+    def clip_stats(self):
+        return L.clip_stats(self.ctx)
 
     def refresh_shadows_group(self, param, group, stream):
         L.refresh_shadows_group(self.ctx, param, group, stream)
@@ -251,9 +264,14 @@ class DataParallelTrainer:
         self.pdrop, self.seed = pdrop, seed
         self.group = group
         self.normalize_features = bool(normalize_features)   # input / sum(input) on the VGG's output (lrcn.jl:595-597)
-        # --gclip (parsed and ignored by the reference): clip the GLOBAL gradient norm, i.e. after the exchange and before update! -- which
-        # rules out the per-group [all-reduce -> Adam] pipeline: one all-reduce of the flat buffer, the norm, one Adam launch
+        # --gclip (parsed and ignored by the reference): clip the GLOBAL gradient norm, i.e. after the exchange and before update!.  On the
+        # device (include/lrcn_clip.h) in every mode of the "torch" backend: the sums of squares are taken per tensor (per slice, sharded)
+        # behind each group's exchange, the norm and the scale stay in device memory and ONE clipped update follows the join -- the host
+        # never waits.  Ops objects without the clip methods (CPU stand-ins) keep the host form: one all-reduce of the flat buffer, the norm
+        # read back, one Adam launch.
         self.gclip = float(gclip or 0.0)
+        self._dev_clip = self.gclip > 0 and all(hasattr(self.ops, n) for n in ("grad_sumsq", "clip_set", "clip_slots", "clip_stats"))
+        host_clip = self.gclip > 0 and not self._dev_clip
         # emulate_shards = N > 1 (one process, world = 1; bench.py --emulate-world N --shard-adam): rank 0's side of an N-rank SHARDED update
         # with the two collectives stubbed by device copies of the bytes a rank receives -- Adam on 1/N of every gradient group, the other
         # (N-1)/N of the parameters are NOT updated.  A timing aid, never a training mode.
@@ -285,7 +303,7 @@ class DataParallelTrainer:
         if shard_adam is None:
             shard_adam = os.environ.get("LRCN_DP_SHARD_ADAM", "0")[:1] == "1"
         self.shard = (bool(shard_adam) and self.backend == "torch" and hasattr(self.ops, "update_flat") and hasattr(self.ops, "grad_group_wait")
-                      and not self.gclip > 0)
+                      and not host_clip)
         env = os.environ.get("LRCN_FUSED_UPDATE")
         fused = (env[:1] != "0") if env else True
         self._fused = bool(fused and not self.shard and hasattr(self.ops, "set_fused_update"))
@@ -337,7 +355,7 @@ class DataParallelTrainer:
         # LRCN_DP_SPARSE_EMBED=0 / 1 forces it off / on (1: also on a one-rank group, for tests).
         env_sp = os.environ.get("LRCN_DP_SPARSE_EMBED")
         want = (env_sp[:1] != "0") if env_sp else world > 1
-        self._sparse_embed = bool(want and self.backend == "torch" and not self.shard and not self.gclip > 0 and self._multi_or_forced_sparse(env_sp)
+        self._sparse_embed = bool(want and self.backend == "torch" and not self.shard and not host_clip and self._multi_or_forced_sparse(env_sp)
                                   and hasattr(self.ops, "embed_grad_from_rows") and hasattr(self.ops, "update_group") and ctx is not None
                                   and self._group_pipeline())   # the per-group [exchange -> Adam] pipeline is where the rows are summed
         if self._sparse_embed:
@@ -695,7 +713,7 @@ class DataParallelTrainer:
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens))
         else:
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)
-        if self.gclip > 0:
+        if self.gclip > 0 and not self._dev_clip:
             if self.world > 1:
                 dist.all_reduce(self.flat_grads, op=dist.ReduceOp.SUM, group=self.group)
             gn = float(torch.linalg.vector_norm(self.flat_grads))
@@ -718,8 +736,22 @@ class DataParallelTrainer:
         inorder_vgg()
         for w in works:
             w.wait()  # the compute stream waits for RCCL
-        self.ops.update(self.param, self.grads, self.optim)
+        self._update_whole_model()
         return consumed
+
+    def _update_whole_model(self):
+        """One update! of all nine tensors on the compute stream; under gclip: nine sums of squares -> norm / scale / skip -> the clipped one."""
+        if self._dev_clip:
+            self.ops.grad_sumsq(self.grads, group=-1)
+            self.ops.clip_set(self.gclip, 9)
+            self.ops.update(self.param, self.grads, self.optim, clipped=True)
+        else:
+            self.ops.update(self.param, self.grads, self.optim)
+
+    def clip_stats(self):
+        """{last_norm, last_scale, last_skipped, steps, clipped, skipped} of the device-side clipping (waits for the device); None when this
+        trainer does not clip on the device."""
+        return self.ops.clip_stats() if self._dev_clip else None
 
     def _group_pipeline(self):
         """Per-group [all-reduce -> Adam] needs the device-side gradient-group events and the per-group update entry point
@@ -737,7 +769,9 @@ class DataParallelTrainer:
     def _reduce_and_update_groups(self):
         if self._bucket_streams is None:
             self._bucket_streams = self._make_update_streams()
-        self.optim.t += 1
+        clip = self._dev_clip   # the norm needs every group: only the exchanges stay behind the backward pass, Adam follows the join
+        if not clip:
+            self.optim.t += 1
         for k, (a, b) in enumerate(self._group_slices()):
             s = self._bucket_streams[k]
             self.ops.grad_group_wait(k, s)  # s waits for the group's event recorded inside lossgradient
@@ -748,8 +782,14 @@ class DataParallelTrainer:
                     self.ops.embed_grad_from_rows(rows_all, tok_all, n, self.grads[6], s)
                 elif self._multi and b > a:
                     dist.all_reduce(self.flat_grads[a:b], op=dist.ReduceOp.SUM, group=self.group, async_op=True).wait()  # s waits for RCCL
-                self.ops.update_group(self.param, self.grads, self.optim, k, s)
+                if clip:
+                    self.ops.grad_sumsq(self.grads, group=k, stream=s)   # tensor k's sum of squares into slot k, behind its exchange
+                else:
+                    self.ops.update_group(self.param, self.grads, self.optim, k, s)
         self.ops.join(self._bucket_streams)
+        if clip:
+            self.ops.clip_set(self.gclip, 9)
+            self.ops.update(self.param, self.grads, self.optim, clipped=True)
 
     def _reduce_scatter_update_gather(self):
         """The sharded form of _reduce_and_update_groups: per group, on its own stream, [wait for the group's gradients] ->
@@ -765,10 +805,13 @@ class DataParallelTrainer:
         # a one-rank process group given explicitly (tests on a one-GPU box): the collectives are issued all the same
         coll = self.world > 1 or (self.group is not None and dist.is_initialized())
         nccl = coll and dist.get_backend(self.group) == "nccl"
+        clip = self._dev_clip
         for k, (a, b) in enumerate(self._ranges):
             s = self._bucket_streams[k]
             self.ops.grad_group_wait(k, s)
             if b == a:
+                if clip:
+                    self.ops.grad_sumsq(self._gshard[k], slot=k, stream=s)   # an empty run: slot k = 0
                 if self._shadow_groups:
                     self.ops.refresh_shadows_group(self.param, k, s)   # an empty group still counts towards "all five refreshed"
                 continue  # LRCN-1f has no W2 / b2 group
@@ -786,24 +829,50 @@ class DataParallelTrainer:
                     tmp = g_all.clone()
                     dist.all_reduce(tmp, op=dist.ReduceOp.SUM, group=self.group)
                     self._gshard[k].copy_(tmp[r * n:(r + 1) * n])
+                if clip:   # this rank's slice of the summed gradient (its padding is zeros) into slot k; phase 2 below does the rest
+                    self.ops.grad_sumsq(self._gshard[k], slot=k, stream=s)
+                    continue
                 self.ops.update_flat(mine, self._gshard[k], self._m[k], self._v[k], self.optim, s)
-                if self._emu_shards:   # stub of the all-gather: (N-1) n floats arrive (device copy of as many bytes; values discarded)
-                    self._emu_scratch[:b - a - n].copy_(self.flat_param[a + n:b])
-                elif coll:
-                    if nccl:
-                        dist.all_gather_into_tensor(self.flat_param[a:b], mine, group=self.group)
-                    else:
-                        parts = [torch.empty_like(mine) for _ in range(W)]
-                        dist.all_gather(parts, mine.clone(), group=self.group)
-                        for i, t in enumerate(parts):
-                            self.flat_param[a + i * n:a + (i + 1) * n].copy_(t)
-                if self._shadow_groups:   # the group's parameters are final on this stream: its shadows for the next step, beside the backward pass
-                    self.ops.refresh_shadows_group(self.param, k, s)
+                self._gather_group(k, a, b, mine, coll, nccl, s)
+        if clip:
+            # the global norm needs every rank's slices of every group: join, one all-reduce of the five partial sums (float64, in the
+            # control block itself), norm / scale / skip, then per group the clipped Adam on the slice, the all-gather and the shadows --
+            # on the compute stream: with the backward pass over there is nothing left to run beside
+            self.ops.join(self._bucket_streams)
+            slots = self.ops.clip_slots(len(self._ranges))
+            if coll:
+                dist.all_reduce(slots, op=dist.ReduceOp.SUM, group=self.group)
+            self.ops.clip_set(self.gclip, len(self._ranges))
+            for k, (a, b) in enumerate(self._ranges):
+                if b == a:
+                    continue
+                n = (b - a) // W
+                mine = self.flat_param[a + r * n:a + (r + 1) * n]
+                self.ops.update_flat(mine, self._gshard[k], self._m[k], self._v[k], self.optim, None, clipped=True)
+                self._gather_group(k, a, b, mine, coll, nccl, None)
+            return
         if tail:
             e_upd = torch.cuda.Event(enable_timing=True)
             e_upd.record(self._bucket_streams[-1])
             self._tail_events = getattr(self, "_tail_events", []) + [(e_bwd, e_upd)]
         self.ops.join(self._bucket_streams)
+
+    def _gather_group(self, k, a, b, mine, coll, nccl, s):
+        """The sharded update's tail for group k on the current stream (`s`, None = the compute stream): all-gather of the parameters from
+        the ranks' slices, then the group's shadow weights for the next step."""
+        n = mine.numel()
+        if self._emu_shards:   # stub of the all-gather: (N-1) n floats arrive (device copy of as many bytes; values discarded)
+            self._emu_scratch[:b - a - n].copy_(self.flat_param[a + n:b])
+        elif coll:
+            if nccl:
+                dist.all_gather_into_tensor(self.flat_param[a:b], mine, group=self.group)
+            else:
+                parts = [torch.empty_like(mine) for _ in range(self._W)]
+                dist.all_gather(parts, mine.clone(), group=self.group)
+                for i, t in enumerate(parts):
+                    self.flat_param[a + i * n:a + (i + 1) * n].copy_(t)
+        if self._shadow_groups:   # the group's parameters are final on this stream: its shadows for the next step, beside the backward pass
+            self.ops.refresh_shadows_group(self.param, k, s)
 
     def describe(self):
         """What this trainer's step is made of (reported in bench.py's line: rccl.pipeline)."""

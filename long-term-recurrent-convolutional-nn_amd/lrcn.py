@@ -290,26 +290,63 @@ def initparams(model):
     return Adam(model)
 
 
-def update(ctx, param, grads, optim):
-    """update!(param, gloss, optim) (lrcn.jl:394)."""
+def _stream_arg(stream):
+    return C.c_void_p(stream.cuda_stream) if stream is not None else None
+
+
+def grad_sumsq(ctx, g, slot=0, stream=None, group=-1):
+    """Sum of squares (a double in the context's control block, include/lrcn_clip.h) of a gradient, on `stream`: g a float32 tensor ->
+    slot `slot`; g a model's nine gradients -> tensor k into slot k, for the tensors of gradient group `group` (-1: all nine)."""
+    if torch.is_tensor(g):
+        assert g.dtype == torch.float32 and g.is_contiguous()
+        ctx._call("lrcn_grad_sumsq", C.c_void_p(g.data_ptr()) if g.numel() else None, g.numel(), int(slot), _stream_arg(stream))
+    else:
+        ctx._call("lrcn_grad_sumsq_model", _p9(g), int(group), _stream_arg(stream))
+
+
+def clip_slots(ctx, n_slots=9):
+    """The control block's first n_slots sums of squares as a float64 device tensor that aliases them (a sharded job all-reduces it)."""
+    p = C.c_void_p()
+    ctx._call("lrcn_clip_slots", C.byref(p))
+
+    class _Mem:   # the CUDA array interface: a view, the context keeps the memory
+        __cuda_array_interface__ = {"shape": (int(n_slots),), "typestr": "<f8", "data": (p.value, False), "version": 2}
+    return torch.as_tensor(_Mem(), device=torch.device("cuda", ctx.device))
+
+
+def clip_set(ctx, max_norm, n_slots=9, stream=None):
+    """norm = sqrt(slot[0] + ... + slot[n_slots - 1]), skip = not finite, scale = max_norm / norm when norm > max_norm (lrcn_clip_set)."""
+    ctx._call("lrcn_clip_set", int(n_slots), float(max_norm), _stream_arg(stream))
+
+
+def clip_stats(ctx):
+    """Waits for the context's stream: {last_norm, last_scale, last_skipped, steps, clipped, skipped} (lrcn_clip_stats)."""
+    st = _lib.ClipStats()
+    ctx._call("lrcn_clip_stats", C.byref(st))
+    return {"last_norm": st.last_norm, "last_scale": st.last_scale, "last_skipped": int(st.last_skipped), "steps": int(st.steps),
+            "clipped": int(st.clipped), "skipped": int(st.skipped)}
+
+
+def update(ctx, param, grads, optim, clipped=False):
+    """update!(param, gloss, optim) (lrcn.jl:394).  clipped: on grads * scale, scale and skip read from the context's control block."""
     optim.t += 1
-    ctx._call("lrcn_adam_update", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), optim.t, optim.lr, optim.beta1,
+    ctx._call("lrcn_adam_update_clipped" if clipped else "lrcn_adam_update", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), optim.t, optim.lr, optim.beta1,
               optim.beta2, optim.eps)
 
 
-def update_group(ctx, param, grads, optim, group, stream=None):
+def update_group(ctx, param, grads, optim, group, stream=None, clipped=False):
     """update! for the tensors of one gradient group (include/lrcn.h lrcn_adam_update_group) on `stream`; the caller
     advances optim.t once per step, before the first group."""
-    ctx._call("lrcn_adam_update_group", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), int(group), optim.t, optim.lr,
+    ctx._call("lrcn_adam_update_group_clipped" if clipped else "lrcn_adam_update_group", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), int(group), optim.t, optim.lr,
               optim.beta1, optim.beta2, optim.eps, C.c_void_p(stream.cuda_stream) if stream is not None else None)
 
 
-def update_flat(ctx, w, g, m, v, optim, stream=None):
+def update_flat(ctx, w, g, m, v, optim, stream=None, clipped=False):
     """The Adam arithmetic on one flat run of floats (lrcn_adam_update_flat): w, g, m, v are 1-D float32 tensors of equal length; the
     caller advances optim.t once per step."""
     n = w.numel()
     assert g.numel() == n and m.numel() == n and v.numel() == n
-    ctx._call("lrcn_adam_update_flat", C.c_void_p(w.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()),
+    ctx._call("lrcn_adam_update_flat_clipped" if clipped else "lrcn_adam_update_flat", C.c_void_p(w.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()),
               n, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps, C.c_void_p(stream.cuda_stream) if stream is not None else None)
 
 
@@ -318,23 +355,27 @@ def refresh_shadows_group(ctx, param, group, stream=None):
     ctx._call("lrcn_refresh_shadows_group", _p9(param), int(group), C.c_void_p(stream.cuda_stream) if stream is not None else None)
 
 
-def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None):
-    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens: as loss()."""
+def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None,
+               gclip=0.0):
+    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens: as loss().
+    gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h; clip_stats() has the counters)."""
+    gclip = float(gclip or 0.0)
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     d, keep = _dropout(pdrop, seed, None, None)
     la = _lens(lens, T, B, norm_tokens) if lens is not None else None   # checked before the step counter moves
     optim.t += 1
     out = C.c_double()
+    clip = (gclip,) if gclip > 0 else ()
     if la is not None:
-        ctx._call("lrcn_train_step_var", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()),
-                  la[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps,
-                  C.byref(out) if want_loss else None)
+        ctx._call("lrcn_train_step_var_clip" if clip else "lrcn_train_step_var", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v),
+                  _ptr(feats), C.c_void_p(tok.data_ptr()), la[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1,
+                  optim.beta2, optim.eps, *clip, C.byref(out) if want_loss else None)
         del keep, la
         return out.value if want_loss else None
-    ctx._call("lrcn_train_step", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()),
-              T, B, norm_B or B, C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps,
-              C.byref(out) if want_loss else None)
+    ctx._call("lrcn_train_step_clip" if clip else "lrcn_train_step", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats),
+              C.c_void_p(tok.data_ptr()), T, B, norm_B or B, C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2,
+              optim.eps, *clip, C.byref(out) if want_loss else None)
     del keep
     return out.value if want_loss else None
 

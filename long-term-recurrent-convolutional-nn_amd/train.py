@@ -123,4 +123,7 @@ def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feat
         if trainer.rank == 0:
             log("(:epoch, %d, :loss, %s)  [%.0f captions/s on %d rank%s]" % (epoch, ", ".join("%.4f" % v for v in losses),
                                                                            n * trainer.world / max(dt_s, 1e-9), trainer.world, "" if trainer.world == 1 else "s"))
+            st = trainer.clip_stats() if getattr(trainer, "gclip", 0) > 0 and hasattr(trainer, "clip_stats") else None
+            if st is not None:   # --gclip on the device (include/lrcn_clip.h): the counters run since the trainer's first step
+                log("(:gclip, %g, :clipped, %d, :skipped, %d, :last_norm, %.6g)" % (trainer.gclip, st["clipped"], st["skipped"], st["last_norm"]))
     return history

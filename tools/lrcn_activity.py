@@ -45,6 +45,7 @@ def parse(argv):
     p.add_argument("--batchsize", type=int, default=32, help="clips per step")
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--gclip", type=float, default=0.0, help="Clip the global gradient norm to this on the device (0 = off).")
     p.add_argument("--atype", default="bf16", choices=("f32", "bf16"), help="arithmetic of the LSTM and the head")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--savefile")
@@ -143,7 +144,7 @@ def train(o):
             sp = [specs[k] for k in order[i:i + o.batchsize]]
             x, lens = A.gather_clips(vf, sp, o.clip)
             lab = labels[[v for v, _, _ in sp]]
-            tot += m.train_step(x, lab, lens, o.clip, lr=o.lr) * float(lens.sum())
+            tot += m.train_step(x, lab, lens, o.clip, lr=o.lr, gclip=o.gclip) * float(lens.sum())
             n += int(lens.sum())
         say("epoch %d loss %.6f" % (ep, tot / max(n, 1)))
     m.sync()
