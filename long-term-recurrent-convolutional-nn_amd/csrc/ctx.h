@@ -1,5 +1,7 @@
 // ctx.h -- the caption model's context (struct lrcn_ctx, opaque at the ABI) and the internal helpers that more than one of its
-// files needs: lrcn_api.hip (context, training, update), decode.hip (beam search, sampling, n-best, scoring), vgg.hip (VGG-16 forward).
+// files needs: lrcn_api.hip (context, GEMM helper, single step), train.hip (forward / backward pass, loss and train-step entry points),
+// update.hip (shadow weights, Adam, gradient-norm clipping), train_dp.hip (data parallelism), decode.hip (beam search, sampling, n-best,
+// scoring), vgg.hip (VGG-16 forward).
 #pragma once
 #include <utility>
 
@@ -225,6 +227,13 @@ struct SegScope {
     }
 };
 
+// a `void *stream` argument of the ABI: NULL means the context's stream
+inline hipStream_t stream_or_ctx(lrcn_ctx *c, void *stream) { return stream ? reinterpret_cast<hipStream_t>(stream) : c->stream; }
+// element counts of the context's 9 tensors (0 for the slots its model does not have)
+inline void ctx_sizes(const lrcn_ctx *c, int64_t sz[9]) { lrcn_param_sizes_n(c->nl, c->E, c->H1, c->H2, c->V, sz); }
+// the tensors of each gradient group, in the order of the grad_ev records in loss_impl
+constexpr int kGradGroup[LRCN_GRAD_GROUPS][2] = {{7, 8}, {2, 3}, {4, 5}, {0, 1}, {6, 6}};
+
 // C[M][N] (+)= A[M][K] * B[N][K]^T on the context's stream or (on_wg_stream) its weight-gradient stream, with its route hints (lrcn_api.hip)
 int gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const void *B, int64_t ldb, void *C, int64_t ldc, int M, int N, int K,
          const float *bias, bool c_f32, bool beta = false, bool relu = false, bool c_is_zero = false, bool on_wg_stream = false);
@@ -235,11 +244,26 @@ int gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const void *B, int6
         if (_r) return _r;            \
     } while (0)
 
-// f32 column-major params -> K-contiguous shadows in T (lrcn_api.hip; see DESIGN.md "shadow weights")
-int prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_bwd, bool cat = false, bool gi = false, bool cat_perm = false,
-                    bool dec_tables = false);
+// the text lrcn_last_error(NULL) returns: failures of the entry points that take no context (lrcn_api.hip)
+void set_create_error(const char *msg);
 // lrcn() on the context's single-step buffers (lrcn_api.hip): lrcn_step and the single-image beam search
 int step_internal(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2, bool h_ready = false);
+// loss / lossgradient on the context's buffers (train.hip): grads NULL = forward only, lens != NULL = the variable-length form
+int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
+              const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens = nullptr, int64_t norm_tokens = 0);
+// waits for the context's stream; the last loss call's mean loss into *out (NULL: only the out-of-range-token check) (train.hip)
+int fetch_loss(lrcn_ctx *c, double *out);
+// f32 column-major params -> K-contiguous shadows in T (update.hip; see DESIGN.md "shadow weights")
+int prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_bwd, bool cat = false, bool gi = false, bool cat_perm = false,
+                    bool dec_tables = false);
+// the second shadow set of LRCN_OPT_FUSED_UPDATE, allocated once (update.hip): lrcn_set_option makes it outside any step
+int ensure_alt_shadows(lrcn_ctx *c);
+// update! of all nine tensors / of one gradient group on `stream` (update.hip): lrcn_adam_update[_group] and, `clipped`, their clipped
+// namesakes, argument checks included
+int adam_update(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int step, float lr, float b1,
+                float b2, float eps, bool clipped);
+int adam_update_group(lrcn_ctx *c, float *const p[9], const float *const g[9], float *const m[9], float *const v[9], int group, int step,
+                      float lr, float b1, float b2, float eps, void *stream, bool clipped);
 // the VGG-16 forward of N images into featsRM (vgg.hip): lrcn_train_step_dp and the image entry points
 int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean, bool calibrate = false);
 int vgg_check(lrcn_ctx *c, int N);

@@ -88,7 +88,7 @@ struct GemmArgs {
                             // walking a fixed share, so one that starts late (its CU still busy with another stream's kernel) does
                             // fewer tiles instead of stretching the whole launch; NULL = static round-robin walk
     unsigned long long *stamps;  // kernel-development: per-tile s_memtime stamps of gemm8p_tile's segments (8 per tile), or NULL
-    int splitk_forced;      // launch_gemm_8p(.., splitk): take the caller's slice count as it is (lrcn_api.hip's LRCN_BWD_SLABS route)
+    int splitk_forced;      // launch_gemm_8p(.., splitk): take the caller's slice count as it is (train.hip's LRCN_BWD_SLABS route)
     int splitk_no_reduce;   // ... and leave the f32 slabs [slices][M][N] in ws for the caller's next kernel to sum (no reduce launch, C untouched)
     int deterministic;      // 1: no float-atomic split-K (gemm_glds.hip takes one K range per tile; gemm_8p's slab split-K is ordered anyway)
     int dbg;                // kernel-development ablation flags (LRCN_DBG env): 8 = gemm_8p.hip does not issue the next tile's first K-tile early
@@ -97,7 +97,7 @@ struct GemmArgs {
     size_t ws_bytes;
 };
 
-// The "beside the convolutions" routes (bg_cus: the 8p-bg rung of gemm_route.hip, the cell-epilogue and K-sliced recurrences of lrcn_api.hip)
+// The "beside the convolutions" routes (bg_cus: the 8p-bg rung of gemm_route.hip, the cell-epilogue and K-sliced recurrences of train.hip)
 // apply to contractions of kBgMinRows..kBgMaxRows rows (below, the VGG forward's own grids are small, more CUs are free, and the LSTM chain is
 // the critical path).
 constexpr int kBgMinRows = 256, kBgMaxRows = 512;

@@ -1,4 +1,4 @@
-// host.h -- host plumbing of the caption model (lrcn_api.hip, decode.hip, vgg.hip) and activity recognition (activity.hip).  Nothing here
+// host.h -- host plumbing of the caption model (lrcn_api.hip, train*.hip, update.hip, decode.hip, vgg.hip) and activity recognition (activity.hip).  Nothing here
 // knows a context: the macros, the device guard and the allocator work on any handle with `std::string err` (the allocator: and `allocs`).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -100,7 +100,7 @@ void k_transpose_multi(hipStream_t st, int dtype, TrPlan &plan);
 void k_init_uniform(hipStream_t st, float *w, int64_t n, float scale, uint64_t seed, int tensor);
 void k_fill(hipStream_t st, float *w, int64_t n, float v);
 
-// ---- train_kernels.hip: the training step (lrcn_api.hip) ----
+// ---- train_kernels.hip: the training step (train.hip, update.hip) ----
 // tok_in[s][b] = bos (s==0) | tokens[s-1][b];  tok_tgt[s][b] = tokens[s][b] (s<T) | eos.   (lrcn.jl:556,565,569,576)
 void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc);
 // Per-row lengths (device int32 [B], 0 <= lens[b] <= T): row b's step s is active for s <= lens[b] -- tok_in / tok_tgt as above with

@@ -1,6 +1,6 @@
 // kernels.hip -- the HBM-bound kernels that more than one model file launches: embedding gather, LSTM cell forward / backward, [x | cnn]
 // concatenation with dropout, fused log-softmax + NLL + dlogits, layout transposes, casts, column sums, fills (one wave = 64 lanes).  What one
-// host file alone uses is beside it: train_kernels.hip (lrcn_api.hip), decode_kernels.hip (decode.hip), image_kernels.hip (the VGG side).
+// host file alone uses is beside it: train_kernels.hip (train.hip, update.hip), decode_kernels.hip (decode.hip), image_kernels.hip (the VGG side).
 #include "kernel_util.h"
 
 namespace {

@@ -1,4 +1,4 @@
-// train_kernels.hip -- the kernels only the training step (lrcn_api.hip) launches: token rows, the embedding gradient (scatter, sparse
+// train_kernels.hip -- the kernels only the training step (train.hip, update.hip) launches: token rows, the embedding gradient (scatter, sparse
 // export, ordered sums), dropout mask + reduce of dX2, the shadow-weight pass with and without Adam, multi-tensor Adam, and the gradient-norm
 // clipping of include/lrcn_clip.h (sum of squares, control block, the clipped forms of both Adam kernels).
 #include "kernel_util.h"

@@ -6,7 +6,7 @@ keeps it iff u > p, with the multiplier 1 / (1 - p), everything in float32.  Her
 and the multiplier, `u > float32(p)`, `float32(1) / (float32(1) - float32(p))`.  The top 24 bits of a hash convert to float32 exactly and
 2^-24 is a power of two, so u is exact and the only rounding of the whole transcription is the one division.
 
-The route code of lrcn_api.hip never looks at a mask (make_drop is the only reader), so a call with (pdrop, seed) and a call with these
+The route code of train.hip never looks at a mask (make_drop is the only reader), so a call with (pdrop, seed) and a call with these
 arrays as explicit masks are the same arithmetic: tests/test_gpu_dropout_seeded.py demands bit-equal results.
 """
 import numpy as np

@@ -3,7 +3,7 @@ real run) against its host transcription (tests/dropout_ref.py).
 
 The seeded mask is applied by two forward kernels (embed_gather, concat_x2) and four backward kernels (embed_scatter_rm, embed_segsum,
 embed_rows_export, dx2_mask_reduce), each of which computes the counter (s, b, j) -> (s B + b) ncols + j on its own.  The route code of
-lrcn_api.hip never looks at the mask, so lossgradient(pdrop, seed) and lossgradient(mask1 = host, mask2 = host) are the same arithmetic with
+train.hip never looks at the mask, so lossgradient(pdrop, seed) and lossgradient(mask1 = host, mask2 = host) are the same arithmetic with
 the same multipliers -- if and only if every one of those kernels indexes the counter as the transcription does, uses stream 1 / 2 where it
 does, compares u > p and multiplies by float32(1) / (float32(1) - float32(p)).  Under LRCN_OPT_DETERMINISTIC every sum has a fixed order,
 so the demand is np.array_equal on the loss and on all nine gradients, in the two-layer model in f32 and bf16 and in LRCN-1f (one mask,
