@@ -18,6 +18,7 @@ NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
 CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
+WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
@@ -195,6 +196,18 @@ VARLEN_SIGNATURES = {
                                       C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_weighted.h declares (bound by lib() as well)
+WEIGHTED_SIGNATURES = {
+    "lrcn_loss_w": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int64,
+                              C.POINTER(Dropout), C.POINTER(C.c_double)]),
+    "lrcn_loss_grad_w": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                   C.c_int64, C.POINTER(Dropout), P9, C.POINTER(C.c_double)]),
+    "lrcn_train_step_w": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                    C.c_int, C.c_int64, C.POINTER(Dropout), C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    C.POINTER(C.c_double)]),
+}
+
+
 class ClipStats(C.Structure):
     """lrcn_clip_stats_t (include/lrcn_clip.h)."""
     _fields_ = [("last_norm", C.c_double), ("last_scale", C.c_float), ("last_skipped", C.c_int32), ("steps", C.c_int64),
@@ -229,7 +242,7 @@ GEMM_DEBUG_SIGNATURES = {
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, GEMM_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -250,7 +263,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
+                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

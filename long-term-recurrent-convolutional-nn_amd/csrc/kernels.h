@@ -68,6 +68,11 @@ void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l
 // all-zero dlog row, and its logits are not read.  The variable-length entry points of include/lrcn_varlen.h.
 void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
                            float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
+// The masked form with a real weight per caption (include/lrcn_weighted.h): row m belongs to caption b = m % B, row_w device f32 [B].
+// row_w[b] == 0 makes row m inactive (logits not read); otherwise its dlog row is (softmax - onehot) * (scale * row_w[b]) and its
+// log-likelihood term row_w[b] * log p(target), in double.
+void k_softmax_xent_weighted(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
+                             double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w, int B);
 
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)

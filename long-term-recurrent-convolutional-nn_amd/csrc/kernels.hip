@@ -108,17 +108,28 @@ __device__ __forceinline__ void softmax_xent_inactive_row(int m, int V, T *dlog,
 }
 
 // MASKED: the variable-length entry points' form (k_softmax_xent_masked); the equal-length launcher instantiates MASKED = false only.
-template <typename T, bool MASKED = false>
+// WEIGHTED (with MASKED; include/lrcn_weighted.h): row m belongs to caption b = m % B and carries the real weight row_w[b] -- a zero
+// weight makes the row inactive (as uniform over the workgroup as the target's sign), any other one scales its d(logits) row and its
+// log-likelihood term.  With every weight 1.0f the arithmetic is the masked kernel's bit for bit (scale * 1.0f == scale).
+// Its two arguments (const float *row_w, int B) are the pack RW, which is empty otherwise: the unweighted instantiations keep their
+// arguments and compile to the instructions they had without the option.
+__device__ __forceinline__ float softmax_xent_row_weight(int m, const float *row_w, int B) { return row_w[m % B]; }
+
+template <typename T, bool MASKED = false, bool WEIGHTED = false, typename... RW>
 __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M,
-                                                           int V, float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows) {
+                                                           int V, float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows,
+                                                           RW... rw) {
     __shared__ float sh[8];
     const int m = blockIdx.x;
+    [[maybe_unused]] float w = 1.0f;
+    if constexpr (WEIGHTED) w = softmax_xent_row_weight(m, rw...);
     if constexpr (MASKED) {
-        if (tgt[m] < 0) {
+        if (tgt[m] < 0 || (WEIGHTED && w == 0.0f)) {
             softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
             return;
         }
     }
+    if constexpr (WEIGHTED) scale *= w;  // rs = scale * row_w[b], once per row
     const float *row = logits + (int64_t)m * ld_l;
     float mx = -INFINITY;
     for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, row[v]);
@@ -129,8 +140,13 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, 
     const float lse = mx + logf(se);
     const int t = tgt[m];
     if (threadIdx.x == 0) {
-        if (logp_rows) logp_rows[m] = (double)(row[t] - lse);
-        else atomicAdd(logp_sum, (double)(row[t] - lse));
+        if constexpr (WEIGHTED) {
+            if (logp_rows) logp_rows[m] = (double)w * (double)(row[t] - lse);
+            else atomicAdd(logp_sum, (double)w * (double)(row[t] - lse));
+        } else {
+            if (logp_rows) logp_rows[m] = (double)(row[t] - lse);
+            else atomicAdd(logp_sum, (double)(row[t] - lse));
+        }
     }
     if (dlog) {
         T *drow = dlog + (int64_t)m * ld_d;
@@ -143,17 +159,21 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, 
 
 // The same for V <= 1024 Q with the row held in registers: one expf per element (e = expf(x - max), p = e / sum) instead of
 // two, 16-byte loads; the log-likelihood term is unchanged (x[t] - (max + logf(sum))).
-template <typename T, int Q, bool MASKED = false>
+template <typename T, int Q, bool MASKED = false, bool WEIGHTED = false, typename... RW>
 __global__ __launch_bounds__(256) void softmax_xent_reg_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                                                               float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows) {
+                                                               float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows,
+                                                               RW... rw) {
     __shared__ float sh[8];
     const int m = blockIdx.x;
+    [[maybe_unused]] float w = 1.0f;
+    if constexpr (WEIGHTED) w = softmax_xent_row_weight(m, rw...);
     if constexpr (MASKED) {
-        if (tgt[m] < 0) {
+        if (tgt[m] < 0 || (WEIGHTED && w == 0.0f)) {
             softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
             return;
         }
     }
+    if constexpr (WEIGHTED) scale *= w;  // rs = scale * row_w[b], once per row
     const float *row = logits + (int64_t)m * ld_l;  // ld_l % 4 == 0, 16-byte aligned rows
     float x[Q][4];
 #pragma unroll
@@ -183,8 +203,13 @@ __global__ __launch_bounds__(256) void softmax_xent_reg_kernel(const float *logi
     se = block_sum(se, sh);
     const int t = tgt[m];
     if (threadIdx.x == 0) {
-        if (logp_rows) logp_rows[m] = (double)(row[t] - (mx + logf(se)));
-        else atomicAdd(logp_sum, (double)(row[t] - (mx + logf(se))));
+        if constexpr (WEIGHTED) {
+            if (logp_rows) logp_rows[m] = (double)w * (double)(row[t] - (mx + logf(se)));
+            else atomicAdd(logp_sum, (double)w * (double)(row[t] - (mx + logf(se))));
+        } else {
+            if (logp_rows) logp_rows[m] = (double)(row[t] - (mx + logf(se)));
+            else atomicAdd(logp_sum, (double)(row[t] - (mx + logf(se))));
+        }
     }
     if (dlog) {
         T *drow = dlog + (int64_t)m * ld_d;
@@ -369,16 +394,22 @@ void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float
                                          B, nl, nr, d));
 }
 namespace {
-template <bool MASKED>
+template <bool MASKED, bool WEIGHTED = false>  // WEIGHTED: the masked form with per-caption weights row_w [B] (device)
 void launch_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                         double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
+                         double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w = nullptr, int B = 1) {
     const bool reg = V <= 16384 && (ld_l % 4) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(dlog) & 15) == 0;
     if (reg) {
         const int q = (V + 1023) / 1024;
 #define SX_LAUNCH(QQ)                                                                                                                      \
-    DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale, \
-                                         logp_sum, (T *)dlog, ld_d, logp_rows))
+    DISPATCH_T(dtype, {                                                                                                                    \
+        if constexpr (WEIGHTED)                                                                                                            \
+            hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, true, true, const float *, int>), dim3(M), dim3(256), 0, st, logits, ld_l,  \
+                               tgt, M, V, scale, logp_sum, (T *)dlog, ld_d, logp_rows, row_w, B);                                          \
+        else                                                                                                                               \
+            hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,        \
+                               logp_sum, (T *)dlog, ld_d, logp_rows);                                                                      \
+    })
         if (q <= 2) SX_LAUNCH(2);
         else if (q <= 4) SX_LAUNCH(4);
         else if (q <= 8) SX_LAUNCH(8);
@@ -386,8 +417,14 @@ void launch_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t
         else SX_LAUNCH(16);
 #undef SX_LAUNCH
     } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_kernel<T, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,
-                                             logp_sum, (T *)dlog, ld_d, logp_rows));
+        DISPATCH_T(dtype, {
+            if constexpr (WEIGHTED)
+                hipLaunchKernelGGL((softmax_xent_kernel<T, true, true, const float *, int>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V,
+                                   scale, logp_sum, (T *)dlog, ld_d, logp_rows, row_w, B);
+            else
+                hipLaunchKernelGGL((softmax_xent_kernel<T, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,
+                                   logp_sum, (T *)dlog, ld_d, logp_rows);
+        });
     }
     if (logp_rows) hipLaunchKernelGGL(sum_rows_f64_kernel, dim3(1), dim3(256), 0, st, logp_rows, M, logp_sum);
 }
@@ -399,6 +436,10 @@ void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l
 void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
                            float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
     launch_softmax_xent<true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows);
+}
+void k_softmax_xent_weighted(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
+                             double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w, int B) {
+    launch_softmax_xent<true, true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows, row_w, B);
 }
 void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t ld_in, int R, int C, void *out,
                  int64_t ld_out, int shift) {

@@ -178,6 +178,9 @@ void lrcn_destroy(lrcn_ctx *c) {
     if (c->lens_pin) (void)hipHostFree(c->lens_pin);
     for (auto &e : c->lens_up)
         if (e) (void)hipEventDestroy(e);
+    if (c->roww_pin) (void)hipHostFree(c->roww_pin);
+    for (auto &e : c->roww_up)
+        if (e) (void)hipEventDestroy(e);
     if (c->wg_stream && c->wg_stream_owned) (void)hipStreamDestroy(c->wg_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     for (int j = 0; j < lrcn_ctx::kStage; ++j) {

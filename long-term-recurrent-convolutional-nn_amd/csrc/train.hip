@@ -18,6 +18,7 @@
 #include "ctx.h"
 #include "../../include/lrcn_varlen.h"
 #include "../../include/lrcn_clip.h"
+#include "../../include/lrcn_weighted.h"
 
 using namespace lrcn_impl;
 
@@ -176,37 +177,47 @@ int check_shapes(lrcn_ctx *c, int T, int B, int norm_B) {
     return LRCN_OK;
 }
 
-// lens (host, [B]) -> c->lens_dev on the context's stream, through the next pinned slot
-int upload_lens(lrcn_ctx *c, const int32_t *lens, int B) {
+// B per-row values (host; int32 lengths or f32 weights) -> dev [maxB] on the context's stream, through the next pinned slot of their ring
+template <typename E>
+int upload_rows(lrcn_ctx *c, const E *host, int B, E *&dev, E *&pin, hipEvent_t (&up)[lrcn_ctx::kLenSlots], int &next) {
     // each piece on its own guard: a call that failed half-way through here leaves the next one to create what is still missing
-    if (!c->lens_dev) DALLOC(c, c->lens_dev, sizeof(int32_t) * (size_t)c->maxB);
-    if (!c->lens_pin)
-        HIPCHK(c, hipHostMalloc((void **)&c->lens_pin, sizeof(int32_t) * (size_t)c->maxB * lrcn_ctx::kLenSlots, hipHostMallocDefault));
-    for (auto &e : c->lens_up)
+    if (!dev) DALLOC(c, dev, sizeof(E) * (size_t)c->maxB);
+    if (!pin) HIPCHK(c, hipHostMalloc((void **)&pin, sizeof(E) * (size_t)c->maxB * lrcn_ctx::kLenSlots, hipHostMallocDefault));
+    for (auto &e : up)
         if (!e) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    const int k = c->lens_slot;
-    c->lens_slot = (k + 1) % lrcn_ctx::kLenSlots;
-    HIPCHK(c, hipEventSynchronize(c->lens_up[k]));  // returns at once for an event never recorded
-    int32_t *slot = c->lens_pin + (size_t)k * c->maxB;
-    std::memcpy(slot, lens, sizeof(int32_t) * (size_t)B);
-    HIPCHK(c, hipMemcpyAsync(c->lens_dev, slot, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->lens_up[k], c->stream));
+    const int k = next;
+    next = (k + 1) % lrcn_ctx::kLenSlots;
+    HIPCHK(c, hipEventSynchronize(up[k]));  // returns at once for an event never recorded
+    E *slot = pin + (size_t)k * c->maxB;
+    std::memcpy(slot, host, sizeof(E) * (size_t)B);
+    HIPCHK(c, hipMemcpyAsync(dev, slot, sizeof(E) * (size_t)B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(up[k], c->stream));
     return LRCN_OK;
 }
+int upload_lens(lrcn_ctx *c, const int32_t *lens, int B) { return upload_rows(c, lens, B, c->lens_dev, c->lens_pin, c->lens_up, c->lens_slot); }
+int upload_row_w(lrcn_ctx *c, const float *w, int B) { return upload_rows(c, w, B, c->roww_dev, c->roww_pin, c->roww_up, c->roww_slot); }
 
 }  // namespace
 
 // loss / lossgradient on internal buffers. feats: B x 4096 column-major f32 (device).
 // lens != NULL (host, [B]): the variable-length form of include/lrcn_varlen.h -- row b has lens[b] + 1 loss terms, the scale is
 // 1 / norm_tokens and norm_B is not used.  Only the token builder and the softmax-NLL kernel differ; every launch in between is the same.
+// row_w != NULL (host, [B], with lens): the weighted form of include/lrcn_weighted.h -- caption b's terms and d(logits) rows carry
+// row_w[b]; the chain after the softmax-NLL kernel is linear in d(logits), so only that launch differs.
 int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
-                         const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens, int64_t norm_tokens) {
+                         const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens, int64_t norm_tokens,
+                         const float *row_w) {
     int r = check_shapes(c, T, B, norm_B);
     if (r) return r;
     if (lens) {
         if (norm_tokens < 1) FAIL(c, LRCN_EINVAL, "norm_tokens=%lld must be >= 1", (long long)norm_tokens);
         for (int b = 0; b < B; ++b)
             if (lens[b] < 0 || lens[b] > T) FAIL(c, LRCN_EINVAL, "lens[%d]=%d outside [0,%d]", b, lens[b], T);
+    }
+    if (row_w) {
+        if (!lens) FAIL(c, LRCN_EINVAL, "row weights need lens");
+        for (int b = 0; b < B; ++b)
+            if (!std::isfinite(row_w[b])) FAIL(c, LRCN_EINVAL, "row_w[%d]=%g is not finite", b, (double)row_w[b]);
     }
     if (drop && (drop->pdrop < 0.0f || drop->pdrop >= 1.0f)) FAIL(c, LRCN_EINVAL, "pdrop=%g outside [0,1)", drop->pdrop);
     if (drop && c->nl == 2 && ((drop->mask1 == nullptr) != (drop->mask2 == nullptr))) FAIL(c, LRCN_EINVAL, "mask1/mask2 must both be set");
@@ -227,6 +238,7 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     if (lens) {
         if ((r = upload_lens(c, lens, B))) return r;
         k_build_tokens_var(st, tokens, c->lens_dev, T, B, V, c->tok_in, c->tok_tgt, c->logp);
+        if (row_w && (r = upload_row_w(c, row_w, B))) return r;
     } else {
         k_build_tokens(st, tokens, T, B, V, c->tok_in, c->tok_tgt, c->logp);  // reads the caller's (T, B) ids once (T = 0: never)
     }
@@ -289,8 +301,10 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     }
     const float scale = (float)(1.0 / (lens ? (double)norm_tokens : (double)norm_B * (double)S));
     if (c->opt_det && !c->logp_rows) DALLOC(c, c->logp_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
-    (lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, bwd ? c->dLog : nullptr, c->ldV,
-                                                    c->opt_det ? c->logp_rows : nullptr);
+    void *const dlog = bwd ? c->dLog : nullptr;
+    double *const rows = c->opt_det ? c->logp_rows : nullptr;
+    if (row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
+    else (lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows);
     c->last_norm = norm_B;
     c->last_S = S;
     c->last_tokens = lens ? norm_tokens : 0;
@@ -432,29 +446,32 @@ int lrcn_impl::fetch_loss(lrcn_ctx *c, double *out) {
 
 namespace {
 
-// The body of the four lrcn_loss* entry points.  var: the variable-length form, whose lens must be given (the other passes NULL);
-// grads NULL: the loss alone.
+// The body of the lrcn_loss* entry points.  var: the variable-length form, whose lens must be given (the other passes NULL);
+// weighted: that form with row_w, which must be given too; grads NULL: the loss alone.
 int loss_entry(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, bool var, const int32_t *lens, int T, int B,
-               int norm_B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host) {
+               int norm_B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host, bool weighted = false,
+               const float *row_w = nullptr) {
     DeviceGuard dg(c);
     if (!c || !p || !feats || (!tokens && T > 0)) return LRCN_EINVAL;
     if (var && !lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
-    int r = loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, nullptr, lens, norm_tokens);
+    if (weighted && !row_w) FAIL(c, LRCN_EINVAL, "row_w is NULL");
+    int r = loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, nullptr, lens, norm_tokens, row_w);
     if (r) return r;
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
 }
 
-// The body of the four lrcn_train_step* entry points: lossgradient, then update! -- with max_norm > 0 on the gradient clipped to that
+// The body of the lrcn_train_step* entry points: lossgradient, then update! -- with max_norm > 0 on the gradient clipped to that
 // global norm (the nine sums of squares, norm / scale / skip and the clipped update, all on the context's stream).
 int train_step_impl(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                     const int32_t *tokens, bool var, const int32_t *lens, int T, int B, int norm_B, int64_t norm_tokens,
-                    const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
+                    const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host,
+                    bool weighted = false, const float *row_w = nullptr) {
     DeviceGuard dg(c);
     if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
     if (std::isnan(max_norm)) FAIL(c, LRCN_EINVAL, "max_norm is NaN");
     const bool clip = max_norm > 0.0f;
     if (clip && step < 1) return LRCN_EINVAL;  // (the unclipped step finds a bad `step` in its update, after the pass)
-    int r = loss_entry(c, p, feats, tokens, var, lens, T, B, norm_B, norm_tokens, drop, g, nullptr);
+    int r = loss_entry(c, p, feats, tokens, var, lens, T, B, norm_B, norm_tokens, drop, g, nullptr, weighted, row_w);
     if (r) return r;
     if (clip) {
         r = lrcn_grad_sumsq_model(c, g, -1, nullptr);
@@ -542,6 +559,26 @@ int lrcn_train_step_var_clip(lrcn_ctx *c, float *const p[9], float *const g[9], 
                              const int32_t *tokens, const int32_t *lens, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop,
                              int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
     return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host);
+}
+
+// ---- include/lrcn_weighted.h: a real weight per caption row ----
+int lrcn_loss_w(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, const float *row_w,
+                int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, double *loss_host) {
+    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, nullptr, loss_host, true, row_w);
+}
+
+int lrcn_loss_grad_w(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens,
+                     const float *row_w, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9],
+                     double *loss_host) {
+    if (!grads) return LRCN_EINVAL;
+    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, grads, loss_host, true, row_w);
+}
+
+int lrcn_train_step_w(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                      const int32_t *tokens, const int32_t *lens, const float *row_w, int T, int B, int64_t norm_tokens,
+                      const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
+    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host,
+                           true, row_w);
 }
 
 }  // extern "C"

@@ -145,9 +145,9 @@ class HipOps:
     def set_vgg_wg_cap(self, cap):
         self.ctx._call("lrcn_vgg_set_wg_cap", int(cap))
 
-    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None):
+    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None, row_weights=None):
         L.lossgradient(self.ctx, param, feats, tokens, norm_B=norm_B, pdrop=pdrop, seed=seed, grads=grads,
-                       want_loss=False, lens=lens, norm_tokens=norm_tokens)
+                       want_loss=False, lens=lens, norm_tokens=norm_tokens, row_weights=row_weights)
 
     def update(self, param, grads, optim, clipped=False):
         L.update(self.ctx, param, grads, optim, clipped=clipped)
@@ -645,7 +645,7 @@ class DataParallelTrainer:
             return staged
         return self.ops.upload(img)
 
-    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None):
+    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None, row_weights=None):
         """One synchronous-SGD step on this rank's shard.  img_u8: this rank's uint8 crops (or feats given);
         next_img_u8: the crops of the NEXT step(s), whose VGG forward runs beside this step's LSTM work and all-reduce.
         img_u8 is IGNORED when an earlier step() already produced this batch's features through its next_img_u8.
@@ -664,7 +664,12 @@ class DataParallelTrainer:
 
         lens: this rank's rows are a padded batch (include/lrcn_varlen.h) of these caption lengths; norm_tokens: the GLOBAL batch's
         sum(lens + 1), which every rank computes from the full batch (train.shard_block) -- one rank may leave it out.  The ranks'
-        gradients then sum to the single-device gradient, as with B_global for equal lengths.  Not with the "abi" backend."""
+        gradients then sum to the single-device gradient, as with B_global for equal lengths.  Not with the "abi" backend.
+
+        row_weights (with lens): a real weight for each of this rank's rows (include/lrcn_weighted.h).  The weights act only inside the
+        loss kernel and norm_tokens stays the global count, so the ranks' gradients sum to the single-device gradient in every mode."""
+        if row_weights is not None and lens is None:
+            raise L.LrcnError("row_weights needs lens")
         rows = int(tokens.shape[1])
         self._cur_M = (int(tokens.shape[0]) + 1) * rows
         if feats is None:
@@ -710,7 +715,8 @@ class DataParallelTrainer:
                 if self.world > 1:
                     raise L.LrcnError("a padded batch over %d ranks needs the global batch's token count (norm_tokens)" % self.world)
                 norm_tokens = int(np.asarray(lens, dtype=np.int64).sum()) + len(lens)
-            self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens))
+            kw = {} if row_weights is None else {"row_weights": row_weights}   # (an ops stand-in without the keyword keeps working)
+            self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens), **kw)
         else:
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)
         if self.gclip > 0 and not self._dev_clip:

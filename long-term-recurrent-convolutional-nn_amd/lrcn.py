@@ -169,6 +169,16 @@ def _lens(lens, T, B, norm_tokens):
     return a, a.ctypes.data_as(C.POINTER(C.c_int32)), C.c_int64(n)
 
 
+def _row_weights(row_weights, lens, B):
+    """Per-row loss weights of the weighted calls (include/lrcn_weighted.h) -> (host float32 array, its ctypes pointer)."""
+    if lens is None:
+        raise LrcnError("row_weights needs lens (the weighted calls take padded batches; equal lengths: lens[b] = T)")
+    a = np.ascontiguousarray(np.asarray(row_weights.detach().cpu() if torch.is_tensor(row_weights) else row_weights, dtype=np.float32).reshape(-1))
+    if a.shape[0] != B:
+        raise LrcnError("row_weights has %d entries, the batch has %d rows" % (a.shape[0], B))
+    return a, a.ctypes.data_as(C.POINTER(C.c_float))
+
+
 # ------------------------------------------------------------------------------------------------ model
 def initweights(ctx, seed=42):
     """initweights(atype, hidden, vocab, embed) (lrcn.jl:489-510) -> list of 9 column-major tensors."""
@@ -220,15 +230,23 @@ def lrcn(ctx, w, s, x_cnn, x_lstm, mask1=None, mask2=None):
     return logits
 
 
-def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None):
+def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None):
     """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
     tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
     lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
-    norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used."""
+    norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used.
+    row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h)."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
+    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if wa is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        ctx._call("lrcn_loss_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
+                  C.byref(out))
+        del keep, la, wa
+        return out.value
     if lens is not None:
         la, lp, nt = _lens(lens, T, B, norm_tokens)
         ctx._call("lrcn_loss_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None, C.byref(out))
@@ -241,14 +259,22 @@ def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, 
 
 
 def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
-                 want_loss=True, lens=None, norm_tokens=None):
-    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens: as loss()."""
+                 want_loss=True, lens=None, norm_tokens=None, row_weights=None):
+    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights:
+    as loss()."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
+    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     if grads is None:
         grads = [jl_empty(*t.shape) for t in param]
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if wa is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        ctx._call("lrcn_loss_grad_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
+                  _p9(grads), C.byref(out) if want_loss else None)
+        del keep, la, wa
+        return grads, (out.value if want_loss else None)
     if lens is not None:
         la, lp, nt = _lens(lens, T, B, norm_tokens)
         ctx._call("lrcn_loss_grad_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None,
@@ -356,17 +382,24 @@ def refresh_shadows_group(ctx, param, group, stream=None):
 
 
 def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None,
-               gclip=0.0):
-    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens: as loss().
+               gclip=0.0, row_weights=None):
+    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights: as loss().
     gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h; clip_stats() has the counters)."""
     gclip = float(gclip or 0.0)
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     d, keep = _dropout(pdrop, seed, None, None)
-    la = _lens(lens, T, B, norm_tokens) if lens is not None else None   # checked before the step counter moves
+    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None   # both checked before the step counter moves
+    la = _lens(lens, T, B, norm_tokens) if lens is not None else None
     optim.t += 1
     out = C.c_double()
     clip = (gclip,) if gclip > 0 else ()
+    if wa is not None:
+        ctx._call("lrcn_train_step_w", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()), la[1],
+                  wa[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps, gclip,
+                  C.byref(out) if want_loss else None)
+        del keep, la, wa
+        return out.value if want_loss else None
     if la is not None:
         ctx._call("lrcn_train_step_var_clip" if clip else "lrcn_train_step_var", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v),
                   _ptr(feats), C.c_void_p(tok.data_ptr()), la[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1,

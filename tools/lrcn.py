@@ -87,6 +87,12 @@ def build_parser():
     p.add_argument("--varlen", action="store_true",
                    help="--train: padded batches of mixed caption lengths (include/lrcn_varlen.h) for the training and the evaluation splits: the "
                         "length-sorted captions cut into windows of --batchsize, none dropped, no forced batch 10 (needs --features)")
+    p.add_argument("--scst", action="store_true",
+                   help="--train: self-critical training on the model's own samples with a CIDEr-D reward (lrcn_amd/scst.py); needs --loadfile")
+    p.add_argument("--scst_samples", type=int, default=5, help="--scst: samples per image; a step takes batchsize // scst_samples images")
+    p.add_argument("--scst_baseline", default="greedy", choices=["greedy", "mean"],
+                   help="--scst: the reward a sample is compared with -- the greedy caption's, or the mean of the image's other samples")
+    p.add_argument("--scst_nword", type=int, default=20, help="--scst: sampled captions have at most this many words")
     p.add_argument("--no_normalize", action="store_true", help="--cnn --train: do not divide fc7 features by their sum (lrcn.jl:595-597 does)")
     return p
 
@@ -115,6 +121,10 @@ def main(argv=None):
     o = build_parser().parse_args(argv)
     if o.varlen and not o.train:
         raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
+    if o.scst and not o.train:
+        raise SystemExit("--scst is a mode of the TRAINING job (--train)")
+    if o.scst and not o.loadfile:
+        raise SystemExit("--scst starts from a trained model: give --loadfile (train with cross-entropy first)")
     world_env = os.environ.get("WORLD_SIZE")
     if o.gpus > 1 and world_env is None:   # before any torch / HIP import: this parent only starts the ranks and passes their output on
         if not o.train:
@@ -174,6 +184,8 @@ def main(argv=None):
         raise SystemExit("--hidden takes two sizes, the second even (LRCN-2f, lrcn.jl:496-504)")
     H1, H2 = o.hidden
     gen_chunk = 256  # images decoded together by the batched beam search (1280 hypothesis rows at beam 5: the decode GEMMs fill the chip)
+    if o.scst and not 1 <= o.scst_nword < L._lib.MAX_T:
+        raise SystemExit("--scst_nword must be in [1, %d]" % (L._lib.MAX_T - 1))
     ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, (o.sample or o.beam_width) * (gen_chunk if o.generate > 0 or o.retrieval else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
                     max_images=max(o.batchsize, 256 if o.train else 1) if o.cnn else 0)   # training: room for the crops of several batches per forward
     param = L.initweights(ctx, seed=o.seed if o.seed > 0 else 42) if host_model is None else L.model_from_arrays(host_model)
@@ -333,6 +345,58 @@ def main(argv=None):
         return 0
 
     # ---------------------------------------------------------------- train! (lrcn.jl:223-246) on dp.DataParallelTrainer
+    if lists and o.train and o.scst:
+        from lrcn_amd import scst
+        from lrcn_amd.cider import CiderD
+        if o.dp_backend == "abi" and world > 1:
+            raise SystemExit("--scst needs --dp_backend torch")
+        if not feats:
+            raise SystemExit("--scst trains on precomputed features (--features)")
+        S = o.scst_samples
+        per_step = o.batchsize // max(S, 1) // world     # images per rank and step
+        if S < 1 or per_step < 1 or (o.scst_baseline == "mean" and S < 2):
+            raise SystemExit("--scst: batchsize // scst_samples images per step (at least one per rank); the mean baseline needs 2 samples")
+        tables = [feats[0], feats[min(1, len(feats) - 1)]]
+        refs = scst.references_by_image(lists[0], vocab)
+        reward = scst.cider_reward(CiderD(refs), idx2word)
+        ids = [i for i in refs if i in tables[0]]
+        mine = ids[rank::world][:len(ids) // world]       # the same count on every rank
+        dev = None
+        if len(lists) > 1:
+            dev_refs = scst.references_by_image(lists[1], vocab)
+            dev = (CiderD(dev_refs), [i for i in dev_refs if i in tables[1]])
+        say("scst: %d images with references, %d per step on %d rank%s, %d samples each, baseline %s"
+            % (len(ids), per_step * world, world, "" if world == 1 else "s", S, o.scst_baseline))
+        optim = L.initparams(param)
+        optim.lr = o.lr
+        seed = o.seed if o.seed > 0 else 0
+        trainer = dp.DataParallelTrainer(ctx, param, optim, per_step * S * world, world, rank, pdrop=o.dropout, seed=seed, backend="torch",
+                                         ops=dp.HipOps(ctx, mean=mean), shard_adam=bool(o.shard_adam) and world > 1, gclip=o.gclip)
+        if adam_state is not None:
+            trainer.restore(adam=(adam_state["m"], adam_state["v"], adam_state["step"]))
+        import time
+        for epoch in range(1, o.epochs + 1):
+            t0 = time.time()
+            rs, rg, steps, seen = scst.train_epoch(trainer, mine, lambda part: feature_rows(tables[0], part), reward, per_step, S, o.scst_nword,
+                                                   seed + rank, epoch, temperature=o.temperature, top_k=o.topk, top_p=o.topp,
+                                                   baseline=o.scst_baseline)
+            ctx.sync()
+            dt_s = time.time() - t0
+            if o.savefile:
+                trainer.gather_optim_state()
+                if rank == 0:
+                    fmt.save_checkpoint(o.savefile, [L.from_jl(p) for p in param], vocab,
+                                        adam={"m": [L.from_jl(t) for t in optim.m], "v": [L.from_jl(t) for t in optim.v], "step": optim.t})
+            line = "(:epoch, %d, :scst_reward, %.4f, :greedy_reward, %s" % (epoch, rs, "%.4f" % rg if rg is not None else "nothing")
+            if dev is not None and rank == 0:
+                line += ", :dev_cider, %.4f" % scst.beam_cider(ctx, param, dev[0], dev[1], lambda part: feature_rows(tables[1], part), idx2word,
+                                                                o.beam_width, o.scst_nword)
+            say(line + ")  [%d steps, %.0f images/s on %d rank%s]" % (steps, seen * world / max(dt_s, 1e-9), world, "" if world == 1 else "s"))
+        trainer.close()
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
     if lists and o.train:
         say("Batching starts")
         if o.varlen:
