@@ -19,6 +19,7 @@ ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_act
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
 CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
 WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
+SCHED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sched.h"))        # lrcn_*_sched (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
@@ -54,6 +55,10 @@ class GemmDebug(C.Structure):   # lrcn_gemm_debug of include/lrcn_gemm_debug.h
 
 class Dropout(C.Structure):
     _fields_ = [("pdrop", C.c_float), ("seed", C.c_uint64), ("mask1", C.c_void_p), ("mask2", C.c_void_p)]
+
+
+class Sched(C.Structure):   # lrcn_sched of include/lrcn_sched.h
+    _fields_ = [("eps", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64), ("row0", C.c_int64)]
 
 
 P9 = C.c_void_p * 9
@@ -207,6 +212,18 @@ WEIGHTED_SIGNATURES = {
                                     C.POINTER(C.c_double)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_sched.h declares (bound by lib() as well)
+SCHED_SIGNATURES = {
+    "lrcn_loss_sched": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int64,
+                                  C.POINTER(Dropout), C.POINTER(Sched), C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "lrcn_loss_grad_sched": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                       C.c_int64, C.POINTER(Dropout), C.POINTER(Sched), P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
+    "lrcn_train_step_sched": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                        C.c_int, C.c_int64, C.POINTER(Dropout), C.POINTER(Sched), C.c_int, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.POINTER(C.c_double)]),
+    "lrcn_sched_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+}
+
 
 class ClipStats(C.Structure):
     """lrcn_clip_stats_t (include/lrcn_clip.h)."""
@@ -242,7 +259,7 @@ GEMM_DEBUG_SIGNATURES = {
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, GEMM_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -263,7 +280,8 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(GEMM_DEBUG_SIGNATURES.items()):
+                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
+                list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

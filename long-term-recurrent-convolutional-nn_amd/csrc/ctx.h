@@ -7,6 +7,7 @@
 
 #include "comm.h"
 #include "host.h"
+#include "../../include/lrcn_sched.h"
 
 namespace lrcn_impl {
 
@@ -103,6 +104,7 @@ struct lrcn_ctx {
     float *roww_dev = nullptr, *roww_pin = nullptr;
     hipEvent_t roww_up[kLenSlots] = {};
     int roww_slot = 0;
+    long long *sched_cnt = nullptr;  // include/lrcn_sched.h, lazily: {coins taken, coins fired} of the most recent scheduled-sampling call
     int cur_B = 0;  // rows of the loss / lossgradient call in flight (gemm() picks its "beside the convolutions" hint by it)
     // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
     float *st_f32[4] = {nullptr, nullptr, nullptr, nullptr};   // h1,c1,h2,c2 [B][H]
@@ -253,10 +255,11 @@ void set_create_error(const char *msg);
 // lrcn() on the context's single-step buffers (lrcn_api.hip): lrcn_step and the single-image beam search
 int step_internal(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2, bool h_ready = false);
 // loss / lossgradient on the context's buffers (train.hip): grads NULL = forward only, lens != NULL = the variable-length form,
-// row_w != NULL (host [B], with lens) = that form with a weight per caption (include/lrcn_weighted.h)
+// row_w != NULL (host [B], with lens) = that form with a weight per caption (include/lrcn_weighted.h), ss != NULL (with lens) = scheduled
+// sampling (include/lrcn_sched.h; eps > 0: the stepwise forward), fed_out (device [T+1][B], with ss, may be NULL) = the words that were fed
 int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
               const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens = nullptr, int64_t norm_tokens = 0,
-              const float *row_w = nullptr);
+              const float *row_w = nullptr, const lrcn_sched *ss = nullptr, int32_t *fed_out = nullptr);
 // waits for the context's stream; the last loss call's mean loss into *out (NULL: only the out-of-range-token check) (train.hip)
 int fetch_loss(lrcn_ctx *c, double *out);
 // f32 column-major params -> K-contiguous shadows in T (update.hip; see DESIGN.md "shadow weights")

@@ -98,26 +98,33 @@ inline bool lstm_fused_on(int dtype, int B, int H, int64_t ldH, int64_t ld4H) {
 // recurrent GEMM `gemm(A, lda, B, ldb, C, ldc, M, N, K, beta, c_is_zero)` (C f32 (+)= A B', no bias) and the cell kernel.  Gx f32 [S*B][4H]
 // holds the input-side pre-activations (+bias) on entry and the full pre-activations on exit; acts (T) [S*B][ld4H], Call f32 [S*B][H] and
 // Hall (T) [S*B][ldH] receive the per-step results (lrcn.jl:528-538, time-batched).  The caller checks the launches (KCHK).
+// Step s of that recurrence alone (`fused`: lstm_fused_on of the layer): rows [s*B, (s+1)*B) of Gx hold the step's input-side pre-activations,
+// steps < s are complete.  lstm_recurrence_fwd's loop body, and what the stepwise forward of scheduled sampling (train.hip) calls per step.
+template <class Handle, class Gemm>
+int lstm_step_fwd(Handle *h, bool alone, const Gemm &gemm, bool fused, int s, int B, int H, int64_t ldH, int64_t ld4H, float *Gx,
+                  const void *Wh, void *acts, float *Call, void *Hall) {
+    float *G = Gx + (int64_t)s * B * 4 * H;
+    if (s > 0 && fused) {  // recurrent GEMM + cell in one launch (small batches: launch-latency bound otherwise)
+        hipError_t e = launch_lstm_rec_fwd(h->stream, boff(Hall, (int64_t)(s - 1) * B * ldH, h->esz), ldH, Wh, G,
+                                           Call + (int64_t)(s - 1) * B * H, B, H, boff(acts, (int64_t)s * B * ld4H, h->esz), ld4H,
+                                           Call + (int64_t)s * B * H, boff(Hall, (int64_t)s * B * ldH, h->esz), h->zero_page, alone);
+        if (e != hipSuccess) FAIL(h, LRCN_EHIP, "lstm_rec_fwd: %s", hipGetErrorString(e));
+        return LRCN_OK;
+    }
+    if (s > 0)
+        if (int rg = gemm(boff(Hall, (int64_t)(s - 1) * B * ldH, h->esz), ldH, Wh, ldH, G, 4 * H, B, 4 * H, H, true, false)) return rg;
+    k_lstm_fwd(h->stream, h->dt, G, 4 * H, s ? Call + (int64_t)(s - 1) * B * H : nullptr, B, H,
+               boff(acts, (int64_t)s * B * ld4H, h->esz), ld4H, Call + (int64_t)s * B * H,
+               boff(Hall, (int64_t)s * B * ldH, h->esz), ldH, nullptr);
+    return LRCN_OK;
+}
+
 template <class Handle, class Gemm>
 int lstm_recurrence_fwd(Handle *h, bool alone, const Gemm &gemm, int S, int B, int H, int64_t ldH, int64_t ld4H, float *Gx, const void *Wh,
                         void *acts, float *Call, void *Hall) {
-    const int dt = h->dt;
-    const bool fused = lstm_fused_on(dt, B, H, ldH, ld4H);
-    for (int s = 0; s < S; ++s) {
-        float *G = Gx + (int64_t)s * B * 4 * H;
-        if (s > 0 && fused) {  // recurrent GEMM + cell in one launch (small batches: launch-latency bound otherwise)
-            hipError_t e = launch_lstm_rec_fwd(h->stream, boff(Hall, (int64_t)(s - 1) * B * ldH, h->esz), ldH, Wh, G,
-                                               Call + (int64_t)(s - 1) * B * H, B, H, boff(acts, (int64_t)s * B * ld4H, h->esz), ld4H,
-                                               Call + (int64_t)s * B * H, boff(Hall, (int64_t)s * B * ldH, h->esz), h->zero_page, alone);
-            if (e != hipSuccess) FAIL(h, LRCN_EHIP, "lstm_rec_fwd: %s", hipGetErrorString(e));
-            continue;
-        }
-        if (s > 0)
-            if (int rg = gemm(boff(Hall, (int64_t)(s - 1) * B * ldH, h->esz), ldH, Wh, ldH, G, 4 * H, B, 4 * H, H, true, false)) return rg;
-        k_lstm_fwd(h->stream, dt, G, 4 * H, s ? Call + (int64_t)(s - 1) * B * H : nullptr, B, H,
-                   boff(acts, (int64_t)s * B * ld4H, h->esz), ld4H, Call + (int64_t)s * B * H,
-                   boff(Hall, (int64_t)s * B * ldH, h->esz), ldH, nullptr);
-    }
+    const bool fused = lstm_fused_on(h->dt, B, H, ldH, ld4H);
+    for (int s = 0; s < S; ++s)
+        if (int r = lstm_step_fwd(h, alone, gemm, fused, s, B, H, ldH, ld4H, Gx, Wh, acts, Call, Hall)) return r;
     return LRCN_OK;
 }
 

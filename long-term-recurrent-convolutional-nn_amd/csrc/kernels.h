@@ -55,8 +55,9 @@ void k_lstm_bwd(hipStream_t st, int dtype, const void *acts, int64_t ld_a, const
 
 // X2[m][j<nl] *= mask ; X2[m][nl+j] = xcnn[b][j] * mask (j < nr); mask over nl+nr columns      (lrcn.jl:546-547: nl = nr = h;
 // LRCN-1f: nl = E, nr = h)
+// s0: the step of x2's first row block (the multipliers are those of steps s0 .. s0 + S - 1; the stepwise forward of scheduled sampling)
 void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B,
-                 int nl, int nr, DropSpec d);
+                 int nl, int nr, DropSpec d, int s0 = 0);
 
 // Row-wise log-softmax + target pick + (optional) dlogits = (softmax - onehot) * scale   (lrcn.jl:562-567 and dual).
 // logits f32 [M][ld_l]; accumulates sum of log p(target) into *logp_sum (double).  dlog (T) may be NULL.
@@ -122,6 +123,30 @@ bool k_embed_scatter_rm(hipStream_t st, const float *dxemb, int64_t ld_dx, const
                         float *stage, int64_t ld_s, float *dwembed, unsigned long long *sort_keys);
 // the rows of dXemb (dropout multiplier applied) E-contiguous into out [S*B][E]: a rank's share of the sparse embedding-gradient exchange
 void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out);
+
+// Scheduled sampling (include/lrcn_sched.h): the input of step s_next, decided and gathered after step s_next - 1's logits.
+struct SchedNext {
+    const float *logits;   // f32 [B][ld_l]: the logits rows of step s_next - 1
+    int64_t ld_l;
+    int V, B, s_next;
+    const int32_t *lens;   // device [B]
+    float eps, temp;
+    uint32_t k0, k1;       // seed & 0xffffffff, seed >> 32
+    uint32_t row0;         // (uint32) index of row 0 in the global batch
+    int32_t *tok_in;       // [(T+1) B]: row s_next*B + b holds the gold word (eos past the row's end) and receives a drawn one
+    const void *wembT;     // T [V][ld_w]
+    int64_t ld_w;
+    int E;
+    DropSpec d;            // the multipliers of the gather (step s_next), or none
+    void *xemb;            // T [(T+1) B][ld_x]: row s_next*B + b is written
+    int64_t ld_x;
+    long long *cnt;        // [2]: += coins taken, += coins fired
+};
+// One 256-thread workgroup per row b: past the row's end the eos row is gathered; else the coin is taken and, only where it fires, the
+// logits row is read (staged in LDS up to V = 15360) and the word drawn as k_sample_rows draws with top_k = 0.
+void k_sched_next_input(hipStream_t st, int dtype, const SchedNext &a);
+// cnt[0] = eligible, cnt[1] = drawn (the counters of lrcn_sched_stats at the start of a call)
+void k_sched_stats_set(hipStream_t st, long long *cnt, long long eligible, long long drawn);
 
 // dX2[m][j] *= mask (all nl+nr columns, in place);  dxcnn[b][j] = sum_s dX2[s*B+b][nl+j]
 void k_dx2_mask_reduce(hipStream_t st, int dtype, void *dx2, int64_t ld, int S, int B, int nl, int nr, DropSpec d,

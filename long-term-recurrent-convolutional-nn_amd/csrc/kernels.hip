@@ -79,9 +79,9 @@ __global__ void lstm_bwd_kernel(const T *acts, int64_t ld_a, const float *c_prev
 }
 
 template <typename T>
-__global__ void concat_x2_kernel(T *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B, int nl, int nr, DropSpec d) {
+__global__ void concat_x2_kernel(T *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B, int nl, int nr, DropSpec d, int s0) {
     const int m = blockIdx.x;
-    const int s = m / B, b = m - s * B;
+    const int sl = m / B, b = m - sl * B, s = s0 + sl;
     T *row = x2 + (int64_t)m * ld_x2;
     for (int j = threadIdx.x; j < nl + nr; j += blockDim.x) {
         const float v = (j < nl) ? to_f32(row[j]) : xcnn[(int64_t)b * ld_xc + (j - nl)];
@@ -389,9 +389,9 @@ void k_lstm_bwd(hipStream_t st, int dtype, const void *acts, int64_t ld_a, const
                                          c_prev, c_new, dh_a, ld_dha, dh_b, dh_b_read, dc, dc_zero, B, H, (T *)dz, ld_dz, nslab));
 }
 void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B, int nl, int nr,
-                 DropSpec d) {
+                 DropSpec d, int s0) {
     DISPATCH_T(dtype, hipLaunchKernelGGL(concat_x2_kernel<T>, dim3(S * B), dim3(256), 0, st, (T *)x2, ld_x2, xcnn, ld_xc, S,
-                                         B, nl, nr, d));
+                                         B, nl, nr, d, s0));
 }
 namespace {
 template <bool MASKED, bool WEIGHTED = false>  // WEIGHTED: the masked form with per-caption weights row_w [B] (device)

@@ -11,7 +11,7 @@
 
 #include "common.h"
 #include "gemm.h"
-#include "philox.h"
+#include "draw.h"
 
 namespace {
 
@@ -26,36 +26,6 @@ __device__ __forceinline__ void sample_commit(const SampleState &s, int r, int t
         s.len[r] = s.current + 1;
         atomicAdd(s.ndone, 1);
     }
-}
-
-// (score, column) pairs: larger score first, lower column in a tie
-__device__ __forceinline__ bool beats(float a, int ai, float b, int bi) { return a > b || (a == b && ai < bi); }
-__device__ __forceinline__ void wave_best(float &v, int &i) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o);
-        const int oi = __shfl_xor(i, o);
-        if (beats(ov, oi, v, i)) { v = ov; i = oi; }
-    }
-}
-// block-wide best pair (256 threads); every thread gets the result
-__device__ __forceinline__ void block_best(float &v, int &i, float *shv, int *shi) {
-    wave_best(v, i);
-    const int w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { shv[w] = v; shi[w] = i; }
-    __syncthreads();
-    v = shv[0]; i = shi[0];
-    for (int q = 1; q < 4; ++q)
-        if (beats(shv[q], shi[q], v, i)) { v = shv[q]; i = shi[q]; }
-}
-__device__ __forceinline__ float block_reduce(float v, float *sh, bool is_max) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = is_max ? fmaxf(v, __shfl_xor(v, o)) : v + __shfl_xor(v, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return is_max ? fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) : (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 __global__ void sample_init_kernel(SampleState s, int R, int bos) {
@@ -84,13 +54,7 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float *logits, i
     if (s.done[r]) return;   // block-uniform
     const float *g = logits + (int64_t)r * ld;
     const float *z = stage ? srow : g;
-    float m = -INFINITY;
-    for (int j = tid; j < V; j += 256) {
-        const float x = g[j];
-        if (stage) srow[j] = x;
-        m = fmaxf(m, x);
-    }
-    m = block_reduce(m, shf, true);   // (its barriers also publish srow)
+    const float m = row_max_stage(g, V, stage, srow, shf);   // (its barriers also publish srow)
     float se = 0.0f;
     for (int j = tid; j < V; j += 256) se += __expf(z[j] - m);
     se = block_reduce(se, shf, false);
@@ -111,33 +75,10 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float *logits, i
     }
     const float thr = temp > 0.0f ? m - GUMBEL_PRUNE * temp : m;
     const uint32_t si = (uint32_t)(r % S), ii = (uint32_t)(r / S);
-    float bs = -INFINITY, bz = -INFINITY;
-    int bc = 0x7FFFFFFF;
-    for (int q = tid; 4 * q < V; q += 256) {
-        float x[4];
-        bool ok[4], any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int j = 4 * q + k;
-            x[k] = j < V ? z[j] : -INFINITY;
-            ok[k] = j < V && x[k] >= thr && (top_k == 0 || x[k] > tv || (x[k] == tv && j <= tc));
-            any |= ok[k];
-        }
-        if (!any) continue;
-        if (temp > 0.0f) {
-            const Philox4 rnd = philox4x32_10((uint32_t)q, (uint32_t)s.current, si, ii, k0, k1);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k]) {
-                    const float sc = x[k] / temp + gumbel_of(rnd.x[k]);
-                    if (beats(sc, 4 * q + k, bs, bc)) { bs = sc; bc = 4 * q + k; bz = x[k]; }
-                }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k] && beats(x[k], 4 * q + k, bs, bc)) { bs = x[k]; bc = 4 * q + k; bz = x[k]; }
-        }
-    }
+    float bs, bz;
+    int bc;
+    gumbel_argmax(z, V, temp, thr, (uint32_t)s.current, si, ii, k0, k1,
+                  [&](float x, int j) { return top_k == 0 || x > tv || (x == tv && j <= tc); }, bs, bc, bz);
     float wv = bs;
     int wc = bc;
     block_best(wv, wc, shv, shi);
@@ -331,13 +272,7 @@ __global__ __launch_bounds__(256) void sample_nucleus_kernel(NucleusArgs a, Samp
     const float *g = a.logits + (int64_t)r * a.ld;
     const float *z = a.stage ? srow : g;
     const float temp = a.temp;
-    float m = -INFINITY;
-    for (int j = tid; j < V; j += 256) {
-        const float x = g[j];
-        if (a.stage) srow[j] = x;
-        m = fmaxf(m, x);
-    }
-    m = block_reduce(m, shf, true);   // (its barriers also publish srow)
+    const float m = row_max_stage(g, V, a.stage, srow, shf);   // (its barriers also publish srow)
     float se = 0.0f;
     for (int j = tid; j < V; j += 256) se += __expf(z[j] - m);
     se = block_reduce(se, shf, false);
@@ -421,33 +356,9 @@ __global__ __launch_bounds__(256) void sample_nucleus_kernel(NucleusArgs a, Samp
     const float thr = temp > 0.0f ? m - GUMBEL_PRUNE * temp : m;
     const int current = s.seq ? s.current : a.current;
     const uint32_t si = (uint32_t)(r % a.S), ii = (uint32_t)(r / a.S);
-    float bs = -INFINITY, bz = -INFINITY;
-    int bc = 0x7FFFFFFF;
-    for (int q = tid; 4 * q < V; q += 256) {
-        float x[4];
-        bool ok[4], any = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int j = 4 * q + k;
-            x[k] = j < V ? z[j] : -INFINITY;
-            ok[k] = j < V && x[k] >= thr && in_cut(okey(x[k]), j, cut);
-            any |= ok[k];
-        }
-        if (!any) continue;
-        if (temp > 0.0f) {
-            const Philox4 rnd = philox4x32_10((uint32_t)q, (uint32_t)current, si, ii, a.k0, a.k1);
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k]) {
-                    const float sc = x[k] / temp + gumbel_of(rnd.x[k]);
-                    if (beats(sc, 4 * q + k, bs, bc)) { bs = sc; bc = 4 * q + k; bz = x[k]; }
-                }
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (ok[k] && beats(x[k], 4 * q + k, bs, bc)) { bs = x[k]; bc = 4 * q + k; bz = x[k]; }
-        }
-    }
+    float bs, bz;
+    int bc;
+    gumbel_argmax(z, V, temp, thr, (uint32_t)current, si, ii, a.k0, a.k1, [&](float x, int j) { return in_cut(okey(x), j, cut); }, bs, bc, bz);
     float wv = bs;
     int wc = bc;
     block_best(wv, wc, shv, shi);

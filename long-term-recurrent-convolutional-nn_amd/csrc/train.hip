@@ -19,6 +19,7 @@
 #include "../../include/lrcn_varlen.h"
 #include "../../include/lrcn_clip.h"
 #include "../../include/lrcn_weighted.h"
+#include "../../include/lrcn_sched.h"
 
 using namespace lrcn_impl;
 
@@ -204,11 +205,22 @@ int upload_row_w(lrcn_ctx *c, const float *w, int B) { return upload_rows(c, w, 
 // 1 / norm_tokens and norm_B is not used.  Only the token builder and the softmax-NLL kernel differ; every launch in between is the same.
 // row_w != NULL (host, [B], with lens): the weighted form of include/lrcn_weighted.h -- caption b's terms and d(logits) rows carry
 // row_w[b]; the chain after the softmax-NLL kernel is linear in d(logits), so only that launch differs.
+// ss != NULL (with lens): scheduled sampling of include/lrcn_sched.h.  eps == 0 changes nothing but the counters and fed_out; eps > 0 runs
+// the forward step by step (sched_forward below) into the same buffers and rejoins at the softmax-NLL launch.
 int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
                          const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens, int64_t norm_tokens,
-                         const float *row_w) {
+                         const float *row_w, const lrcn_sched *ss, int32_t *fed_out) {
     int r = check_shapes(c, T, B, norm_B);
     if (r) return r;
+    if (ss) {
+        if (!lens) FAIL(c, LRCN_EINVAL, "scheduled sampling needs lens");
+        if (!(ss->eps >= 0.0f && ss->eps <= 1.0f)) FAIL(c, LRCN_EINVAL, "sched eps=%g outside [0,1]", (double)ss->eps);
+        if (!(ss->temperature >= 0.0f) || std::isinf(ss->temperature))
+            FAIL(c, LRCN_EINVAL, "sched temperature=%g must be finite and >= 0", (double)ss->temperature);
+        if (ss->row0 < 0 || ss->row0 > ((int64_t)1 << 32) - B)
+            FAIL(c, LRCN_EINVAL, "sched row0=%lld: rows [row0, row0 + B) must lie in [0, 2^32)", (long long)ss->row0);
+    }
+    const bool stepwise = ss && ss->eps > 0.0f;
     if (lens) {
         if (norm_tokens < 1) FAIL(c, LRCN_EINVAL, "norm_tokens=%lld must be >= 1", (long long)norm_tokens);
         for (int b = 0; b < B; ++b)
@@ -232,7 +244,7 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     const DropSpec none{};
 
     c->cur_B = B;
-    const bool epi = lstm_epi_on(c, B) && !lstm_fused_on(c->dt, B, H1, c->ldH1, c->ld4H1);
+    const bool epi = !stepwise && lstm_epi_on(c, B) && !lstm_fused_on(c->dt, B, H1, c->ldH1, c->ld4H1);  // (no cell epilogues in the stepwise forward)
     r = prepare_weights(c, p, bwd, false, epi);
     if (r) return r;
     if (lens) {
@@ -248,14 +260,68 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     // there a second stream of LSTM-side workgroups takes CUs from the convolutions); LRCN_WG_STREAM=0 / 1 forces it off / on.
     const bool beside_vgg = !lstm_alone(c) && B >= kBgMinRows;
     const bool par = knob_set("LRCN_WG_STREAM") ? !knob_off("LRCN_WG_STREAM") : !beside_vgg;  // the weight-gradient stream is in use
-    const bool xfork = two && par;
+    const bool xfork = two && par && !stepwise;
     auto image_embedding = [&](hipStream_t s_, bool on_wg) -> int {
         // feats (B x 4096 column-major = memory [4096][B]) -> F [B][4096] (T)
         k_transpose(s_, dt, 1, feats, B, LRCN_CNNOUT, B, c->F, LRCN_CNNOUT, 0);
         return gemm(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->xcnn, c->ldh, B, h, LRCN_CNNOUT, nullptr, true, false, false, false, on_wg);
     };
+    if (ss) {
+        if (!c->sched_cnt) DALLOC(c, c->sched_cnt, 2 * sizeof(long long));
+        long long eligible = 0;
+        for (int b = 0; b < B; ++b) eligible += lens[b];
+        k_sched_stats_set(st, c->sched_cnt, stepwise ? 0 : eligible, 0);  // the stepwise route counts its coins on the device
+    }
+    // Scheduled sampling with eps > 0: step s+1's input is a function of step s's logits, so nothing is time-batched.  Per step, on the rows
+    // [s*B, (s+1)*B) of the buffers the time-batched route fills: input projection, one step of LSTM-1, (projection, concat + dropout, input
+    // projection, one step of LSTM-2,) the logits GEMM, and the kernel that decides and gathers the input of step s+1.  Every launch applies
+    // the dropout multipliers of step s itself: the backward pass regenerates them from (s, b, j).  x_cnn is needed at step 0, so the image
+    // embedding runs on the main stream.
+    auto sched_forward = [&]() -> int {
+        if (int e = image_embedding(st, false)) return e;
+        const bool fused1 = lstm_fused_on(dt, B, H1, c->ldH1, c->ld4H1), fused2 = two && lstm_fused_on(dt, B, H2, c->ldH2, c->ld4H2);
+        const bool alone = lstm_alone(c);
+        const auto rg = rec_gemm(c);
+        k_embed_gather(st, dt, c->WeT, c->ldE, c->tok_in, 1, B, E, two ? d1 : none, c->Xemb, c->ldX1);  // step 0: bos
+        for (int s = 0; s < S; ++s) {
+            const int64_t m0 = (int64_t)s * B;
+            void *Xs = boff(c->Xemb, m0 * c->ldX1, es);
+            if (!two) k_concat_x2(st, dt, Xs, c->ldX1, c->xcnn, c->ldh, 1, B, E, h, d1, s);
+            GEMM(c, dt, Xs, c->ldX1, c->W1x, c->ldX1, c->G1 + m0 * 4 * H1, 4 * H1, B, 4 * H1, X1, p[1], true);
+            if (int e = lstm_step_fwd(c, alone, rg, fused1, s, B, H1, c->ldH1, c->ld4H1, c->G1, c->W1h, c->A1, c->C1, c->H1all)) return e;
+            const void *Hs = boff(c->H1all, m0 * c->ldH1, es);
+            if (two) {
+                void *X2s = boff(c->X2, m0 * c->ldH2, es);
+                GEMM(c, dt, Hs, c->ldH1, c->Wpd, c->ldH1, X2s, c->ldH2, B, h, H1, nullptr, false);
+                k_concat_x2(st, dt, X2s, c->ldH2, c->xcnn, c->ldh, 1, B, h, h, d2, s);
+                GEMM(c, dt, X2s, c->ldH2, c->W2x, c->ldH2, c->G2 + m0 * 4 * H2, 4 * H2, B, 4 * H2, H2, p[3], true);
+                if (int e = lstm_step_fwd(c, alone, rg, fused2, s, B, H2, c->ldH2, c->ld4H2, c->G2, c->W2h, c->A2, c->C2, c->H2all)) return e;
+                Hs = boff(c->H2all, m0 * c->ldH2, es);
+            }
+            GEMM(c, dt, Hs, c->ldH2, c->Wod, c->ldH2, c->Logits + m0 * c->ldV, c->ldV, B, V, H2, p[8], true);
+            if (s + 1 < S) {
+                SchedNext a{};
+                a.logits = c->Logits + m0 * c->ldV; a.ld_l = c->ldV;
+                a.V = V; a.B = B; a.s_next = s + 1;
+                a.lens = c->lens_dev;
+                a.eps = ss->eps; a.temp = ss->temperature;
+                a.k0 = (uint32_t)ss->seed; a.k1 = (uint32_t)(ss->seed >> 32);
+                a.row0 = (uint32_t)ss->row0;
+                a.tok_in = c->tok_in;
+                a.wembT = c->WeT; a.ld_w = c->ldE; a.E = E;
+                a.d = two ? d1 : none;
+                a.xemb = c->Xemb; a.ld_x = c->ldX1;
+                a.cnt = c->sched_cnt;
+                k_sched_next_input(st, dt, a);
+            }
+        }
+        KCHK(c, "stepwise forward");
+        return LRCN_OK;
+    };
     int rx = LRCN_OK;
-    if (xfork) {
+    if (stepwise) {
+        if ((r = sched_forward())) return r;
+    } else if (xfork) {
         HIPCHK(c, hipEventRecord(c->xc_fork, st));
         HIPCHK(c, hipStreamWaitEvent(c->wg_stream, c->xc_fork, 0));
         rx = image_embedding(c->wg_stream, true);
@@ -276,14 +342,14 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
         GEMM(c, dt, c->Xemb, c->ldX1, c->W1x, c->ldX1, c->G1, 4 * H1, M, 4 * H1, X1, p[1], true);
         return lstm_layer_fwd(c, S, B, H1, c->ldH1, c->ld4H1, c->G1, c->W1h, c->A1, c->C1, c->H1all, epi ? c->W1h_gi : nullptr);
     };
-    r = first_layer();
+    if (!stepwise) r = first_layer();
     if (xfork) {  // joined on EVERY exit: the side chain reads the caller's feats
         if (hipStreamWaitEvent(st, c->xc_done, 0) != hipSuccess) (void)hipStreamSynchronize(c->wg_stream);
         if (rx) return rx;
     }
     if (r) return r;
-    const void *Htop = c->H1all;  // the hidden states the logits are computed from
-    if (two) {
+    const void *Htop = two ? c->H2all : c->H1all;  // the hidden states the logits are computed from
+    if (two && !stepwise) {
         // x = s[1]*w[end-4]; x = hcat(x, x_cnn); x = dropout(x)    lrcn.jl:544-547
         GEMM(c, dt, c->H1all, c->ldH1, c->Wpd, c->ldH1, c->X2, c->ldH2, M, h, H1, nullptr, false);
         k_concat_x2(st, dt, c->X2, c->ldH2, c->xcnn, c->ldh, S, B, h, h, d2);
@@ -291,10 +357,10 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
         GEMM(c, dt, c->X2, c->ldH2, c->W2x, c->ldH2, c->G2, 4 * H2, M, 4 * H2, H2, p[3], true);
         r = lstm_layer_fwd(c, S, B, H2, c->ldH2, c->ld4H2, c->G2, c->W2h, c->A2, c->C2, c->H2all, epi ? c->W2h_gi : nullptr);
         if (r) return r;
-        Htop = c->H2all;
     }
     // logits for all steps: x * w[end-1] .+ w[end]   lrcn.jl:550
-    GEMM(c, dt, Htop, c->ldH2, c->Wod, c->ldH2, c->Logits, c->ldV, M, V, H2, p[8], true);
+    if (!stepwise) GEMM(c, dt, Htop, c->ldH2, c->Wod, c->ldH2, c->Logits, c->ldV, M, V, H2, p[8], true);
+    if (fed_out) HIPCHK(c, hipMemcpyAsync(fed_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
     if (logits_out) {  // (T+1) blocks of B x V column-major: block s memory [V][B]
         for (int s = 0; s < S; ++s)
             k_transpose_f32(st, c->Logits + (int64_t)s * B * c->ldV, c->ldV, B, V, logits_out + (int64_t)s * B * V, B);
@@ -447,15 +513,23 @@ int lrcn_impl::fetch_loss(lrcn_ctx *c, double *out) {
 namespace {
 
 // The body of the lrcn_loss* entry points.  var: the variable-length form, whose lens must be given (the other passes NULL);
-// weighted: that form with row_w, which must be given too; grads NULL: the loss alone.
+// weighted: that form with row_w, which must be given too; grads NULL: the loss alone.  sched (include/lrcn_sched.h): the variable-length form
+// with ss, which must be given, an optional row_w and the optional outputs fed / logits.
+struct SchedIo {
+    const lrcn_sched *ss;
+    int32_t *fed;
+    float *logits;
+};
 int loss_entry(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, bool var, const int32_t *lens, int T, int B,
                int norm_B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host, bool weighted = false,
-               const float *row_w = nullptr) {
+               const float *row_w = nullptr, const SchedIo *sched = nullptr) {
     DeviceGuard dg(c);
     if (!c || !p || !feats || (!tokens && T > 0)) return LRCN_EINVAL;
     if (var && !lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
     if (weighted && !row_w) FAIL(c, LRCN_EINVAL, "row_w is NULL");
-    int r = loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, nullptr, lens, norm_tokens, row_w);
+    if (sched && !sched->ss) FAIL(c, LRCN_EINVAL, "the lrcn_sched argument is NULL");
+    int r = sched ? loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, sched->logits, lens, norm_tokens, row_w, sched->ss, sched->fed)
+                  : loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, nullptr, lens, norm_tokens, row_w);
     if (r) return r;
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
 }
@@ -465,13 +539,13 @@ int loss_entry(lrcn_ctx *c, const float *const p[9], const float *feats, const i
 int train_step_impl(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                     const int32_t *tokens, bool var, const int32_t *lens, int T, int B, int norm_B, int64_t norm_tokens,
                     const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host,
-                    bool weighted = false, const float *row_w = nullptr) {
+                    bool weighted = false, const float *row_w = nullptr, const SchedIo *sched = nullptr) {
     DeviceGuard dg(c);
     if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
     if (std::isnan(max_norm)) FAIL(c, LRCN_EINVAL, "max_norm is NaN");
     const bool clip = max_norm > 0.0f;
     if (clip && step < 1) return LRCN_EINVAL;  // (the unclipped step finds a bad `step` in its update, after the pass)
-    int r = loss_entry(c, p, feats, tokens, var, lens, T, B, norm_B, norm_tokens, drop, g, nullptr, weighted, row_w);
+    int r = loss_entry(c, p, feats, tokens, var, lens, T, B, norm_B, norm_tokens, drop, g, nullptr, weighted, row_w, sched);
     if (r) return r;
     if (clip) {
         r = lrcn_grad_sumsq_model(c, g, -1, nullptr);
@@ -579,6 +653,42 @@ int lrcn_train_step_w(lrcn_ctx *c, float *const p[9], float *const g[9], float *
                       const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
     return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host,
                            true, row_w);
+}
+
+// ---- include/lrcn_sched.h: scheduled sampling ----
+int lrcn_loss_sched(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, const float *row_w,
+                    int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss, int32_t *fed_out, float *logits_out,
+                    double *loss_host) {
+    const SchedIo io{ss, fed_out, logits_out};
+    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, nullptr, loss_host, false, row_w, &io);
+}
+
+int lrcn_loss_grad_sched(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens,
+                         const float *row_w, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss,
+                         float *const grads[9], int32_t *fed_out, float *logits_out, double *loss_host) {
+    if (!grads) return LRCN_EINVAL;
+    const SchedIo io{ss, fed_out, logits_out};
+    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, grads, loss_host, false, row_w, &io);
+}
+
+int lrcn_train_step_sched(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                          const int32_t *tokens, const int32_t *lens, const float *row_w, int T, int B, int64_t norm_tokens,
+                          const lrcn_dropout *drop, const lrcn_sched *ss, int step, float lr, float b1, float b2, float eps, float max_norm,
+                          double *loss_host) {
+    const SchedIo io{ss, nullptr, nullptr};
+    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host,
+                           false, row_w, &io);
+}
+
+int lrcn_sched_stats(lrcn_ctx *c, int64_t *eligible, int64_t *drawn) {
+    DeviceGuard dg(c);
+    if (!c) return LRCN_EINVAL;
+    long long n[2] = {0, 0};
+    if (c->sched_cnt) HIPCHK(c, hipMemcpyAsync(n, c->sched_cnt, sizeof(n), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (eligible) *eligible = n[0];
+    if (drawn) *drawn = n[1];
+    return LRCN_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // train_kernels.hip -- the kernels only the training step (train.hip, update.hip) launches: token rows, the embedding gradient (scatter, sparse
 // export, ordered sums), dropout mask + reduce of dX2, the shadow-weight pass with and without Adam, multi-tensor Adam, and the gradient-norm
-// clipping of include/lrcn_clip.h (sum of squares, control block, the clipped forms of both Adam kernels).
+// clipping of include/lrcn_clip.h (sum of squares, control block, the clipped forms of both Adam kernels), and the next-input kernel of
+// scheduled sampling (include/lrcn_sched.h).
 #include "kernel_util.h"
+#include "draw.h"
 
 namespace {
 
@@ -49,6 +51,54 @@ __global__ void build_tokens_var_kernel(const int32_t *tokens, const int32_t *le
     }
     tok_in[i] = in;
     tok_tgt[i] = tg;
+}
+
+// ---- scheduled sampling (include/lrcn_sched.h): the input of row b at step s1 = a.s_next, after the logits of step s1 - 1 ----
+// One 256-thread workgroup per row; every branch is uniform over the workgroup (lens[b], the coin and the temperature are per row).
+//   s1 > lens[b]   tok_in holds eos (k_build_tokens_var): gather that row.
+//   coin           u of Philox counter (0xFFFFFFFF, s1, 0xFFFFFFFF, row0 + b) -- every thread computes the same word; no fire: the gold word
+//                  of tok_in, and the logits row is NOT read.
+//   fire           the row's maximum (the row staged in LDS up to V = 15360: `stage`, 60 KB of dynamic LDS, two workgroups per CU), then the
+//                  Gumbel argmax of draw.h over the columns within 20 * temp of it, noise counter (j >> 2, s1, 0, row0 + b); the winner
+//                  goes to tok_in and counts as drawn.  No log-sum-exp: the draw needs none.
+// Then the word's embedding row into Xemb row s1*B + b, times the dropout multiplier of step s1 (d: none in LRCN-1f, whose concat applies it).
+template <typename T> __global__ __launch_bounds__(256) void sched_next_input_kernel(const SchedNext a, int stage) {
+    extern __shared__ float srow[];
+    __shared__ float shf[4];
+    __shared__ float shv[4];
+    __shared__ int shi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, s1 = a.s_next;
+    const int64_t m = (int64_t)s1 * a.B + b;
+    int tok = a.tok_in[m];
+    if (s1 <= a.lens[b]) {
+        const uint32_t row = a.row0 + (uint32_t)b;
+        const uint32_t x = philox4x32_10(0xFFFFFFFFu, (uint32_t)s1, 0xFFFFFFFFu, row, a.k0, a.k1).x[0];
+        const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+        const bool fire = u < a.eps;
+        if (tid == 0) atomicAdd(reinterpret_cast<unsigned long long *>(a.cnt), 1ull);
+        if (fire) {
+            const float *g = a.logits + (int64_t)b * a.ld_l;
+            const float *z = stage ? srow : g;
+            const float mx = row_max_stage(g, a.V, stage, srow, shf);   // (its barriers also publish srow)
+            const float thr = a.temp > 0.0f ? mx - GUMBEL_PRUNE * a.temp : mx;
+            float bs, bz;
+            int bc;
+            gumbel_argmax(z, a.V, a.temp, thr, (uint32_t)s1, 0u, row, a.k0, a.k1, [](float, int) { return true; }, bs, bc, bz);
+            block_best(bs, bc, shv, shi);
+            tok = (unsigned)bc < (unsigned)a.V ? bc : 2;   // the row's maximum is admitted; only an all-NaN row admits no column: unk
+            if (tid == 0) {
+                a.tok_in[m] = tok;
+                atomicAdd(reinterpret_cast<unsigned long long *>(a.cnt) + 1, 1ull);
+            }
+        }
+    }
+    const T *src = reinterpret_cast<const T *>(a.wembT) + (int64_t)tok * a.ld_w;
+    T *dst = reinterpret_cast<T *>(a.xemb) + m * a.ld_x;
+    for (int e = tid; e < a.E; e += 256) dst[e] = from_f32<T>(to_f32(src[e]) * drop_mult(a.d, s1, b, e, a.B, a.E));
+}
+__global__ void sched_stats_set_kernel(long long *cnt, long long eligible, long long drawn) {
+    cnt[0] = eligible;
+    cnt[1] = drawn;
 }
 
 // ---- embedding gradient, E-contiguous form (dual of the gather, lrcn.jl:556/569 under AutoGrad) ----
@@ -454,6 +504,13 @@ void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *le
                         double *zero_acc) {
     const int n = (T + 1) * B;
     hipLaunchKernelGGL(build_tokens_var_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, tokens, lens, T, B, V, tok_in, tok_tgt, zero_acc);
+}
+void k_sched_next_input(hipStream_t st, int dtype, const SchedNext &a) {
+    const int stage = a.V <= 15360;   // as k_sample_rows: 60 KB of LDS (+ the static few bytes: under the default 64 KB limit)
+    DISPATCH_T(dtype, hipLaunchKernelGGL(sched_next_input_kernel<T>, dim3(a.B), dim3(256), stage ? sizeof(float) * a.V : 0, st, a, stage));
+}
+void k_sched_stats_set(hipStream_t st, long long *cnt, long long eligible, long long drawn) {
+    hipLaunchKernelGGL(sched_stats_set_kernel, dim3(1), dim3(1), 0, st, cnt, eligible, drawn);
 }
 void k_embed_rows_export(hipStream_t st, const float *dxemb, int64_t ld_dx, int S, int B, int E, DropSpec d, float *out) {
     hipLaunchKernelGGL(embed_rows_export_kernel, dim3(S * B), dim3(256), 0, st, dxemb, ld_dx, S, B, E, d, out);

@@ -145,9 +145,13 @@ class HipOps:
     def set_vgg_wg_cap(self, cap):
         self.ctx._call("lrcn_vgg_set_wg_cap", int(cap))
 
-    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None, row_weights=None):
+    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None, row_weights=None, sched=None):
         L.lossgradient(self.ctx, param, feats, tokens, norm_B=norm_B, pdrop=pdrop, seed=seed, grads=grads,
-                       want_loss=False, lens=lens, norm_tokens=norm_tokens, row_weights=row_weights)
+                       want_loss=False, lens=lens, norm_tokens=norm_tokens, row_weights=row_weights, sched=sched)
+
+    def sched_stats(self):
+        """(eligible, drawn) of the most recent lossgradient with sched (waits for the context's stream)."""
+        return L.sched_stats(self.ctx)
 
     def update(self, param, grads, optim, clipped=False):
         L.update(self.ctx, param, grads, optim, clipped=clipped)
@@ -645,7 +649,8 @@ class DataParallelTrainer:
             return staged
         return self.ops.upload(img)
 
-    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None, row_weights=None):
+    def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None, row_weights=None,
+             sched=None):
         """One synchronous-SGD step on this rank's shard.  img_u8: this rank's uint8 crops (or feats given);
         next_img_u8: the crops of the NEXT step(s), whose VGG forward runs beside this step's LSTM work and all-reduce.
         img_u8 is IGNORED when an earlier step() already produced this batch's features through its next_img_u8.
@@ -667,10 +672,22 @@ class DataParallelTrainer:
         gradients then sum to the single-device gradient, as with B_global for equal lengths.  Not with the "abi" backend.
 
         row_weights (with lens): a real weight for each of this rank's rows (include/lrcn_weighted.h).  The weights act only inside the
-        loss kernel and norm_tokens stays the global count, so the ranks' gradients sum to the single-device gradient in every mode."""
-        if row_weights is not None and lens is None:
+        loss kernel and norm_tokens stays the global count, so the ranks' gradients sum to the single-device gradient in every mode.
+
+        sched ((eps, temperature, seed) or lrcn.Sched): scheduled sampling (include/lrcn_sched.h).  Its row0 is set here to this rank's
+        first row in the global batch (shard_rows), so coins and noise are those of the single-device step on the global batch.  Without
+        lens the rows are equal-length captions: lens[b] = T and norm_tokens = B_global * (T + 1).  Not with the "abi" backend."""
+        if row_weights is not None and lens is None and sched is None:
             raise L.LrcnError("row_weights needs lens")
         rows = int(tokens.shape[1])
+        if sched is not None:
+            if self.backend == "abi" and self._multi:
+                raise L.LrcnError("the \"abi\" data-parallel backend (lrcn_train_step_dp) has no scheduled sampling; use backend=\"torch\"")
+            eps, temperature, sseed = tuple(sched)[:3]
+            sched = (eps, temperature, sseed, shard_rows(self.B_global, self.world, self.rank).start)
+            if lens is None:
+                lens = np.full(rows, int(tokens.shape[0]), np.int32)
+                norm_tokens = self.B_global * (int(tokens.shape[0]) + 1)
         self._cur_M = (int(tokens.shape[0]) + 1) * rows
         if feats is None:
             if self._feat_q:
@@ -716,6 +733,8 @@ class DataParallelTrainer:
                     raise L.LrcnError("a padded batch over %d ranks needs the global batch's token count (norm_tokens)" % self.world)
                 norm_tokens = int(np.asarray(lens, dtype=np.int64).sum()) + len(lens)
             kw = {} if row_weights is None else {"row_weights": row_weights}   # (an ops stand-in without the keyword keeps working)
+            if sched is not None:
+                kw["sched"] = sched
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens), **kw)
         else:
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)

@@ -179,6 +179,46 @@ def _row_weights(row_weights, lens, B):
     return a, a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+class Sched:
+    """Scheduled sampling of one call (include/lrcn_sched.h): a row's eligible input is, with probability eps, a word drawn at `temperature`
+    from the row's own logits of the step before; seed keys coins and noise, row0 is the call's first row in the global batch."""
+    __slots__ = ("eps", "temperature", "seed", "row0")
+
+    def __init__(self, eps, temperature=1.0, seed=0, row0=0):
+        self.eps, self.temperature, self.seed, self.row0 = float(eps), float(temperature), int(seed), int(row0)
+
+    def __iter__(self):
+        return iter((self.eps, self.temperature, self.seed, self.row0))
+
+
+def _sched(sched, B):
+    """sched: Sched, (eps, temperature, seed) or (eps, temperature, seed, row0) -> _lib.Sched, checked as the library checks it."""
+    t = tuple(sched)
+    if len(t) not in (3, 4):
+        raise LrcnError("sched must be (eps, temperature, seed[, row0])")
+    eps, temp, seed, row0 = float(t[0]), float(t[1]), int(t[2]), int(t[3]) if len(t) == 4 else 0
+    if not 0.0 <= eps <= 1.0:   # (a NaN fails every comparison)
+        raise LrcnError("sched eps=%r outside [0, 1]" % (t[0],))
+    if not 0.0 <= temp < float("inf"):
+        raise LrcnError("sched temperature=%r must be finite and >= 0" % (t[1],))
+    if not 0 <= seed < 2 ** 64:
+        raise LrcnError("sched seed=%r outside [0, 2^64)" % (t[2],))
+    if row0 < 0 or row0 + B > 2 ** 32:
+        raise LrcnError("sched row0=%d: rows [row0, row0 + %d) must lie in [0, 2^32)" % (row0, B))
+    return _lib.Sched(eps, temp, seed, row0)
+
+
+def _sched_lens(lens, T, B):
+    return np.full(B, T, np.int32) if lens is None else lens   # scheduled sampling takes padded batches; equal lengths: lens[b] = T
+
+
+def sched_stats(ctx):
+    """(eligible, drawn) of the most recent scheduled-sampling call: sum(lens) and the coins that fired.  Waits for the context's stream."""
+    e, d = C.c_int64(), C.c_int64()
+    ctx._call("lrcn_sched_stats", C.byref(e), C.byref(d))
+    return int(e.value), int(d.value)
+
+
 # ------------------------------------------------------------------------------------------------ model
 def initweights(ctx, seed=42):
     """initweights(atype, hidden, vocab, embed) (lrcn.jl:489-510) -> list of 9 column-major tensors."""
@@ -230,17 +270,28 @@ def lrcn(ctx, w, s, x_cnn, x_lstm, mask1=None, mask2=None):
     return logits
 
 
-def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None):
+def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None,
+         sched=None):
     """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
     tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
     lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
     norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used.
-    row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h)."""
+    row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h).
+    sched (Sched, or (eps, temperature, seed[, row0])): scheduled sampling (include/lrcn_sched.h); lens then defaults to [T] * B."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
+    ss = _sched(sched, B) if sched is not None else None
+    if ss is not None:
+        lens = _sched_lens(lens, T, B)
     wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if ss is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        ctx._call("lrcn_loss_sched", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1] if wa else None, T, B, nt,
+                  C.byref(d) if d else None, C.byref(ss), None, None, C.byref(out))
+        del keep, la, wa
+        return out.value
     if wa is not None:
         la, lp, nt = _lens(lens, T, B, norm_tokens)
         ctx._call("lrcn_loss_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
@@ -259,16 +310,36 @@ def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, 
 
 
 def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
-                 want_loss=True, lens=None, norm_tokens=None, row_weights=None):
-    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights:
-    as loss()."""
+                 want_loss=True, lens=None, norm_tokens=None, row_weights=None, sched=None, return_fed=False, return_logits=False):
+    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights /
+    sched: as loss().  With sched, return_fed / return_logits append the words that were fed ((T+1, B) int32 numpy) and the logits the
+    draws were made from ((T+1, B, V) float32 numpy) to the result."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
+    ss = _sched(sched, B) if sched is not None else None
+    if ss is None and (return_fed or return_logits):
+        raise LrcnError("return_fed / return_logits need sched")
+    if ss is not None:
+        lens = _sched_lens(lens, T, B)
     wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     if grads is None:
         grads = [jl_empty(*t.shape) for t in param]
     d, keep = _dropout(pdrop, seed, mask1, mask2)
     out = C.c_double()
+    if ss is not None:
+        la, lp, nt = _lens(lens, T, B, norm_tokens)
+        fed = torch.empty((T + 1, B), device=feats.device, dtype=torch.int32) if return_fed else None
+        logits = torch.empty((T + 1, ctx.V, B), device=feats.device, dtype=torch.float32) if return_logits else None  # blocks of B x V column-major
+        ctx._call("lrcn_loss_grad_sched", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1] if wa else None, T, B, nt,
+                  C.byref(d) if d else None, C.byref(ss), _p9(grads), C.c_void_p(fed.data_ptr()) if return_fed else None,
+                  C.c_void_p(logits.data_ptr()) if return_logits else None, C.byref(out) if want_loss else None)
+        del keep, la, wa
+        res = (grads, (out.value if want_loss else None))
+        if return_fed:
+            res += (fed.cpu().numpy(),)
+        if return_logits:
+            res += (logits.permute(0, 2, 1).cpu().numpy(),)
+        return res
     if wa is not None:
         la, lp, nt = _lens(lens, T, B, norm_tokens)
         ctx._call("lrcn_loss_grad_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
@@ -382,18 +453,27 @@ def refresh_shadows_group(ctx, param, group, stream=None):
 
 
 def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None,
-               gclip=0.0, row_weights=None):
-    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights: as loss().
+               gclip=0.0, row_weights=None, sched=None):
+    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights / sched: as loss().
     gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h; clip_stats() has the counters)."""
     gclip = float(gclip or 0.0)
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     d, keep = _dropout(pdrop, seed, None, None)
-    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None   # both checked before the step counter moves
+    ss = _sched(sched, B) if sched is not None else None   # all checked before the step counter moves
+    if ss is not None:
+        lens = _sched_lens(lens, T, B)
+    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     la = _lens(lens, T, B, norm_tokens) if lens is not None else None
     optim.t += 1
     out = C.c_double()
     clip = (gclip,) if gclip > 0 else ()
+    if ss is not None:
+        ctx._call("lrcn_train_step_sched", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()), la[1],
+                  wa[1] if wa else None, T, B, la[2], C.byref(d) if d else None, C.byref(ss), optim.t, optim.lr, optim.beta1, optim.beta2,
+                  optim.eps, gclip, C.byref(out) if want_loss else None)
+        del keep, la, wa
+        return out.value if want_loss else None
     if wa is not None:
         ctx._call("lrcn_train_step_w", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()), la[1],
                   wa[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps, gclip,

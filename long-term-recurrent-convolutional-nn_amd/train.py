@@ -16,6 +16,7 @@ import torch.distributed as dist
 
 from . import dp
 from . import lrcn as L
+from . import sched as S
 
 
 def epoch_order(n_blocks, seed, epoch):
@@ -48,17 +49,28 @@ def batches_per_forward(rows, chunk_images=256):
     return max(1, int(chunk_images) // int(rows)) if rows <= 64 else 1
 
 
-def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1):
+def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1, sched=None, sched_counts=None):
     """One epoch (lrcn.jl:350-396).  feats_of(ids) -> this rank's feature rows on the device, or crops_of(ids) -> uint8 crops
     [len(ids)][224][224][3] (device, or pinned host): then the VGG forward of the NEXT `lookahead` batches (one forward for all of them)
-    runs beside the LSTM steps of the current ones.  Returns the number of captions this rank trained on."""
+    runs beside the LSTM steps of the current ones.  Returns the number of captions this rank trained on.
+    sched (eps, temperature, epoch seed): scheduled sampling (include/lrcn_sched.h) on precomputed features, step k with the key
+    sched.step_seed(epoch seed, k); sched_counts (a list [eligible, drawn]) then receives this rank's counts, read after every step."""
     W, r = trainer.world, trainer.rank
     n = 0
+    if sched is not None and crops_of is not None:
+        raise L.LrcnError("scheduled sampling trains on precomputed features (feats_of)")
     shards = [shard_block(blocks[k], W, r) for k in order]
     nxt_pos, nxt = 1, None          # position (in `order`) of the first batch whose crops have not been handed to the trainer yet
     for pos, shard in enumerate(shards):
         ids, toks = shard[0], shard[1]
-        if len(shard) == 4:   # a padded batch: precomputed features only (the crops' pipeline counts on one row count per step)
+        if sched is not None:
+            kw = {"lens": shard[2], "norm_tokens": shard[3]} if len(shard) == 4 else {}
+            trainer.step(None, toks, feats=feats_of(ids), sched=(sched[0], sched[1], S.step_seed(sched[2], pos)), **kw)
+            if sched_counts is not None:
+                e, d = trainer.ops.sched_stats()
+                sched_counts[0] += e
+                sched_counts[1] += d
+        elif len(shard) == 4:   # a padded batch: precomputed features only (the crops' pipeline counts on one row count per step)
             if crops_of is not None:
                 raise L.LrcnError("variable-length batches train on precomputed features (feats_of)")
             trainer.step(None, toks, feats=feats_of(ids), lens=shard[2], norm_tokens=shard[3])
@@ -100,18 +112,28 @@ def average_loss(trainer, blocks, feats_of):
     return total / max(count, 1)
 
 
-def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feats_of=None, save=None, log=print, sync=None, lookahead=1):
+def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feats_of=None, save=None, log=print, sync=None, lookahead=1,
+          sched_of=None):
     """train! (lrcn.jl:223-246).  splits: [(blocks of the training split), (blocks of the dev split)?], blocks = [(ids, tokens)] or the
     padded [(ids, tokens, lens)] of captions.minibatch_varlen.
     feats_of / crops_of: the training inputs (one of them); eval_feats_of[i](ids): features of split i for average_loss (default:
     feats_of).  save(epoch): called on every rank after each epoch (rank 0 writes; a sharded update gathers its moments first).
+    sched_of(e) (e = epoch - 1, 0-based as in sched.epsilon): None, or (eps, temperature, seed) of that epoch's scheduled sampling
+    (sched.sched_of); one more line per epoch then gives eps and the realised drawn / eligible over all ranks.
     Returns the list of per-epoch loss tuples."""
     import time
     history = []
     ev = eval_feats_of or [feats_of] * len(splits)
     for epoch in range(1, epochs + 1):
         t0 = time.time()
-        n = train1(trainer, splits[0], epoch_order(len(splits[0]), seed, epoch), feats_of=feats_of, crops_of=crops_of, lookahead=lookahead)
+        ss = sched_of(epoch - 1) if sched_of is not None else None
+        counts = [0, 0]
+        n = train1(trainer, splits[0], epoch_order(len(splits[0]), seed, epoch), feats_of=feats_of, crops_of=crops_of, lookahead=lookahead,
+                   sched=ss, sched_counts=counts)
+        if sched_of is not None and trainer.world > 1:
+            t = torch.tensor(counts, dtype=torch.int64, device=trainer.param[0].device if dist.get_backend(trainer.group) == "nccl" else "cpu")
+            dist.all_reduce(t, group=trainer.group)
+            counts = [int(t[0].item()), int(t[1].item())]
         if sync is not None:
             sync()
         dt_s = time.time() - t0
@@ -123,6 +145,9 @@ def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feat
         if trainer.rank == 0:
             log("(:epoch, %d, :loss, %s)  [%.0f captions/s on %d rank%s]" % (epoch, ", ".join("%.4f" % v for v in losses),
                                                                            n * trainer.world / max(dt_s, 1e-9), trainer.world, "" if trainer.world == 1 else "s"))
+            if sched_of is not None:
+                log("(:sched, %d, :eps, %g, :drawn, %d, :eligible, %d, :rate, %.4f)" % (epoch - 1, ss[0] if ss else 0.0, counts[1], counts[0],
+                                                                                        counts[1] / max(counts[0], 1)))
             st = trainer.clip_stats() if getattr(trainer, "gclip", 0) > 0 and hasattr(trainer, "clip_stats") else None
             if st is not None:   # --gclip on the device (include/lrcn_clip.h): the counters run since the trainer's first step
                 log("(:gclip, %g, :clipped, %d, :skipped, %d, :last_norm, %.6g)" % (trainer.gclip, st["clipped"], st["skipped"], st["last_norm"]))

@@ -14,6 +14,8 @@
 Training runs on dp.DataParallelTrainer (train.py = train! / train1 / average_loss, lrcn.jl:223-246, 330-397, 407-486): every bucketed
 batch is split by rows over the ranks (same T everywhere, the global batch as normaliser, gradients summed over RCCL, identical Adam).
 `--varlen` batches captions of mixed lengths (padded, masked loss) instead of the reference's equal-length batches: nothing is dropped.
+`--ss_start E` turns scheduled sampling on from epoch E (counted from 0): an input word is, with a probability that grows by `--ss_step`
+every `--ss_every` epochs up to `--ss_max`, drawn on the device from the model's own logits of the step before (include/lrcn_sched.h).
 `--gpus N` starts the ranks itself from a parent that never touches the GPU; the torchrun form works too.  `--cnn --train --imagedir`
 trains end to end from images: the VGG forward of the next batch runs beside the LSTM step of the current one.
 
@@ -87,6 +89,13 @@ def build_parser():
     p.add_argument("--varlen", action="store_true",
                    help="--train: padded batches of mixed caption lengths (include/lrcn_varlen.h) for the training and the evaluation splits: the "
                         "length-sorted captions cut into windows of --batchsize, none dropped, no forced batch 10 (needs --features)")
+    p.add_argument("--ss_start", type=int, default=-1,
+                   help="--train: scheduled sampling (include/lrcn_sched.h) from this epoch on, counted from 0 (-1 = off): an input word is, "
+                        "with probability eps, drawn from the model's own logits of the step before (needs --features, --dp_backend torch)")
+    p.add_argument("--ss_every", type=int, default=5, help="--ss_start: eps grows every this many epochs")
+    p.add_argument("--ss_step", type=float, default=0.05, help="--ss_start: eps starts at this value and grows by it")
+    p.add_argument("--ss_max", type=float, default=0.25, help="--ss_start: the largest eps")
+    p.add_argument("--ss_temperature", type=float, default=1.0, help="--ss_start: temperature of the draw (0 = the argmax)")
     p.add_argument("--scst", action="store_true",
                    help="--train: self-critical training on the model's own samples with a CIDEr-D reward (lrcn_amd/scst.py); needs --loadfile")
     p.add_argument("--scst_samples", type=int, default=5, help="--scst: samples per image; a step takes batchsize // scst_samples images")
@@ -121,6 +130,8 @@ def main(argv=None):
     o = build_parser().parse_args(argv)
     if o.varlen and not o.train:
         raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
+    if o.ss_start >= 0 and (not o.train or o.scst):
+        raise SystemExit("--ss_start is a mode of the cross-entropy TRAINING job (--train without --scst)")
     if o.scst and not o.train:
         raise SystemExit("--scst is a mode of the TRAINING job (--train)")
     if o.scst and not o.loadfile:
@@ -462,6 +473,13 @@ def main(argv=None):
                 fmt.save_checkpoint(o.savefile, [L.from_jl(p) for p in param], vocab,
                                     adam={"m": [L.from_jl(t) for t in optim.m], "v": [L.from_jl(t) for t in optim.v], "step": optim.t})
 
+        if o.ss_start >= 0:
+            if from_images:
+                raise SystemExit("--ss_start trains on precomputed features (--features)")
+            if o.dp_backend == "abi" and world > 1:
+                raise SystemExit("--ss_start needs --dp_backend torch")
+            from lrcn_amd import sched as ss
+            kw["sched_of"] = ss.sched_of(o.ss_start, o.ss_every, o.ss_step, o.ss_max, temperature=o.ss_temperature, seed=seed)
         trn.train(trainer, splits, o.epochs, seed, save=save, log=say, sync=ctx.sync, lookahead=lookahead, **kw)
         trainer.close()
         if world > 1:
