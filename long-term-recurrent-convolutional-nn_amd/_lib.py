@@ -15,6 +15,7 @@ SAMPLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sampl
 SCORE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_score.h"))    # lrcn_score_matrix / _pairs (not in lrcn.h)
 NUCLEUS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nucleus.h"))  # lrcn_sample_batch_p / lrcn_sample_logits (not in lrcn.h)
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
+DIVERSE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_diverse.h"))  # lrcn_beam_diverse_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
 CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
@@ -177,6 +178,12 @@ NBEST_SIGNATURES = {
                                         C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_diverse.h declares (bound by lib() as well)
+DIVERSE_SIGNATURES = {
+    "lrcn_beam_diverse_batch": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+}
+
 
 # name -> (restype, argtypes); exactly the symbols include/lrcn_activity.h declares (bound by lib() as well)
 ACTIVITY_SIGNATURES = {
@@ -258,7 +265,7 @@ GEMM_DEBUG_SIGNATURES = {
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER,
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER,
                                                                                                    ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
@@ -279,7 +286,7 @@ def lib():
         # the one this process uses: import torch BEFORE the library so the dynamic linker binds to that instance.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + \
+        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
                 list(GEMM_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported

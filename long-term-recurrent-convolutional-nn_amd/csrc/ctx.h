@@ -127,6 +127,7 @@ struct lrcn_ctx {
     int32_t *nb_store = nullptr;
     int4 *nb_pool = nullptr, *nb_img = nullptr;
     float *nb_cum = nullptr, *nb_res_score = nullptr;
+    int32_t *dv_done = nullptr;   // lrcn_beam_diverse_batch (include/lrcn_diverse.h), lazily: one done flag per image [maxB]; the rest is nb_*
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;

@@ -1,10 +1,11 @@
-// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_score.h): the batched decode's routes,
-// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best beam and caption scoring.
+// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_score.h): the batched decode's routes,
+// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams and caption scoring.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "../../include/lrcn_nbest.h"
+#include "../../include/lrcn_diverse.h"
 #include "../../include/lrcn_nucleus.h"
 #include "../../include/lrcn_sample.h"
 #include "../../include/lrcn_score.h"
@@ -768,30 +769,38 @@ int lrcn_sample_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int 
 // The n-best beam search (include/lrcn_nbest.h): the batched decode of lrcn_beam_search_batch (decode_begin / decode_step on the route
 // decode_route picks, N*K rows) with log-probability top-K (the LOGP forms of the records merge and the rows kernel) and its own per-step
 // bookkeeping (nbest.hip): live slots in log space, a pool of finished hypotheses with length normalisation, the exact early stop.
-int lrcn_beam_nbest_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int nword, float alpha, int32_t *out_tokens,
-                          int *out_len, float *out_logp, float *out_score) {
-    if (!c) return LRCN_EINVAL;
-    DeviceGuard dg(c);
+// G > 0 (0: the n-best beam): diverse beam search (include/lrcn_diverse.h) -- the same decode and top-K at the full width K, the bookkeeping
+// of diverse.hip.
+static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
+                          int32_t *out_tokens, int *out_len, float *out_logp, float *out_score) {
     if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
     if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
     if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d must be in [1, max_B = %d]", N, K, c->maxB);
     if (nword < 1 || nword + 2 > LRCN_BEAM_MAXLEN) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,%d]", nword, LRCN_BEAM_MAXLEN - 2);
     if (!std::isfinite(alpha) || alpha < 0.0f) FAIL(c, LRCN_EINVAL, "alpha=%g must be finite and >= 0", (double)alpha);
+    const bool diverse = G != 0;
+    if (diverse && K % G != 0) FAIL(c, LRCN_EINVAL, "groups G=%d must divide the beam width K=%d", G, K);
+    if (diverse && (!std::isfinite(lambda) || lambda < 0.0f)) FAIL(c, LRCN_EINVAL, "lambda=%g must be finite and >= 0", (double)lambda);
     const int R = N * K, Lh = nword + 2;
     hipStream_t st = c->stream;
     int r = nbest_alloc(c);
     if (r) return r;
+    if (diverse && !c->dv_done) DALLOC(c, c->dv_done, sizeof(int32_t) * (size_t)c->maxB);
     const DecodeRoute rt = decode_route(c, R, K);
     if ((r = decode_begin(c, p, feats, N, K, rt))) return r;
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
-    NbestState ns{};
+    DiverseState ds{};
+    NbestState &ns = ds.nb;
     ns.parent = c->st_parent; ns.last = c->bs_last; ns.ndone = c->bs_ndone; ns.img = c->nb_img; ns.cum = c->nb_cum;
     ns.store = c->nb_store; ns.pool = c->nb_pool;
     ns.res_tok = c->bs_res_tok; ns.res_len = c->bs_res_len; ns.res_logp = c->bs_res_p; ns.res_score = c->nb_res_score;
     ns.K = K; ns.L = Lh; ns.nword = nword; ns.eos = LRCN_EOS;
     ns.lp_max = (float)std::pow((double)(nword + 1), (double)alpha);
     ns.seq_in = c->bs_seq[0];
-    k_nbest_init(st, ns, N, LRCN_BOS);   // histories = [bos], cum 0, next input = bos, one live slot, empty pools
+    ds.done = c->dv_done; ds.G = G; ds.lambda = lambda;
+    // histories = [bos], cum 0, next input = bos, one live slot (per group), empty pools
+    if (diverse) k_diverse_init(st, ds, N, LRCN_BOS);
+    else k_nbest_init(st, ns, N, LRCN_BOS);
     DecodeTail tail{};   // log-probability top-K (in the logits GEMM's epilogue + merge on the record route)
     tail.kind = DecodeTail::TOPK;
     tail.K = K;
@@ -804,15 +813,31 @@ int lrcn_beam_nbest_batch(lrcn_ctx *c, const float *const p[9], const float *fea
         ns.seq_out = c->bs_seq[cur ^ 1];
         ns.current = current;
         ns.lp_cur = (float)std::pow((double)current, (double)alpha);
-        k_nbest_update(st, c->st_topi, c->st_topv, ns, N);
+        if (diverse) k_diverse_update(st, c->st_topi, c->st_topv, ds, N);
+        else k_nbest_update(st, c->st_topi, c->st_topv, ns, N);
         cur ^= 1;
         if (!rt.epi) follow_parents(c, R);
         bool done = false;   // every image finished early?
         if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
         if (done) break;
     }
-    KCHK(c, "beam_nbest_batch");
+    KCHK(c, diverse ? "beam_diverse_batch" : "beam_nbest_batch");
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, R, Lh, out_tokens, out_len, out_logp, c->nb_res_score, out_score);
+}
+
+int lrcn_beam_nbest_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int nword, float alpha, int32_t *out_tokens,
+                          int *out_len, float *out_logp, float *out_score) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    return pool_beam_impl(c, p, feats, N, K, 0, 0.0f, nword, alpha, out_tokens, out_len, out_logp, out_score);
+}
+
+int lrcn_beam_diverse_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
+                            int32_t *out_tokens, int *out_len, float *out_logp, float *out_score) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (G < 1) FAIL(c, LRCN_EINVAL, "groups G=%d must be >= 1", G);
+    return pool_beam_impl(c, p, feats, N, K, G, lambda, nword, alpha, out_tokens, out_len, out_logp, out_score);
 }
 
 // Caption scoring (include/lrcn_score.h; paper section 5.1 / Table 2 -- not in lrcn.jl): see score_impl

@@ -351,3 +351,17 @@ struct NbestState {
 void k_nbest_init(hipStream_t st, const NbestState &s, int N, int bos);
 // one step for N images (one workgroup each) from this step's log-probability top-K topi / topv [N*K][K]; K <= 32
 void k_nbest_update(hipStream_t st, const int32_t *topi, const float *topv, const NbestState &s, int N);
+
+// ---- diverse.hip: the per-step bookkeeping of diverse beam search (lrcn_beam_diverse_batch, include/lrcn_diverse.h) ----
+// The n-best state with K = the full width, read as G groups of K' = K / G per image: group g of image n owns rows n*K + g*K' .. + K'-1 of
+// the histories, cum and the results, entries g*K' .. of the image's pool and storage rows g*2K' .. of its 2K; img is [N*G] group records
+// {live slots, pool entries, dead, satisfied}; done [N] marks the images whose results are written.
+struct DiverseState {
+    NbestState nb;
+    int32_t *done;
+    int G;
+    float lambda;
+};
+void k_diverse_init(hipStream_t st, const DiverseState &s, int N, int bos);
+// one step for N images (one workgroup each) from this step's log-probability top-K topi / topv [N*K][K] (the full width); K <= 32
+void k_diverse_update(hipStream_t st, const int32_t *topi, const float *topv, const DiverseState &s, int N);

@@ -691,6 +691,32 @@ def nbest_captions(ctx, param, feats, index_to_word, beam_width, nword, alpha=0.
             for entries in beam_nbest_batch(ctx, param, feats, beam_width, nword, alpha)]
 
 
+def beam_diverse_batch(ctx, param, feats, beam_width, groups, strength, nword, alpha=0.0):
+    """Diverse beam search for N images in one device-resident decode (lrcn_beam_diverse_batch, include/lrcn_diverse.h): beam_width beams in
+    `groups` groups of beam_width / groups, each an n-best beam whose proposals lose `strength` per live slot that an earlier group of the
+    image filled with the same word at the same step.  logp is the model's log-likelihood of the caption (the penalty never enters it).
+    feats N x 4096 -> per image a list of `groups` lists of (token ids incl. bos, logp, score), each best score first."""
+    N, K, G, L = feats.shape[0], beam_width, groups, nword + 2
+    out = (C.c_int32 * (N * K * L))()
+    n = (C.c_int * (N * K))()
+    lp = (C.c_float * (N * K))()
+    sc = (C.c_float * (N * K))()
+    ctx._call("lrcn_beam_diverse_batch", _p9(param), _ptr(feats), N, K, G, float(strength), nword, float(alpha), out, n, lp, sc)
+    toks = np.ctypeslib.as_array(out).reshape(N * K, L).tolist()
+    n, lp, sc = list(n), list(lp), list(sc)
+    Kp = K // G
+    return [[[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K + g * Kp, i * K + (g + 1) * Kp) if n[r] > 0] for g in range(G)] for i in range(N)]
+
+
+def diverse_captions(ctx, param, feats, index_to_word, beam_width, groups, strength, nword, alpha=0.0, normalize=False):
+    """beam_diverse_batch as caption text: per image the list of groups, each a list of (caption, logp, score), best score first."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    return [[[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in grp] for grp in img]
+            for img in beam_diverse_batch(ctx, param, feats, beam_width, groups, strength, nword, alpha)]
+
+
 def _caption(seq, index_to_word):
     words = []
     for t in seq[1:]:

@@ -70,6 +70,12 @@ def build_parser():
                         "--beam_width lines per image (id, score, logp, caption), candidates / ids keep each image's best")
     p.add_argument("--length_norm", type=float, default=0.0,
                    help="--nbest: rank by logp / len^ALPHA, len = predicted tokens (0 = raw log-likelihood, 1 = per token)")
+    p.add_argument("--diverse_groups", type=int, default=0,
+                   help="--nbest: diverse beam search (include/lrcn_diverse.h) -- --beam_width beams in this many groups (a divisor of it); writes "
+                        "<out>/diverse with --beam_width lines per image (id, group, score, logp, caption), candidates / ids keep the "
+                        "best-scoring entry over all groups (0 = off)")
+    p.add_argument("--diverse_strength", type=float, default=0.5,
+                   help="--diverse_groups: what a word loses per beam of an earlier group that took it at the same step")
     p.add_argument("--retrieval", action="store_true",
                    help="image-caption retrieval (paper section 5.1 / Table 2): score --capnumber images of the --generate split, drawn as --generate "
                         "draws them (a permutation seeded by --seed), against all their captions; R@1/5/10 and Medr both ways, "
@@ -254,6 +260,11 @@ def main(argv=None):
                 for line in L.sample_captions(ctx, param, f, idx2word, o.sample, o.generate, o.temperature, o.topk, sample_seed, top_p=o.topp)[0]:
                     print(line)
                 return 0
+            if o.nbest and o.diverse_groups > 0:   # the groups in order, each best score first: group<TAB>score<TAB>logp<TAB>caption
+                for g, grp in enumerate(L.beam_diverse_batch(ctx, param, f, o.beam_width, o.diverse_groups, o.diverse_strength, o.generate, o.length_norm)[0]):
+                    for toks, lp, sc in grp:
+                        print("%d\t%.6f\t%.6f\t%s" % (g, sc, lp, cap.caption_text(toks, idx2word)))
+                return 0
             if o.nbest:   # the n-best list, best score first: score<TAB>logp<TAB>caption
                 for toks, lp, sc in L.beam_nbest_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm)[0]:
                     print("%.6f\t%.6f\t%s" % (sc, lp, cap.caption_text(toks, idx2word)))
@@ -276,7 +287,8 @@ def main(argv=None):
         gc.collect()
         gc.freeze()
         smp = open(os.path.join(o.out, "samples" + suffix), "w") if o.sample > 0 else None
-        nbf = open(os.path.join(o.out, "nbest" + suffix), "w") if o.nbest and o.sample <= 0 else None
+        dvf = open(os.path.join(o.out, "diverse" + suffix), "w") if o.nbest and o.diverse_groups > 0 and o.sample <= 0 else None
+        nbf = open(os.path.join(o.out, "nbest" + suffix), "w") if o.nbest and o.sample <= 0 and dvf is None else None
         with open(os.path.join(o.out, "candidates" + suffix), "w") as out, open(os.path.join(o.out, "candidate_ids" + suffix), "w") as ido:
             for s0 in range(0, len(ids), gen_chunk):  # the reference decodes image by image; here gen_chunk images x beam_width rows per step
                 chunk = ids[s0:s0 + gen_chunk]
@@ -291,6 +303,18 @@ def main(argv=None):
                         out.write(cap.caption_text(rows[best][0], idx2word) + "\n")
                         for toks, lp in rows:
                             smp.write("%d\t%.6f\t%s\n" % (i, lp, cap.caption_text(toks, idx2word)))
+                    continue
+                if dvf is not None:
+                    # candidates / ids keep the best-scoring entry over all groups (the earlier group wins a tie); `diverse` holds the groups
+                    # in order, each best first: "id<TAB>group<TAB>score<TAB>logp<TAB>caption"
+                    res = L.beam_diverse_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.diverse_groups, o.diverse_strength, o.generate, o.length_norm)
+                    for i, groups in zip(chunk, res):
+                        best = max((grp[0] for grp in groups if grp), key=lambda e: e[2])
+                        ido.write("%d\n" % i)
+                        out.write(cap.caption_text(best[0], idx2word) + "\n")
+                        for g, grp in enumerate(groups):
+                            for toks, lp, sc in grp:
+                                dvf.write("%d\t%d\t%.6f\t%.6f\t%s\n" % (i, g, sc, lp, cap.caption_text(toks, idx2word)))
                     continue
                 if nbf is not None:
                     # candidates / ids keep each image's best entry; `nbest` holds the list: "id<TAB>score<TAB>logp<TAB>caption", best first
@@ -307,6 +331,8 @@ def main(argv=None):
             smp.close()
         if nbf is not None:
             nbf.close()
+        if dvf is not None:
+            dvf.close()
         return 0
 
     # ---------------------------------------------------------------- retrieval (paper section 5.1 / Table 2; not in lrcn.jl)
