@@ -255,17 +255,36 @@ int gemm(lrcn_ctx *c, int dtype, const void *A, int64_t lda, const void *B, int6
 void set_create_error(const char *msg);
 // lrcn() on the context's single-step buffers (lrcn_api.hip): lrcn_step and the single-image beam search
 int step_internal(lrcn_ctx *c, const float *const p[9], int B, const DropSpec &d2, bool h_ready = false);
-// loss / lossgradient on the context's buffers (train.hip): grads NULL = forward only, lens != NULL = the variable-length form,
-// row_w != NULL (host [B], with lens) = that form with a weight per caption (include/lrcn_weighted.h), ss != NULL (with lens) = scheduled
-// sampling (include/lrcn_sched.h; eps > 0: the stepwise forward), fed_out (device [T+1][B], with ss, may be NULL) = the words that were fed
-int loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
-              const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens = nullptr, int64_t norm_tokens = 0,
-              const float *row_w = nullptr, const lrcn_sched *ss = nullptr, int32_t *fed_out = nullptr);
+// One loss / lossgradient call.  An optional pointer that is set turns its form on; the entry points of train.hip fill this by member name.
+struct LossCall {
+    const float *const *p = nullptr;      // the nine parameter tensors
+    const float *feats = nullptr;         // B x 4096 column-major f32 (device)
+    const int32_t *tokens = nullptr;      // [T][B] (device)
+    int T = 0, B = 0, norm_B = 1;         // the equal-length form's scale is 1 / (norm_B (T+1)); norm_B is not used with lens
+    int64_t norm_tokens = 0;              // with lens: the scale is 1 / norm_tokens
+    const lrcn_dropout *drop = nullptr;
+    float *const *grads = nullptr;        // NULL: forward only
+    const int32_t *lens = nullptr;        // host [B]: the variable-length form (include/lrcn_varlen.h)
+    const float *row_w = nullptr;         // host [B], with lens: a weight per caption (include/lrcn_weighted.h)
+    const lrcn_sched *ss = nullptr;       // with lens: scheduled sampling (include/lrcn_sched.h; eps > 0: the stepwise forward)
+    int32_t *fed_out = nullptr;           // device [T+1][B], with ss: the words that were fed
+    float *logits_out = nullptr;          // device, (T+1) blocks of B x V column-major
+    enum Form { PLAIN, VAR, WEIGHTED, SCHED } form = PLAIN;   // which of lens / row_w / ss the entry point requires (train.hip loss_entry checks it)
+};
+// loss / lossgradient on the context's buffers (train.hip)
+int loss_impl(lrcn_ctx *c, const LossCall &q);
 // waits for the context's stream; the last loss call's mean loss into *out (NULL: only the out-of-range-token check) (train.hip)
 int fetch_loss(lrcn_ctx *c, double *out);
+// Which shadows a prepare_weights call needs on top of the forward ones.  cat, cat_perm and dec_tables belong to the batched decode.
+struct ShadowNeed {
+    bool bwd = false;         // the transposed copies of the backward pass
+    bool cat = false;         // W1cat / W2cat: [x | h] side by side, one gate GEMM per LSTM
+    bool gi = false;          // the recurrent weights with (unit, gate)-interleaved rows (cell-epilogue routes); sticky under the fused update
+    bool cat_perm = false;    // with cat: their rows interleaved likewise
+    bool dec_tables = false;  // gi and dec_W2c (W2 without its x_cnn columns, rows interleaved): a decode call, not sticky
+};
 // f32 column-major params -> K-contiguous shadows in T (update.hip; see DESIGN.md "shadow weights")
-int prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_bwd, bool cat = false, bool gi = false, bool cat_perm = false,
-                    bool dec_tables = false);
+int prepare_weights(lrcn_ctx *c, const float *const p[9], const ShadowNeed &need = ShadowNeed{});
 // the second shadow set of LRCN_OPT_FUSED_UPDATE, allocated once (update.hip): lrcn_set_option makes it outside any step
 int ensure_alt_shadows(lrcn_ctx *c);
 // update! of all nine tensors / of one gradient group on `stream` (update.hip): lrcn_adam_update[_group] and, `clipped`, their clipped

@@ -184,7 +184,9 @@ int decode_begin(lrcn_ctx *c, const float *const p[9], const float *feats, int N
     const int dt = c->dt, H1 = c->H1, H2 = c->H2, h = c->h, R = N * per_image;
     hipStream_t st = c->stream;
     int r = rt.tables ? decode_tables_alloc(c) : LRCN_OK;
-    if (r || (r = prepare_weights(c, p, false, !rt.tables, false, rt.epi, rt.tables))) return r;
+    ShadowNeed sh{};
+    sh.cat = !rt.tables; sh.cat_perm = rt.epi; sh.dec_tables = rt.tables;
+    if (r || (r = prepare_weights(c, p, sh))) return r;
     k_transpose(st, dt, 1, feats, N, LRCN_CNNOUT, N, c->F, LRCN_CNNOUT, 0);
     GEMM(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->dxcnn, c->ldh, N, h, LRCN_CNNOUT, nullptr, true);
     k_repeat_rows(st, GEMM_T_F32, c->dxcnn, c->ldh, N, per_image, h, c->xcnn);
@@ -443,7 +445,9 @@ int score_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, 
 
     int r = decode_tables_alloc(c);
     if (r) return r;
-    if ((r = prepare_weights(c, p, false, false, false, false, true))) return r;   // + the interleaved recurrent copies and dec_W2c
+    ShadowNeed sh{};
+    sh.dec_tables = true;   // + the interleaved recurrent copies and dec_W2c
+    if ((r = prepare_weights(c, p, sh))) return r;
     // ---- caption side: T1, then LSTM-1 and P_t = h1_t Wproj over blocks of max_B sorted captions
     GEMM(c, dt, c->WeT, c->ldE, c->W1x, c->ldX1, c->dec_T1, 4 * H1, V, 4 * H1, E, p[1], true);
     for (int j0 = 0; j0 < M; j0 += maxB) {
@@ -538,7 +542,7 @@ int lrcn_beam_search(lrcn_ctx *c, const float *const p[9], const float *feat, in
     if (nword < 1 || nword > 256) FAIL(c, LRCN_EINVAL, "nword=%d outside [1,256]", nword);
     const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h;
     hipStream_t st = c->stream;
-    int r = prepare_weights(c, p, false);
+    int r = prepare_weights(c, p);   // the forward shadows alone
     if (r) return r;
     // input = input * param[end-3]  (lrcn.jl:611), replicated to K rows
     k_cast_rows(st, dt, feat, LRCN_CNNOUT, 1, LRCN_CNNOUT, c->F, LRCN_CNNOUT);

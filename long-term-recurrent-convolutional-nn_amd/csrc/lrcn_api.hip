@@ -436,7 +436,7 @@ int lrcn_step(lrcn_ctx *c, const float *const p[9], float *const state[4], int B
     if (B < 1 || B > c->maxB) FAIL(c, LRCN_EINVAL, "B=%d outside [1,%d]", B, c->maxB);
     const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V;
     hipStream_t st = c->stream;
-    int r = prepare_weights(c, p, false);
+    int r = prepare_weights(c, p);   // the forward shadows alone
     if (r) return r;
     const int Hs[4] = {H1, H1, H2, H2};
     const int ns = c->nl == 1 ? 2 : 4;  // LRCN-1f: state = {h, c}

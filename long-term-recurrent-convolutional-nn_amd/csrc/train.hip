@@ -1,5 +1,5 @@
 // train.hip -- the caption model's forward / backward pass on one gfx950 device, and its loss and train-step entry points (include/lrcn.h,
-// lrcn_varlen.h, lrcn_clip.h).
+// lrcn_varlen.h, lrcn_clip.h, lrcn_weighted.h, lrcn_sched.h), each of which describes its call in one LossCall (ctx.h) filled by member name.
 //
 // Orchestration of the hot path on one gfx950 device.  The reference runs lrcn() once per timestep with ~50 tiny
 // kernels and a blocking D2H per step (lrcn.jl:560-570); here everything that does not feed back through the
@@ -200,59 +200,60 @@ int upload_row_w(lrcn_ctx *c, const float *w, int B) { return upload_rows(c, w, 
 
 }  // namespace
 
-// loss / lossgradient on internal buffers. feats: B x 4096 column-major f32 (device).
-// lens != NULL (host, [B]): the variable-length form of include/lrcn_varlen.h -- row b has lens[b] + 1 loss terms, the scale is
+// loss / lossgradient on internal buffers, described by a LossCall (ctx.h).  q.feats: B x 4096 column-major f32 (device).
+// q.lens (host, [B]): the variable-length form of include/lrcn_varlen.h -- row b has lens[b] + 1 loss terms, the scale is
 // 1 / norm_tokens and norm_B is not used.  Only the token builder and the softmax-NLL kernel differ; every launch in between is the same.
-// row_w != NULL (host, [B], with lens): the weighted form of include/lrcn_weighted.h -- caption b's terms and d(logits) rows carry
+// q.row_w (host, [B], with lens): the weighted form of include/lrcn_weighted.h -- caption b's terms and d(logits) rows carry
 // row_w[b]; the chain after the softmax-NLL kernel is linear in d(logits), so only that launch differs.
-// ss != NULL (with lens): scheduled sampling of include/lrcn_sched.h.  eps == 0 changes nothing but the counters and fed_out; eps > 0 runs
+// q.ss (with lens): scheduled sampling of include/lrcn_sched.h.  eps == 0 changes nothing but the counters and fed_out; eps > 0 runs
 // the forward step by step (sched_forward below) into the same buffers and rejoins at the softmax-NLL launch.
-int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
-                         const lrcn_dropout *drop, float *const grads[9], float *logits_out, const int32_t *lens, int64_t norm_tokens,
-                         const float *row_w, const lrcn_sched *ss, int32_t *fed_out) {
-    int r = check_shapes(c, T, B, norm_B);
+int lrcn_impl::loss_impl(lrcn_ctx *c, const LossCall &q) {
+    const int T = q.T, B = q.B;
+    int r = check_shapes(c, T, B, q.norm_B);
     if (r) return r;
-    if (ss) {
-        if (!lens) FAIL(c, LRCN_EINVAL, "scheduled sampling needs lens");
-        if (!(ss->eps >= 0.0f && ss->eps <= 1.0f)) FAIL(c, LRCN_EINVAL, "sched eps=%g outside [0,1]", (double)ss->eps);
-        if (!(ss->temperature >= 0.0f) || std::isinf(ss->temperature))
-            FAIL(c, LRCN_EINVAL, "sched temperature=%g must be finite and >= 0", (double)ss->temperature);
-        if (ss->row0 < 0 || ss->row0 > ((int64_t)1 << 32) - B)
-            FAIL(c, LRCN_EINVAL, "sched row0=%lld: rows [row0, row0 + B) must lie in [0, 2^32)", (long long)ss->row0);
+    if (q.ss) {
+        if (!q.lens) FAIL(c, LRCN_EINVAL, "scheduled sampling needs lens");
+        if (!(q.ss->eps >= 0.0f && q.ss->eps <= 1.0f)) FAIL(c, LRCN_EINVAL, "sched eps=%g outside [0,1]", (double)q.ss->eps);
+        if (!(q.ss->temperature >= 0.0f) || std::isinf(q.ss->temperature))
+            FAIL(c, LRCN_EINVAL, "sched temperature=%g must be finite and >= 0", (double)q.ss->temperature);
+        if (q.ss->row0 < 0 || q.ss->row0 > ((int64_t)1 << 32) - B)
+            FAIL(c, LRCN_EINVAL, "sched row0=%lld: rows [row0, row0 + B) must lie in [0, 2^32)", (long long)q.ss->row0);
     }
-    const bool stepwise = ss && ss->eps > 0.0f;
-    if (lens) {
-        if (norm_tokens < 1) FAIL(c, LRCN_EINVAL, "norm_tokens=%lld must be >= 1", (long long)norm_tokens);
+    const bool stepwise = q.ss && q.ss->eps > 0.0f;
+    if (q.lens) {
+        if (q.norm_tokens < 1) FAIL(c, LRCN_EINVAL, "norm_tokens=%lld must be >= 1", (long long)q.norm_tokens);
         for (int b = 0; b < B; ++b)
-            if (lens[b] < 0 || lens[b] > T) FAIL(c, LRCN_EINVAL, "lens[%d]=%d outside [0,%d]", b, lens[b], T);
+            if (q.lens[b] < 0 || q.lens[b] > T) FAIL(c, LRCN_EINVAL, "lens[%d]=%d outside [0,%d]", b, q.lens[b], T);
     }
-    if (row_w) {
-        if (!lens) FAIL(c, LRCN_EINVAL, "row weights need lens");
+    if (q.row_w) {
+        if (!q.lens) FAIL(c, LRCN_EINVAL, "row weights need lens");
         for (int b = 0; b < B; ++b)
-            if (!std::isfinite(row_w[b])) FAIL(c, LRCN_EINVAL, "row_w[%d]=%g is not finite", b, (double)row_w[b]);
+            if (!std::isfinite(q.row_w[b])) FAIL(c, LRCN_EINVAL, "row_w[%d]=%g is not finite", b, (double)q.row_w[b]);
     }
-    if (drop && (drop->pdrop < 0.0f || drop->pdrop >= 1.0f)) FAIL(c, LRCN_EINVAL, "pdrop=%g outside [0,1)", drop->pdrop);
-    if (drop && c->nl == 2 && ((drop->mask1 == nullptr) != (drop->mask2 == nullptr))) FAIL(c, LRCN_EINVAL, "mask1/mask2 must both be set");
+    if (q.drop && (q.drop->pdrop < 0.0f || q.drop->pdrop >= 1.0f)) FAIL(c, LRCN_EINVAL, "pdrop=%g outside [0,1)", q.drop->pdrop);
+    if (q.drop && c->nl == 2 && ((q.drop->mask1 == nullptr) != (q.drop->mask2 == nullptr))) FAIL(c, LRCN_EINVAL, "mask1/mask2 must both be set");
     const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V, X1 = c->X1;
     const int S = T + 1, M = S * B;
     const size_t es = c->esz;
     hipStream_t st = c->stream;
-    const bool bwd = grads != nullptr, two = c->nl == 2;
-    if (bwd && (!grads[0] || !grads[1] || !grads[5] || !grads[6] || !grads[7] || !grads[8] || (two && (!grads[2] || !grads[3] || !grads[4]))))
+    const bool bwd = q.grads != nullptr, two = c->nl == 2;
+    if (bwd && (!q.grads[0] || !q.grads[1] || !q.grads[5] || !q.grads[6] || !q.grads[7] || !q.grads[8] || (two && (!q.grads[2] || !q.grads[3] || !q.grads[4]))))
         FAIL(c, LRCN_EINVAL, "null gradient tensor");
-    const DropSpec d1 = make_drop(drop, 1), d2 = make_drop(drop, 2);
+    const DropSpec d1 = make_drop(q.drop, 1), d2 = make_drop(q.drop, 2);
     const DropSpec none{};
 
     c->cur_B = B;
     const bool epi = !stepwise && lstm_epi_on(c, B) && !lstm_fused_on(c->dt, B, H1, c->ldH1, c->ld4H1);  // (no cell epilogues in the stepwise forward)
-    r = prepare_weights(c, p, bwd, false, epi);
+    ShadowNeed sh{};
+    sh.bwd = bwd; sh.gi = epi;
+    r = prepare_weights(c, q.p, sh);
     if (r) return r;
-    if (lens) {
-        if ((r = upload_lens(c, lens, B))) return r;
-        k_build_tokens_var(st, tokens, c->lens_dev, T, B, V, c->tok_in, c->tok_tgt, c->logp);
-        if (row_w && (r = upload_row_w(c, row_w, B))) return r;
+    if (q.lens) {
+        if ((r = upload_lens(c, q.lens, B))) return r;
+        k_build_tokens_var(st, q.tokens, c->lens_dev, T, B, V, c->tok_in, c->tok_tgt, c->logp);
+        if (q.row_w && (r = upload_row_w(c, q.row_w, B))) return r;
     } else {
-        k_build_tokens(st, tokens, T, B, V, c->tok_in, c->tok_tgt, c->logp);  // reads the caller's (T, B) ids once (T = 0: never)
+        k_build_tokens(st, q.tokens, T, B, V, c->tok_in, c->tok_tgt, c->logp);  // reads the caller's (T, B) ids once (T = 0: never)
     }
     // input = input * param[end-3]   lrcn.jl:558.  The two-layer model needs x_cnn only at LSTM-2's input, after the whole first
     // recurrence: its three launches (transpose, split-K GEMM, reduce: ~20 us at 32 rows) run on the weight-gradient stream beside that
@@ -263,13 +264,13 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     const bool xfork = two && par && !stepwise;
     auto image_embedding = [&](hipStream_t s_, bool on_wg) -> int {
         // feats (B x 4096 column-major = memory [4096][B]) -> F [B][4096] (T)
-        k_transpose(s_, dt, 1, feats, B, LRCN_CNNOUT, B, c->F, LRCN_CNNOUT, 0);
+        k_transpose(s_, dt, 1, q.feats, B, LRCN_CNNOUT, B, c->F, LRCN_CNNOUT, 0);
         return gemm(c, dt, c->F, LRCN_CNNOUT, c->Wcd, LRCN_CNNOUT, c->xcnn, c->ldh, B, h, LRCN_CNNOUT, nullptr, true, false, false, false, on_wg);
     };
-    if (ss) {
+    if (q.ss) {
         if (!c->sched_cnt) DALLOC(c, c->sched_cnt, 2 * sizeof(long long));
         long long eligible = 0;
-        for (int b = 0; b < B; ++b) eligible += lens[b];
+        for (int b = 0; b < B; ++b) eligible += q.lens[b];
         k_sched_stats_set(st, c->sched_cnt, stepwise ? 0 : eligible, 0);  // the stepwise route counts its coins on the device
     }
     // Scheduled sampling with eps > 0: step s+1's input is a function of step s's logits, so nothing is time-batched.  Per step, on the rows
@@ -287,26 +288,26 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
             const int64_t m0 = (int64_t)s * B;
             void *Xs = boff(c->Xemb, m0 * c->ldX1, es);
             if (!two) k_concat_x2(st, dt, Xs, c->ldX1, c->xcnn, c->ldh, 1, B, E, h, d1, s);
-            GEMM(c, dt, Xs, c->ldX1, c->W1x, c->ldX1, c->G1 + m0 * 4 * H1, 4 * H1, B, 4 * H1, X1, p[1], true);
+            GEMM(c, dt, Xs, c->ldX1, c->W1x, c->ldX1, c->G1 + m0 * 4 * H1, 4 * H1, B, 4 * H1, X1, q.p[1], true);
             if (int e = lstm_step_fwd(c, alone, rg, fused1, s, B, H1, c->ldH1, c->ld4H1, c->G1, c->W1h, c->A1, c->C1, c->H1all)) return e;
             const void *Hs = boff(c->H1all, m0 * c->ldH1, es);
             if (two) {
                 void *X2s = boff(c->X2, m0 * c->ldH2, es);
                 GEMM(c, dt, Hs, c->ldH1, c->Wpd, c->ldH1, X2s, c->ldH2, B, h, H1, nullptr, false);
                 k_concat_x2(st, dt, X2s, c->ldH2, c->xcnn, c->ldh, 1, B, h, h, d2, s);
-                GEMM(c, dt, X2s, c->ldH2, c->W2x, c->ldH2, c->G2 + m0 * 4 * H2, 4 * H2, B, 4 * H2, H2, p[3], true);
+                GEMM(c, dt, X2s, c->ldH2, c->W2x, c->ldH2, c->G2 + m0 * 4 * H2, 4 * H2, B, 4 * H2, H2, q.p[3], true);
                 if (int e = lstm_step_fwd(c, alone, rg, fused2, s, B, H2, c->ldH2, c->ld4H2, c->G2, c->W2h, c->A2, c->C2, c->H2all)) return e;
                 Hs = boff(c->H2all, m0 * c->ldH2, es);
             }
-            GEMM(c, dt, Hs, c->ldH2, c->Wod, c->ldH2, c->Logits + m0 * c->ldV, c->ldV, B, V, H2, p[8], true);
+            GEMM(c, dt, Hs, c->ldH2, c->Wod, c->ldH2, c->Logits + m0 * c->ldV, c->ldV, B, V, H2, q.p[8], true);
             if (s + 1 < S) {
                 SchedNext a{};
                 a.logits = c->Logits + m0 * c->ldV; a.ld_l = c->ldV;
                 a.V = V; a.B = B; a.s_next = s + 1;
                 a.lens = c->lens_dev;
-                a.eps = ss->eps; a.temp = ss->temperature;
-                a.k0 = (uint32_t)ss->seed; a.k1 = (uint32_t)(ss->seed >> 32);
-                a.row0 = (uint32_t)ss->row0;
+                a.eps = q.ss->eps; a.temp = q.ss->temperature;
+                a.k0 = (uint32_t)q.ss->seed; a.k1 = (uint32_t)(q.ss->seed >> 32);
+                a.row0 = (uint32_t)q.ss->row0;
                 a.tok_in = c->tok_in;
                 a.wembT = c->WeT; a.ld_w = c->ldE; a.E = E;
                 a.d = two ? d1 : none;
@@ -339,7 +340,7 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
         }
         if (!two) k_concat_x2(st, dt, c->Xemb, c->ldX1, c->xcnn, c->ldh, S, B, E, h, d1);
         // LSTM 1
-        GEMM(c, dt, c->Xemb, c->ldX1, c->W1x, c->ldX1, c->G1, 4 * H1, M, 4 * H1, X1, p[1], true);
+        GEMM(c, dt, c->Xemb, c->ldX1, c->W1x, c->ldX1, c->G1, 4 * H1, M, 4 * H1, X1, q.p[1], true);
         return lstm_layer_fwd(c, S, B, H1, c->ldH1, c->ld4H1, c->G1, c->W1h, c->A1, c->C1, c->H1all, epi ? c->W1h_gi : nullptr);
     };
     if (!stepwise) r = first_layer();
@@ -354,26 +355,26 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
         GEMM(c, dt, c->H1all, c->ldH1, c->Wpd, c->ldH1, c->X2, c->ldH2, M, h, H1, nullptr, false);
         k_concat_x2(st, dt, c->X2, c->ldH2, c->xcnn, c->ldh, S, B, h, h, d2);
         // LSTM 2
-        GEMM(c, dt, c->X2, c->ldH2, c->W2x, c->ldH2, c->G2, 4 * H2, M, 4 * H2, H2, p[3], true);
+        GEMM(c, dt, c->X2, c->ldH2, c->W2x, c->ldH2, c->G2, 4 * H2, M, 4 * H2, H2, q.p[3], true);
         r = lstm_layer_fwd(c, S, B, H2, c->ldH2, c->ld4H2, c->G2, c->W2h, c->A2, c->C2, c->H2all, epi ? c->W2h_gi : nullptr);
         if (r) return r;
     }
     // logits for all steps: x * w[end-1] .+ w[end]   lrcn.jl:550
-    if (!stepwise) GEMM(c, dt, Htop, c->ldH2, c->Wod, c->ldH2, c->Logits, c->ldV, M, V, H2, p[8], true);
-    if (fed_out) HIPCHK(c, hipMemcpyAsync(fed_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
-    if (logits_out) {  // (T+1) blocks of B x V column-major: block s memory [V][B]
+    if (!stepwise) GEMM(c, dt, Htop, c->ldH2, c->Wod, c->ldH2, c->Logits, c->ldV, M, V, H2, q.p[8], true);
+    if (q.fed_out) HIPCHK(c, hipMemcpyAsync(q.fed_out, c->tok_in, sizeof(int32_t) * (size_t)M, hipMemcpyDeviceToDevice, st));
+    if (q.logits_out) {  // (T+1) blocks of B x V column-major: block s memory [V][B]
         for (int s = 0; s < S; ++s)
-            k_transpose_f32(st, c->Logits + (int64_t)s * B * c->ldV, c->ldV, B, V, logits_out + (int64_t)s * B * V, B);
+            k_transpose_f32(st, c->Logits + (int64_t)s * B * c->ldV, c->ldV, B, V, q.logits_out + (int64_t)s * B * V, B);
     }
-    const float scale = (float)(1.0 / (lens ? (double)norm_tokens : (double)norm_B * (double)S));
+    const float scale = (float)(1.0 / (q.lens ? (double)q.norm_tokens : (double)q.norm_B * (double)S));
     if (c->opt_det && !c->logp_rows) DALLOC(c, c->logp_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
     void *const dlog = bwd ? c->dLog : nullptr;
     double *const rows = c->opt_det ? c->logp_rows : nullptr;
-    if (row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
-    else (lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows);
-    c->last_norm = norm_B;
+    if (q.row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
+    else (q.lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows);
+    c->last_norm = q.norm_B;
     c->last_S = S;
-    c->last_tokens = lens ? norm_tokens : 0;
+    c->last_tokens = q.lens ? q.norm_tokens : 0;
     KCHK(c, "forward");
     if (!bwd) return LRCN_OK;
 
@@ -419,8 +420,8 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     // dWcnn = d x_cnn' feats on sw, the last tensor of group 2 in either model
     auto image_embedding_grad = [&]() -> int {
         k_transpose(sw, dt, 1, c->dxcnn, c->ldh, B, h, c->dxcT, ldB, 0);     // dxcnn^T [h][ldB]
-        k_cast_rows(sw, dt, feats, B, LRCN_CNNOUT, B, c->FT, ldB);           // feats^T [4096][ldB] (it already is, in memory)
-        GEMM(c, dt, c->dxcT, ldB, c->FT, ldB, grads[5], LRCN_CNNOUT, h, LRCN_CNNOUT, B, nullptr, true, false, false, false, par);
+        k_cast_rows(sw, dt, q.feats, B, LRCN_CNNOUT, B, c->FT, ldB);           // feats^T [4096][ldB] (it already is, in memory)
+        GEMM(c, dt, c->dxcT, ldB, c->FT, ldB, q.grads[5], LRCN_CNNOUT, h, LRCN_CNNOUT, B, nullptr, true, false, false, false, par);
         HIPCHK(c, hipEventRecord(c->grad_ev[2], sw));  // group 2: (Wproj,) Wcnn
         return LRCN_OK;
     };
@@ -430,14 +431,14 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
     auto backward = [&]() -> int {
     // ---- logits layer: dWout, dbout (sw) | dH2 (main) ----
         if (int e = fork()) return e;
-        if (int e = weight_grad(c->dLog, c->ldV, V, Htop, c->ldH2, H2, nullptr, 0, 0, grads[7], grads[8])) return e;
+        if (int e = weight_grad(c->dLog, c->ldV, V, Htop, c->ldH2, H2, nullptr, 0, 0, q.grads[7], q.grads[8])) return e;
         HIPCHK(c, hipEventRecord(c->grad_ev[0], sw));  // group 0: Wout, bout
         GEMM(c, dt, c->dLog, c->ldV, c->WoT, c->ldV, two ? c->dH2all : c->dH1all, H2, M, H2, V, nullptr, true);
         if (two) {
             // ---- LSTM 2 ----
             if (int e = lstm_layer_bwd(c, S, B, H2, c->ld4H2, c->A2, c->C2, c->dH2all, c->W2hT, c->dZ2)) return e;
             if (int e = fork()) return e;
-            if (int e = weight_grad(c->dZ2, c->ld4H2, 4 * H2, c->X2, c->ldH2, H2, c->H2all, c->ldH2, H2, grads[2], grads[3])) return e;
+            if (int e = weight_grad(c->dZ2, c->ld4H2, 4 * H2, c->X2, c->ldH2, H2, c->H2all, c->ldH2, H2, q.grads[2], q.grads[3])) return e;
         }
         HIPCHK(c, hipEventRecord(c->grad_ev[1], sw));  // group 1: W2, b2
         if (two) {
@@ -445,14 +446,14 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
             k_dx2_mask_reduce(st, dt, c->dX2, c->ldH2, S, B, h, h, d2, c->dxcnn, c->ldh);
             // ---- projection and image embedding: dWproj, dWcnn (sw) | dH1 (main) ----
             if (int e = fork()) return e;
-            if (int e = weight_grad(c->dX2, c->ldH2, h, c->H1all, c->ldH1, H1, nullptr, 0, 0, grads[4], nullptr)) return e;
+            if (int e = weight_grad(c->dX2, c->ldH2, h, c->H1all, c->ldH1, H1, nullptr, 0, 0, q.grads[4], nullptr)) return e;
             GEMM(c, dt, c->dX2, c->ldH2, c->WpT, c->ldh, c->dH1all, H1, M, H1, h, nullptr, true);
             if (int e = image_embedding_grad()) return e;
         }
         // ---- LSTM 1 ----
         if (int e = lstm_layer_bwd(c, S, B, H1, c->ld4H1, c->A1, c->C1, c->dH1all, c->W1hT, c->dZ1)) return e;
         if (int e = fork()) return e;
-        if (int e = weight_grad(c->dZ1, c->ld4H1, 4 * H1, c->Xemb, c->ldX1, X1, c->H1all, c->ldH1, H1, grads[0], grads[1])) return e;
+        if (int e = weight_grad(c->dZ1, c->ld4H1, 4 * H1, c->Xemb, c->ldX1, X1, c->H1all, c->ldH1, H1, q.grads[0], q.grads[1])) return e;
         HIPCHK(c, hipEventRecord(c->grad_ev[3], sw));  // group 3: W1, b1
         GEMM(c, dt, c->dZ1, c->ld4H1, c->W1xT, c->ld4H1, c->dXemb, c->ldX1, M, X1, 4 * H1, nullptr, true);
         if (!two) {
@@ -477,7 +478,7 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const float *const p[9], const float *feat
                 keys = c->sort_keys;
             }
             // declines only with sort keys: more rows than the counting sort ranks
-            if (!k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, grads[6], keys))
+            if (!k_embed_scatter_rm(st, c->dXemb, c->ldX1, c->tok_in, S, B, E, V, two ? d1 : none, c->dWe_rm, c->ldE, q.grads[6], keys))
                 FAIL(c, LRCN_EINVAL, "LRCN_OPT_DETERMINISTIC supports (T+1)*B <= 8192 rows per call (got %d)", M);
         }
         HIPCHK(c, hipEventRecord(c->grad_ev[4], st));  // group 4: Wembed
@@ -512,48 +513,39 @@ int lrcn_impl::fetch_loss(lrcn_ctx *c, double *out) {
 
 namespace {
 
-// The body of the lrcn_loss* entry points.  var: the variable-length form, whose lens must be given (the other passes NULL);
-// weighted: that form with row_w, which must be given too; grads NULL: the loss alone.  sched (include/lrcn_sched.h): the variable-length form
-// with ss, which must be given, an optional row_w and the optional outputs fed / logits.
-struct SchedIo {
-    const lrcn_sched *ss;
-    int32_t *fed;
-    float *logits;
-};
-int loss_entry(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, bool var, const int32_t *lens, int T, int B,
-               int norm_B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host, bool weighted = false,
-               const float *row_w = nullptr, const SchedIo *sched = nullptr) {
+// The body of the lrcn_loss* entry points: q.form says which of lens / row_w / ss the entry point requires (the others it leaves NULL, but
+// for the scheduled-sampling form's optional row_w); q.grads NULL: the loss alone.
+int loss_entry(lrcn_ctx *c, const LossCall &q, double *loss_host) {
     DeviceGuard dg(c);
-    if (!c || !p || !feats || (!tokens && T > 0)) return LRCN_EINVAL;
-    if (var && !lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
-    if (weighted && !row_w) FAIL(c, LRCN_EINVAL, "row_w is NULL");
-    if (sched && !sched->ss) FAIL(c, LRCN_EINVAL, "the lrcn_sched argument is NULL");
-    int r = sched ? loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, sched->logits, lens, norm_tokens, row_w, sched->ss, sched->fed)
-                  : loss_impl(c, p, feats, tokens, T, B, norm_B, drop, grads, nullptr, lens, norm_tokens, row_w);
+    if (!c || !q.p || !q.feats || (!q.tokens && q.T > 0)) return LRCN_EINVAL;
+    if (q.form != LossCall::PLAIN && !q.lens) FAIL(c, LRCN_EINVAL, "lens is NULL");
+    if (q.form == LossCall::WEIGHTED && !q.row_w) FAIL(c, LRCN_EINVAL, "row_w is NULL");
+    if (q.form == LossCall::SCHED && !q.ss) FAIL(c, LRCN_EINVAL, "the lrcn_sched argument is NULL");
+    int r = loss_impl(c, q);
     if (r) return r;
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
 }
 
-// The body of the lrcn_train_step* entry points: lossgradient, then update! -- with max_norm > 0 on the gradient clipped to that
-// global norm (the nine sums of squares, norm / scale / skip and the clipped update, all on the context's stream).
-int train_step_impl(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
-                    const int32_t *tokens, bool var, const int32_t *lens, int T, int B, int norm_B, int64_t norm_tokens,
-                    const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host,
-                    bool weighted = false, const float *row_w = nullptr, const SchedIo *sched = nullptr) {
+// The body of the lrcn_train_step* entry points: lossgradient (q, whose p is set here and whose grads the entry point sets), then update! --
+// with max_norm > 0 on the gradient clipped to that global norm (the nine sums of squares, norm / scale / skip and the clipped update, all
+// on the context's stream).
+int train_step_impl(lrcn_ctx *c, LossCall q, float *const p[9], float *const m[9], float *const v[9], int step, float lr, float b1, float b2,
+                    float eps, float max_norm, double *loss_host) {
     DeviceGuard dg(c);
-    if (!c || !p || !g || !m || !v) return LRCN_EINVAL;
+    if (!c || !p || !q.grads || !m || !v) return LRCN_EINVAL;
     if (std::isnan(max_norm)) FAIL(c, LRCN_EINVAL, "max_norm is NaN");
     const bool clip = max_norm > 0.0f;
     if (clip && step < 1) return LRCN_EINVAL;  // (the unclipped step finds a bad `step` in its update, after the pass)
-    int r = loss_entry(c, p, feats, tokens, var, lens, T, B, norm_B, norm_tokens, drop, g, nullptr, weighted, row_w, sched);
+    q.p = p;
+    int r = loss_entry(c, q, nullptr);
     if (r) return r;
     if (clip) {
-        r = lrcn_grad_sumsq_model(c, g, -1, nullptr);
+        r = lrcn_grad_sumsq_model(c, q.grads, -1, nullptr);
         if (r || (r = lrcn_clip_set(c, LRCN_CLIP_SLOTS, max_norm, nullptr))) return r;
     } else if (step < 1) {
         return LRCN_EINVAL;
     }
-    r = adam_update(c, p, g, m, v, step, lr, b1, b2, eps, clip);
+    r = adam_update(c, p, q.grads, m, v, step, lr, b1, b2, eps, clip);
     if (r) return r;
     return loss_host ? fetch_loss(c, loss_host) : LRCN_OK;
 }
@@ -564,25 +556,35 @@ extern "C" {
 
 int lrcn_loss(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
               const lrcn_dropout *drop, double *loss_host) {
-    return loss_entry(c, p, feats, tokens, false, nullptr, T, B, norm_B, 0, drop, nullptr, loss_host);
+    LossCall q{};
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = norm_B; q.drop = drop;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_loss_grad(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, int norm_B,
                    const lrcn_dropout *drop, float *const grads[9], double *loss_host) {
     if (!grads) return LRCN_EINVAL;
-    return loss_entry(c, p, feats, tokens, false, nullptr, T, B, norm_B, 0, drop, grads, loss_host);
+    LossCall q{};
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = norm_B; q.drop = drop; q.grads = grads;
+    return loss_entry(c, q, loss_host);
 }
 
 // ---- include/lrcn_varlen.h: per-row caption lengths ----
 int lrcn_loss_var(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, int T, int B,
                   int64_t norm_tokens, const lrcn_dropout *drop, double *loss_host) {
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, nullptr, loss_host);
+    LossCall q{};
+    q.form = LossCall::VAR; q.lens = lens; q.norm_tokens = norm_tokens;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_loss_grad_var(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, int T, int B,
                        int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9], double *loss_host) {
     if (!grads) return LRCN_EINVAL;
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, grads, loss_host);
+    LossCall q{};
+    q.form = LossCall::VAR; q.lens = lens; q.norm_tokens = norm_tokens;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = grads;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_grad_group_wait(lrcn_ctx *c, int group, void *stream) {
@@ -602,82 +604,104 @@ int lrcn_forward_logits(lrcn_ctx *c, const float *const p[9], const float *feats
                         float *logits_out) {
     DeviceGuard dg(c);
     if (!c || !p || !feats || (!tokens && T > 0) || !logits_out) return LRCN_EINVAL;
-    return loss_impl(c, p, feats, tokens, T, B, B, nullptr, nullptr, logits_out);
+    LossCall q{};
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = B; q.logits_out = logits_out;
+    return loss_impl(c, q);
 }
 
 int lrcn_avg_loss_batch(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, int T, int B, double *loss_host) {
     // average_loss's loop body (lrcn.jl:452-475): pdrop 0, normalised by the batch's own size (lrcn.jl:412)
-    return lrcn_loss(c, p, feats, tokens, T, B, B, nullptr, loss_host);
+    LossCall q{};
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = B;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_train_step(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                     const int32_t *tokens, int T, int B, int norm_B, const lrcn_dropout *drop, int step, float lr, float b1,
                     float b2, float eps, double *loss_host) {
-    return train_step_impl(c, p, g, m, v, feats, tokens, false, nullptr, T, B, norm_B, 0, drop, step, lr, b1, b2, eps, 0.0f, loss_host);
+    return lrcn_train_step_clip(c, p, g, m, v, feats, tokens, T, B, norm_B, drop, step, lr, b1, b2, eps, /* max_norm */ 0.0f, loss_host);
 }
 
 int lrcn_train_step_var(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                         const int32_t *tokens, const int32_t *lens, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, int step,
                         float lr, float b1, float b2, float eps, double *loss_host) {
-    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, 0.0f, loss_host);
+    return lrcn_train_step_var_clip(c, p, g, m, v, feats, tokens, lens, T, B, norm_tokens, drop, step, lr, b1, b2, eps, /* max_norm */ 0.0f, loss_host);
 }
 
 // ---- include/lrcn_clip.h: max_norm <= 0 is the unclipped step ----
 int lrcn_train_step_clip(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                          const int32_t *tokens, int T, int B, int norm_B, const lrcn_dropout *drop, int step, float lr, float b1, float b2,
                          float eps, float max_norm, double *loss_host) {
-    return train_step_impl(c, p, g, m, v, feats, tokens, false, nullptr, T, B, norm_B, 0, drop, step, lr, b1, b2, eps, max_norm, loss_host);
+    LossCall q{};
+    q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = norm_B; q.drop = drop; q.grads = g;
+    return train_step_impl(c, q, p, m, v, step, lr, b1, b2, eps, max_norm, loss_host);
 }
 
 int lrcn_train_step_var_clip(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                              const int32_t *tokens, const int32_t *lens, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop,
                              int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
-    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host);
+    LossCall q{};
+    q.form = LossCall::VAR; q.lens = lens; q.norm_tokens = norm_tokens;
+    q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = g;
+    return train_step_impl(c, q, p, m, v, step, lr, b1, b2, eps, max_norm, loss_host);
 }
 
 // ---- include/lrcn_weighted.h: a real weight per caption row ----
 int lrcn_loss_w(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, const float *row_w,
                 int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, double *loss_host) {
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, nullptr, loss_host, true, row_w);
+    LossCall q{};
+    q.form = LossCall::WEIGHTED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_loss_grad_w(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens,
                      const float *row_w, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, float *const grads[9],
                      double *loss_host) {
     if (!grads) return LRCN_EINVAL;
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, grads, loss_host, true, row_w);
+    LossCall q{};
+    q.form = LossCall::WEIGHTED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = grads;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_train_step_w(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                       const int32_t *tokens, const int32_t *lens, const float *row_w, int T, int B, int64_t norm_tokens,
                       const lrcn_dropout *drop, int step, float lr, float b1, float b2, float eps, float max_norm, double *loss_host) {
-    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host,
-                           true, row_w);
+    LossCall q{};
+    q.form = LossCall::WEIGHTED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens;
+    q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = g;
+    return train_step_impl(c, q, p, m, v, step, lr, b1, b2, eps, max_norm, loss_host);
 }
 
-// ---- include/lrcn_sched.h: scheduled sampling ----
+// ---- include/lrcn_sched.h: scheduled sampling (row_w optional) ----
 int lrcn_loss_sched(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, const float *row_w,
                     int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss, int32_t *fed_out, float *logits_out,
                     double *loss_host) {
-    const SchedIo io{ss, fed_out, logits_out};
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, nullptr, loss_host, false, row_w, &io);
+    LossCall q{};
+    q.form = LossCall::SCHED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens; q.ss = ss; q.fed_out = fed_out; q.logits_out = logits_out;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_loss_grad_sched(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens,
                          const float *row_w, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss,
                          float *const grads[9], int32_t *fed_out, float *logits_out, double *loss_host) {
     if (!grads) return LRCN_EINVAL;
-    const SchedIo io{ss, fed_out, logits_out};
-    return loss_entry(c, p, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, grads, loss_host, false, row_w, &io);
+    LossCall q{};
+    q.form = LossCall::SCHED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens; q.ss = ss; q.fed_out = fed_out; q.logits_out = logits_out;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = grads;
+    return loss_entry(c, q, loss_host);
 }
 
 int lrcn_train_step_sched(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
                           const int32_t *tokens, const int32_t *lens, const float *row_w, int T, int B, int64_t norm_tokens,
                           const lrcn_dropout *drop, const lrcn_sched *ss, int step, float lr, float b1, float b2, float eps, float max_norm,
                           double *loss_host) {
-    const SchedIo io{ss, nullptr, nullptr};
-    return train_step_impl(c, p, g, m, v, feats, tokens, true, lens, T, B, 1, norm_tokens, drop, step, lr, b1, b2, eps, max_norm, loss_host,
-                           false, row_w, &io);
+    LossCall q{};
+    q.form = LossCall::SCHED; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens; q.ss = ss;
+    q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = g;
+    return train_step_impl(c, q, p, m, v, step, lr, b1, b2, eps, max_norm, loss_host);
 }
 
 int lrcn_sched_stats(lrcn_ctx *c, int64_t *eligible, int64_t *drawn) {

@@ -184,7 +184,9 @@ int lrcn_train_step_dp(lrcn_ctx *c, float *const p[9], float *const g[9], float 
         if (normalize) k_normalize_rows(c->stream, feats, B, LRCN_CNNOUT);
         KCHK(c, "train_step_dp (vgg)");
     }
-    r = loss_impl(c, p, feats, tokens, T, B, norm_B, drop, g, nullptr);
+    LossCall q{};
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.norm_B = norm_B; q.drop = drop; q.grads = g;
+    r = loss_impl(c, q);
     if (r) return r;
     if (!c->comm || (comm_world(c->comm) == 1 && !dp_force_pipeline())) {  // one rank: nothing to hide the update behind -- one Adam launch
         r = adam_update(c, p, g, m, v, step, lr, b1, b2, eps, false);

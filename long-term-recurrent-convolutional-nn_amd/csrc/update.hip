@@ -176,20 +176,19 @@ int adam_update_flat(lrcn_ctx *c, float *w, const float *g, float *m, float *v, 
 }  // namespace
 
 // f32 column-major params -> K-contiguous shadows in T (direct and transposed).  See DESIGN.md "shadow weights".
-int lrcn_impl::prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_bwd, bool cat, bool gi, bool cat_perm,
-                    bool dec_tables) {   // dec_tables: the interleaved recurrent copies + W2 without its x_cnn columns (a decode call: not sticky)
+int lrcn_impl::prepare_weights(lrcn_ctx *c, const float *const p[9], const ShadowNeed &need) {
     const int dt = c->dt, H1 = c->H1, H2 = c->H2, X1 = c->X1;
     if (!p[0] || !p[1] || !p[5] || !p[6] || !p[7] || !p[8] || (c->nl == 2 && (!p[2] || !p[3] || !p[4]))) FAIL(c, LRCN_EINVAL, "null parameter tensor");
     hipStream_t st = c->stream;
     const bool two = c->nl == 2;
     // LRCN_OPT_FUSED_UPDATE: the previous train step's Adam kernel already wrote this set from these very parameters
-    if (gi || dec_tables) {
+    if (need.gi || need.dec_tables) {
         int rg = ensure_gi_sets(c);
         if (rg) return rg;
-        if (gi) c->gi_live = true;   // from now on the fused update writes the interleaved copies with the other shadows
+        if (need.gi) c->gi_live = true;   // from now on the fused update writes the interleaved copies with the other shadows
     }
-    if (dec_tables) gi = true;
-    if (c->opt_fused && c->shadow_valid && !cat && (!gi || c->shadow_has_gi)) {
+    const bool gi = need.gi || need.dec_tables;   // (dec_tables makes the interleaved copies without making them sticky)
+    if (c->opt_fused && c->shadow_valid && !need.cat && (!gi || c->shadow_has_gi)) {
         bool same = true;
         for (int k = 0; k < 9; ++k) same = same && c->shadow_p[k] == p[k];
         if (same) return LRCN_OK;
@@ -198,8 +197,8 @@ int lrcn_impl::prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_b
     c->refresh_groups = 0;  // a full shadow pass supersedes a per-group refresh sequence that was left unfinished
     PrepPlan plan{};
     void *const gi_cur[2] = {c->W1h_gi, c->W2h_gi};
-    plan_matrices(c, p, cur_shadows(c), need_bwd, plan, -1, -1, gi ? gi_cur : nullptr);
-    if (dec_tables && c->nl == 2) {
+    plan_matrices(c, p, cur_shadows(c), need.bwd, plan, -1, -1, gi ? gi_cur : nullptr);
+    if (need.dec_tables && c->nl == 2) {
         // W2 (memory [4H2][2 H2]: columns [h1 Wproj (h) | x_cnn (h) | h2 (H2)]) -> dec_W2c [4H2][ldh + ldH2] = [proj columns | h2 columns], rows
         // (unit, gate)-interleaved: two descriptors over the same source, each with one live side
         const int64_t ld = c->ldh + c->ldH2;
@@ -210,13 +209,13 @@ int lrcn_impl::prepare_weights(lrcn_ctx *c, const float *const p[9], bool need_b
         b = PrepDesc{};
         b.src = p[2]; b.R = 4 * H2; b.C = 2 * H2; b.cs = H2; b.dB = boff(c->dec_W2c, c->ldh, c->esz); b.ldB = ld; b.permH = H2;
     }
-    if (cat) {  // batched decode: W1 / W2 with the x and h column blocks each padded to whole K-steps, side by side
+    if (need.cat) {  // batched decode: W1 / W2 with the x and h column blocks each padded to whole K-steps, side by side
         // cat_perm: the rows in (unit, gate)-interleaved order, for the decode step with the cell math in the GEMM's epilogue
         auto add = [&](const float *src, int R, int C, int cs, void *dA, int64_t ldA, void *dB, int64_t ldB, int permH) {
             PrepDesc &d = plan.d[plan.n++];
             d = PrepDesc{};
             d.src = src; d.R = R; d.C = C; d.cs = cs; d.dA = dA; d.ldA = ldA; d.dB = dB; d.ldB = ldB;
-            d.permH = cat_perm ? permH : 0;
+            d.permH = need.cat_perm ? permH : 0;
         };
         add(p[0], 4 * H1, X1 + H1, X1, c->W1cat, c->ldXH1, boff(c->W1cat, c->ldX1, c->esz), c->ldXH1, H1);
         if (two) add(p[2], 4 * H2, 2 * H2, H2, c->W2cat, c->ldXH2, boff(c->W2cat, c->ldH2, c->esz), c->ldXH2, H2);

@@ -270,50 +270,11 @@ def lrcn(ctx, w, s, x_cnn, x_lstm, mask1=None, mask2=None):
     return logits
 
 
-def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None,
-         sched=None):
-    """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
-    tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
-    lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
-    norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used.
-    row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h).
-    sched (Sched, or (eps, temperature, seed[, row0])): scheduled sampling (include/lrcn_sched.h); lens then defaults to [T] * B."""
-    tok = _tokens(tokens, feats.device)
-    T, B = tok.shape
-    ss = _sched(sched, B) if sched is not None else None
-    if ss is not None:
-        lens = _sched_lens(lens, T, B)
-    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
-    d, keep = _dropout(pdrop, seed, mask1, mask2)
-    out = C.c_double()
-    if ss is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        ctx._call("lrcn_loss_sched", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1] if wa else None, T, B, nt,
-                  C.byref(d) if d else None, C.byref(ss), None, None, C.byref(out))
-        del keep, la, wa
-        return out.value
-    if wa is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        ctx._call("lrcn_loss_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
-                  C.byref(out))
-        del keep, la, wa
-        return out.value
-    if lens is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        ctx._call("lrcn_loss_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None, C.byref(out))
-        del keep, la
-        return out.value
-    ctx._call("lrcn_loss", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), T, B, norm_B or B,
-              C.byref(d) if d else None, C.byref(out))
-    del keep
-    return out.value
-
-
-def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
-                 want_loss=True, lens=None, norm_tokens=None, row_weights=None, sched=None, return_fed=False, return_logits=False):
-    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights /
-    sched: as loss().  With sched, return_fed / return_logits append the words that were fed ((T+1, B) int32 numpy) and the logits the
-    draws were made from ((T+1, B, V) float32 numpy) to the result."""
+def _caption_call(ctx, param, feats, tokens, norm_B, drop, lens, norm_tokens, row_weights, sched, want_loss=True, grads=None, optim=None,
+                  gclip=0.0, return_fed=False, return_logits=False):
+    """The one path of loss / lossgradient / train_step (optim given) to the library -> (loss or None, fed, logits).  The entry point is named
+    by the first of sched, row_weights, lens that is given: lrcn_{loss, loss_grad, train_step}{_sched, _w, _var, ""}, and a step with neither
+    sched nor row_weights takes max_norm (gclip) only as lrcn_train_step[_var]_clip.  Every check runs before optim.t moves."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     ss = _sched(sched, B) if sched is not None else None
@@ -322,40 +283,62 @@ def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask
     if ss is not None:
         lens = _sched_lens(lens, T, B)
     wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
+    la = _lens(lens, T, B, norm_tokens) if lens is not None else None
+    d, keep = _dropout(*drop)
+    form = "_sched" if ss is not None else "_w" if wa is not None else "_var" if la is not None else ""
+    name = ("lrcn_train_step" if optim is not None else "lrcn_loss_grad" if grads is not None else "lrcn_loss") + form
+    args = [_p9(param)] + ([_p9(grads), _p9(optim.m), _p9(optim.v)] if optim is not None else []) + [_ptr(feats), C.c_void_p(tok.data_ptr())]
+    if la is not None:
+        args.append(la[1])
+    if form in ("_sched", "_w"):
+        args.append(wa[1] if wa else None)
+    args += [T, B, la[2] if la is not None else norm_B or B, C.byref(d) if d else None] + ([C.byref(ss)] if ss is not None else [])
+    fed = torch.empty((T + 1, B), device=feats.device, dtype=torch.int32) if return_fed else None
+    logits = torch.empty((T + 1, ctx.V, B), device=feats.device, dtype=torch.float32) if return_logits else None  # blocks of B x V column-major
+    if optim is not None:
+        optim.t += 1
+        args += [optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps]
+        if form in ("_sched", "_w"):   # these two always take max_norm, the others only as their _clip namesakes
+            args.append(gclip)
+        elif gclip > 0:
+            name += "_clip"
+            args.append(gclip)
+    else:
+        args += [_p9(grads)] if grads is not None else []
+        if ss is not None:
+            args += [C.c_void_p(fed.data_ptr()) if return_fed else None, C.c_void_p(logits.data_ptr()) if return_logits else None]
+    out = C.c_double()
+    ctx._call(name, *args, C.byref(out) if want_loss else None)
+    del keep, la, wa   # the host arrays and masks the arguments point into: held until the call has returned
+    return (out.value if want_loss else None), fed, logits
+
+
+def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None,
+         sched=None):
+    """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
+    tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
+    lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
+    norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used.
+    row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h).
+    sched (Sched, or (eps, temperature, seed[, row0])): scheduled sampling (include/lrcn_sched.h); lens then defaults to [T] * B."""
+    return _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, mask1, mask2), lens, norm_tokens, row_weights, sched)[0]
+
+
+def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
+                 want_loss=True, lens=None, norm_tokens=None, row_weights=None, sched=None, return_fed=False, return_logits=False):
+    """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights /
+    sched: as loss().  With sched, return_fed / return_logits append the words that were fed ((T+1, B) int32 numpy) and the logits the
+    draws were made from ((T+1, B, V) float32 numpy) to the result."""
     if grads is None:
         grads = [jl_empty(*t.shape) for t in param]
-    d, keep = _dropout(pdrop, seed, mask1, mask2)
-    out = C.c_double()
-    if ss is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        fed = torch.empty((T + 1, B), device=feats.device, dtype=torch.int32) if return_fed else None
-        logits = torch.empty((T + 1, ctx.V, B), device=feats.device, dtype=torch.float32) if return_logits else None  # blocks of B x V column-major
-        ctx._call("lrcn_loss_grad_sched", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1] if wa else None, T, B, nt,
-                  C.byref(d) if d else None, C.byref(ss), _p9(grads), C.c_void_p(fed.data_ptr()) if return_fed else None,
-                  C.c_void_p(logits.data_ptr()) if return_logits else None, C.byref(out) if want_loss else None)
-        del keep, la, wa
-        res = (grads, (out.value if want_loss else None))
-        if return_fed:
-            res += (fed.cpu().numpy(),)
-        if return_logits:
-            res += (logits.permute(0, 2, 1).cpu().numpy(),)
-        return res
-    if wa is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        ctx._call("lrcn_loss_grad_w", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, wa[1], T, B, nt, C.byref(d) if d else None,
-                  _p9(grads), C.byref(out) if want_loss else None)
-        del keep, la, wa
-        return grads, (out.value if want_loss else None)
-    if lens is not None:
-        la, lp, nt = _lens(lens, T, B, norm_tokens)
-        ctx._call("lrcn_loss_grad_var", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), lp, T, B, nt, C.byref(d) if d else None,
-                  _p9(grads), C.byref(out) if want_loss else None)
-        del keep, la
-        return grads, (out.value if want_loss else None)
-    ctx._call("lrcn_loss_grad", _p9(param), _ptr(feats), C.c_void_p(tok.data_ptr()), T, B, norm_B or B,
-              C.byref(d) if d else None, _p9(grads), C.byref(out) if want_loss else None)
-    del keep
-    return grads, (out.value if want_loss else None)
+    val, fed, logits = _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, mask1, mask2), lens, norm_tokens, row_weights, sched,
+                                     want_loss, grads, return_fed=return_fed, return_logits=return_logits)
+    res = (grads, val)
+    if return_fed:
+        res += (fed.cpu().numpy(),)
+    if return_logits:
+        res += (logits.permute(0, 2, 1).cpu().numpy(),)
+    return res
 
 
 def last_loss(ctx):
@@ -456,41 +439,8 @@ def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, 
                gclip=0.0, row_weights=None, sched=None):
     """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights / sched: as loss().
     gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h; clip_stats() has the counters)."""
-    gclip = float(gclip or 0.0)
-    tok = _tokens(tokens, feats.device)
-    T, B = tok.shape
-    d, keep = _dropout(pdrop, seed, None, None)
-    ss = _sched(sched, B) if sched is not None else None   # all checked before the step counter moves
-    if ss is not None:
-        lens = _sched_lens(lens, T, B)
-    wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
-    la = _lens(lens, T, B, norm_tokens) if lens is not None else None
-    optim.t += 1
-    out = C.c_double()
-    clip = (gclip,) if gclip > 0 else ()
-    if ss is not None:
-        ctx._call("lrcn_train_step_sched", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()), la[1],
-                  wa[1] if wa else None, T, B, la[2], C.byref(d) if d else None, C.byref(ss), optim.t, optim.lr, optim.beta1, optim.beta2,
-                  optim.eps, gclip, C.byref(out) if want_loss else None)
-        del keep, la, wa
-        return out.value if want_loss else None
-    if wa is not None:
-        ctx._call("lrcn_train_step_w", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats), C.c_void_p(tok.data_ptr()), la[1],
-                  wa[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps, gclip,
-                  C.byref(out) if want_loss else None)
-        del keep, la, wa
-        return out.value if want_loss else None
-    if la is not None:
-        ctx._call("lrcn_train_step_var_clip" if clip else "lrcn_train_step_var", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v),
-                  _ptr(feats), C.c_void_p(tok.data_ptr()), la[1], T, B, la[2], C.byref(d) if d else None, optim.t, optim.lr, optim.beta1,
-                  optim.beta2, optim.eps, *clip, C.byref(out) if want_loss else None)
-        del keep, la
-        return out.value if want_loss else None
-    ctx._call("lrcn_train_step_clip" if clip else "lrcn_train_step", _p9(param), _p9(grads), _p9(optim.m), _p9(optim.v), _ptr(feats),
-              C.c_void_p(tok.data_ptr()), T, B, norm_B or B, C.byref(d) if d else None, optim.t, optim.lr, optim.beta1, optim.beta2,
-              optim.eps, *clip, C.byref(out) if want_loss else None)
-    del keep
-    return out.value if want_loss else None
+    return _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, None, None), lens, norm_tokens, row_weights, sched, want_loss, grads,
+                         optim, float(gclip or 0.0))[0]
 
 
 def comm_unique_id():
