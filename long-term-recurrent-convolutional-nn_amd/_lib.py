@@ -22,6 +22,7 @@ CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"
 WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
 SCHED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sched.h"))        # lrcn_*_sched (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
+CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -262,11 +263,16 @@ GEMM_DEBUG_SIGNATURES = {
     "lrcn_debug_gemm": (C.c_int, [C.c_void_p, C.POINTER(GemmDebug)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_conv_debug.h declares (bound by lib() as well)
+CONV_DEBUG_SIGNATURES = {
+    "lrcn_debug_conv11": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -288,7 +294,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
-                list(GEMM_DEBUG_SIGNATURES.items()):
+                list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

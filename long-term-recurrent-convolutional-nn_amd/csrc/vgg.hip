@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ctx.h"
+#include "../../include/lrcn_conv_debug.h"
 #include "../../include/lrcn_gemm_debug.h"
 
 using namespace lrcn_impl;
@@ -722,6 +723,37 @@ int lrcn_conv1_fused(lrcn_ctx *c, const uint8_t *img, int N, int S, const float 
     }
     cleanup();
     if (e != hipSuccess) FAIL(c, LRCN_EHIP, "conv1_fused: %s", hipGetErrorString(e));
+    return LRCN_OK;
+}
+
+// Test entry (include/lrcn_conv_debug.h): conv11.hip's kernel by itself on the caller's source, weights repacked as lrcn_vgg_load repacks them
+int lrcn_debug_conv11(lrcn_ctx *c, const void *src, int src_is_u8, int N, int S, const float mean[3], const float *w11, const float *b11,
+                      float *y) {
+    DeviceGuard dg(c);
+    if (!c || !src || (src_is_u8 && !mean) || !w11 || !b11 || !y) return LRCN_EINVAL;
+    if (c->vdt != GEMM_T_BF16) FAIL(c, LRCN_EINVAL, "debug_conv11: the context's vgg_dtype must be LRCN_BF16 or LRCN_FP8");
+    if (N < 1 || S < 2 || (S & 1) || (int64_t)N * S * S * 64 >= (1ll << 31)) FAIL(c, LRCN_EINVAL, "debug_conv11: S must be even and >= 2, N >= 1");
+    void *wp = nullptr, *out = nullptr;
+    float *bd = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(wp);
+        (void)hipFree(out);
+        (void)hipFree(bd);
+    };
+    if (hipMalloc(&wp, 2 * 64 * 32) != hipSuccess || hipMalloc(&out, 2 * (size_t)N * S * S * 64) != hipSuccess ||
+        hipMalloc((void **)&bd, sizeof(float) * 64) != hipSuccess) {
+        cleanup();
+        FAIL(c, LRCN_ENOMEM, "debug_conv11 scratch");
+    }
+    (void)hipMemcpyAsync(bd, b11, sizeof(float) * 64, hipMemcpyDeviceToDevice, c->stream);
+    k_repack_conv11_w(c->stream, GEMM_T_BF16, w11, 64, wp, 32);
+    k_conv11_fused(c->stream, src_is_u8 ? 1 : 0, src, N, S, src_is_u8 ? mean[0] : 0.f, src_is_u8 ? mean[1] : 0.f, src_is_u8 ? mean[2] : 0.f, wp,
+                   bd, out);
+    k_nhwc_to_ref(c->stream, GEMM_T_BF16, out, S, S, 64, N, 64, y);
+    const hipError_t e = hipGetLastError();
+    cleanup();
+    if (e != hipSuccess) FAIL(c, LRCN_EHIP, "debug_conv11: %s", hipGetErrorString(e));
     return LRCN_OK;
 }
 

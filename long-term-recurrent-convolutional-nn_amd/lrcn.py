@@ -878,6 +878,19 @@ def conv1_fused(ctx, img_u8, mean, w11, b11, w12, b12):
     return y
 
 
+def debug_conv11(ctx, src, w11, b11, mean=VGG_MEAN):
+    """conv1_1 of the bf16 stack by itself (lrcn_debug_conv11, include/lrcn_conv_debug.h; conv11.hip).  src: uint8 crops [N][S][S][3] (device;
+    `mean` is subtracted per channel) or the preprocessed float tensor (S,S,3,N) column-major (`mean` is not used) -> (S,S,64,N)."""
+    if src.dtype == torch.uint8:
+        N, S, u8 = src.shape[0], src.shape[1], 1
+        m = (C.c_float * 3)(*[float(v) for v in mean])
+    else:
+        S, N, u8, m = src.shape[0], src.shape[3], 0, None
+    y = jl_empty(S, S, 64, N)
+    ctx._call("lrcn_debug_conv11", C.c_void_p(src.data_ptr()) if u8 else _ptr(src), u8, N, S, m, _ptr(w11), _ptr(b11), _ptr(y))
+    return y
+
+
 def vgg_set_wg_cap(ctx, cap):
     """Cap the VGG convolution grids at `cap` workgroups (0 = off): include/lrcn.h lrcn_vgg_set_wg_cap."""
     ctx._call("lrcn_vgg_set_wg_cap", int(cap))

@@ -43,3 +43,13 @@ def test_product_package_does_not_import_the_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp")):
                 src = open(os.path.join(root, f)).read()
                 assert "oracle" not in src.replace("the CPU oracle", "").replace("CPU oracle", "") or f == "_lib.py", (root, f)
+
+
+def test_conv_debug_binding_declares_exactly_its_header():
+    # include/lrcn_conv_debug.h: a test entry beside the ABI -- exported by the library, bound by its own table, absent from lrcn.h
+    raw = open(_lib.CONV_DEBUG_HEADER).read()
+    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.CONV_DEBUG_SIGNATURES) == ["lrcn_debug_conv11"]
+    assert "lrcn_debug_conv11" not in _lib.SIGNATURES and "lrcn_debug_conv11" not in open(_lib.HEADER).read()
+    assert "#define LRCN_ABI_VERSION" not in raw and '#include "lrcn.h"' in raw
+    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "lrcn_debug_conv11")

@@ -46,10 +46,14 @@ def assert_grads_close(g, r, rtol, what):
 def test_f32_parity(shape):
     F, H, C_, T, B = shape
     m, x, lab, lens = setup(F, H, C_, T, B)
+    _f32_assert(m, x, lab, lens, T, B, "f32 %s" % (shape,))
+
+
+def _f32_assert(m, x, lab, lens, T, B, what):
     loss, g, cp, fp = run(m, x, lab, lens, T)
     rl, rg, rc, rf = reference(*host(m), x, lab, lens, T, B)
     assert abs(loss - rl) <= 1e-4 * abs(rl), (loss, rl)
-    assert_grads_close(g, rg, 1e-3, "f32 %s" % (shape,))
+    assert_grads_close(g, rg, 1e-3, what)
     np.testing.assert_allclose(cp, rc, rtol=1e-4, atol=1e-7)
     np.testing.assert_allclose(fp, rf, rtol=1e-4, atol=1e-7)
     np.testing.assert_allclose(cp.sum(0), 1.0, atol=1e-5)
@@ -81,6 +85,10 @@ def _bf16_check(shape, fused_env, monkeypatch):
         monkeypatch.setenv("LRCN_LSTM_FUSED", fused_env)
     F, H, C_, T, B = shape
     m, x, lab, lens = setup(F, H, C_, T, B, dtype=BF16)
+    _bf16_assert(m, x, lab, lens, T, B)
+
+
+def _bf16_assert(m, x, lab, lens, T, B):
     loss, g, cp, fp = run(m, x, lab, lens, T)
     P = host(m)
     el, eg, ec, ef = emulated(*P, x, lab, lens, T, B, bf16=True)
@@ -228,3 +236,43 @@ def test_bf16_learns_the_order_of_two_patterns():
             if acc >= 0.97:
                 break
     assert acc >= 0.95, acc
+
+
+def head_critical_classes(C_):
+    """act_head_kernel<T, NQ> maps class c to thread c % 256 and register slot c // 256 (launch_head: NQ = 1, 2, 4, 8, 16 for C <= 256, 512,
+    1024, 2048, 4096): the first and the last thread of the first two slots, both sides of the instantiation's last slot, the last class."""
+    nq = next(q for q in (1, 2, 4, 8, 16) if C_ <= 256 * q)
+    return nq, sorted({c for c in (0, 255, 256, 256 * (nq - 1) - 1, 256 * (nq - 1), C_ - 1) if 0 <= c < C_})
+
+
+@pytest.mark.parametrize("dtype", [F32, BF16])
+@pytest.mark.parametrize("C_", [256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096])
+def test_head_instantiations(C_, dtype):
+    """Every act_head_kernel<T, NQ> that launch_head can pick, at the last class count of each rung and the first of the next (the other
+    tests stop at C = 101: NQ = 1 only).  The labels are critical classes and the output bias is N(0, 2^2) plus 4 on the critical classes,
+    so each of them carries probability far above the tolerances and a slot that is dropped, doubled or scaled moves the loss, dbout, the
+    clip and the frame probabilities.  References and bounds: test_f32_parity's against reference(), _bf16_check's against emulated().
+    A local build (not kept) whose act_head_kernel<., 4> added the LAST slot's exponentials x 1.01 to the row sum failed C = 1024 in both
+    types at the first assertion, the loss (8.9e-4 relative > 1e-4, against reference() and against emulated()), and no other case: at
+    C = 513 the fourth slot (classes 768 ..) holds no class, the other counts are other instantiations."""
+    F, H, T, B = 64, 32, 4, 3
+    nq, crit = head_critical_classes(C_)
+    m = A.ActivityModel(F, H, C_, max_B=B, max_T=T, dtype=dtype, seed=7)
+    rng = np.random.default_rng(C_)
+    x = rng.standard_normal((B * T, F)).astype(np.float32)
+    lens = np.array([1, 4, 2], np.int32)
+    lab = np.array([crit[-1], crit[-2], crit[len(crit) // 2]], np.int32)  # C - 1, the critical class below it, one of the middle
+    bout = 2.0 * rng.standard_normal((1, C_))
+    bout[0, crit] += 4.0
+    m.params[3].copy_(torch.as_tensor(bout.astype(np.float32)))
+    if dtype == F32:
+        _f32_assert(m, x, lab, lens, T, B, "f32 head C=%d" % C_)
+    else:
+        _bf16_assert(m, x, lab, lens, T, B)
+    m.close()
+
+
+def test_more_than_4096_classes_are_refused():
+    h = C.c_void_p()
+    assert _lib.lib().lrcn_act_create(C.byref(_lib.ActConfig(0, 64, 32, 4097, 3, 4, 0, 0)), C.byref(h)) == -1
+    assert not h.value and b"4096" in _lib.lib().lrcn_act_last_error(None)

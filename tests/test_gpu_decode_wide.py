@@ -355,11 +355,13 @@ def score_oracle(m, feats, caps, pairs):
     return out
 
 
-@pytest.mark.parametrize("V", [15361, 16385, 32768, 33024])
+@pytest.mark.parametrize("V", [8192, 8196, 15361, 16384, 16385, 16388, 32768, 33024])
 def test_large_vocabulary_bf16_record_routes_against_row_routes_and_oracle(V, monkeypatch):
     """bf16 from 256 rows, where the logits GEMM reduces to records when V % 4 == 0 and no more than 256 records make a row (V <= 32768):
     beam, n-best, sampling (top_k 0 and 3) and scoring on the default route against LRCN_DECODE_SMAX=0 / LRCN_SCORE_FUSED=0 and the
-    emulating oracle.  At V = 33024 (258 records) every call must still return: the default route is then the f32-logits one."""
+    emulating oracle.  At V = 33024 (258 records) every call must still return: the default route is then the f32-logits one.
+    V = 8192 | 8196 and 16384 | 16388: 64 | 66 and 128 | 130 records per row, both sides of the <1> | <2> | <4> instantiations of
+    softmax_topk_merge_kernel, sample_gumbel_merge_kernel, sample_topk_merge_kernel and score_pick_merge_kernel (tests/INSTANTIATIONS.md)."""
     K, nword = 5, 5
     N = 52   # 260 rows: beam, n-best and K = 5 samples per image
     m = peaked_model(E4, V, seed=V + 3, eos_rel=-0.3)

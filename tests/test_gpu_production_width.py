@@ -39,9 +39,11 @@ PAIRS = [(n, r) for n in pw.GPU_CASES for r in pw.REGIMES]
 ids = ["%s-%s" % p for p in PAIRS]
 
 
-def run(c, dtype, logits=False):
+def run(c, dtype, logits=False, deterministic=False):
     """lossgradient (and the per-step logits) of case c on the device -> pw.Result, the route of the last contraction."""
     ctx = L.Context(c.E, c.H, c.H, c.V, max_B=c.B, max_T=c.T, lstm_dtype=dtype, n_layers=c.n_layers)
+    if deterministic:
+        ctx.set_option(lrcn_amd._lib.LRCN_OPT_DETERMINISTIC, 1)
     param = L.model_from_arrays(c.model.p)
     kw = dict(lens=c.lens, norm_tokens=c.norm_tokens) if c.lens is not None else dict(norm_B=c.norm_B)
     if c.pdrop is not None:   # the device's own masks, by (pdrop, seed): the references got the host transcription of them as mask1 / mask2
@@ -102,6 +104,22 @@ def test_bf16_loss_and_gradients_vs_emulation_and_float64_autograd(name, regime)
     assert hdl <= max(pu.BF16_LOSS_RTOL, 2 * odl)
     for n in hd:
         assert hd[n] <= max(pu.BF16_GRAD_NORM, 2 * od[n]), (n, hd[n], od[n])
+
+
+@pytest.mark.parametrize("regime", pw.REGIMES)
+def test_ordered_sums_at_1024_rows_f32_vs_float64_autograd(regime):
+    """c1-rows256 on a context with LRCN_OPT_DETERMINISTIC: (T + 1) B = 1024 rows > 512, so the bias gradients come from the one-slab
+    colsum_kernel<T, 64> (summed in row order) instead of the slabbed atomic form, and the embedding gradient from the sorted segmented
+    sums -- forms the other deterministic tests hold only to the default route or to themselves.  Same reference, same f32 constants."""
+    name = "c1-rows256"
+    c, ref = pw.case(name, regime), pw.reference(name, regime)
+    got, route = run(c, F32, deterministic=True)
+    d, dl = pw.distances(got, ref)
+    print("%s %s f32 deterministic: loss rel %.1e; per tensor %s" % (name, regime, dl, " ".join("%s %.1e" % (n, d[n]) for n in d)))
+    assert dl <= 1e-5
+    for n in ref.g:
+        assert d[n] <= F32_GRAD_NORM, (n, d[n])
+        np.testing.assert_allclose(got.g[n], ref.g[n], rtol=1e-3, atol=1e-5, err_msg=n)
 
 
 @pytest.mark.parametrize("K", [3, 10])

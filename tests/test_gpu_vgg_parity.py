@@ -1,6 +1,7 @@
 """GPU: the HIP VGG-16 path (implicit-GEMM 3x3 conv + bias + ReLU + fused 2x2 max-pool, fc6/fc7, preprocessing) through
 the C ABI against the golden vectors and the CPU oracle.  fp32: exact-fp32 MFMA, tolerance 1e-4 relative to the
 tensor's max; bf16: 3e-2 relative to the tensor's max (operands rounded to 8 bits of mantissa per layer)."""
+import ctypes
 import os
 
 import numpy as np
@@ -365,3 +366,164 @@ def test_config2_end_to_end_fp32_images_to_loss(vgg_setup):
         a, b = L.from_jl(g).ravel().astype(np.float64), ref_g.p[n].ravel().astype(np.float64)
         assert np.linalg.norm(a - b) <= 2e-3 * np.linalg.norm(b) + 1e-9, n
     ctx.close()
+
+
+# ------------------------------------------------------- conv1_1 by itself and the float-input forward (include/lrcn_conv_debug.h)
+CONV11_MEAN = (135.68, 116.779, 97.939)   # the three channels differ by more than 10: a swapped channel or mean moves every pixel
+
+
+def _conv11_case(S, N):
+    rng = np.random.default_rng(S * 10 + N)
+    img = rng.integers(0, 256, size=(N, S, S, 3), dtype=np.uint8)
+    img[0, : S // 4] = 255  # a saturated and a dark band: ReLU cut-off at the borders
+    img[-1, -S // 4:] = 0
+    w11 = (rng.standard_normal((3, 3, 3, 64)) * np.sqrt(2.0 / 27)).astype(np.float32)
+    b11 = (rng.standard_normal(64) * 20.0).astype(np.float32)  # of the size of the activations: a bias lost or doubled cannot hide
+    return img, w11, b11
+
+
+@pytest.mark.parametrize("dtype", [lrcn_amd.LRCN_BF16, lrcn_amd.LRCN_FP8], ids=["bf16", "fp8"])
+@pytest.mark.parametrize("S,N", [(6, 1), (16, 1), (18, 3), (224, 1)])
+def test_conv11_launch_vs_emulating_oracle(S, N, dtype):
+    """conv11.hip by itself (lrcn_debug_conv11), from uint8 crops (conv11_kernel<true>) and from the preprocessed float tensor
+    (conv11_kernel<false>: what lrcn_vgg_forward runs on a bf16 or fp8 context, and the average-image path outside the fused first launch),
+    value by value against the bf16-emulating oracle.  36 rows: one partial block, every pixel on or beside the border; 256: exactly one
+    block; 972: three blocks and a 204-row tail, image seams inside blocks (rows 324 and 648); 50176: the product geometry.  Both sources
+    are the same bf16 operands in the same kernel: bit for bit.  (An fp8 context runs conv1_1 in bf16 like a bf16 one: same bounds.)
+    A local build (not kept) whose conv11_kernel<false> read f[y + S * x] for f[x + S * y] failed every case at the float source's
+    assert_bf16_layer (worst |d| 492 .. 568 at max|ref| 440 .. 568) and both whole-stack tests at their bitwise comparison."""
+    img, w11, b11 = _conv11_case(S, N)
+    mean = np.array(CONV11_MEAN, np.float32)
+    x = orc.preprocess_u8(img, mean)
+    with orc.emulate_bf16():
+        emu = orc.conv3x3(x, w11, b11, relu=True)
+    ctx = small_ctx(dtype)
+    w, b = L.to_jl(w11), torch.as_tensor(b11).cuda()
+    got8 = L.from_jl(L.debug_conv11(ctx, torch.as_tensor(img).cuda(), w, b, mean=CONV11_MEAN))
+    gotf = L.from_jl(L.debug_conv11(ctx, L.to_jl(x), w, b))
+    ctx.close()
+    assert got8.shape == emu.shape == (S, S, 64, N) and (emu > 0).any() and (emu == 0).any()
+    assert_bf16_layer(got8, emu, "uint8 source S=%d N=%d" % (S, N))
+    assert_bf16_layer(gotf, emu, "float source S=%d N=%d" % (S, N))
+    np.testing.assert_array_equal(gotf, got8)
+
+
+def test_conv11_launch_refuses_bad_arguments_before_any_launch():
+    img, w11, b11 = _conv11_case(6, 1)
+    w, b = L.to_jl(w11), torch.as_tensor(b11).cuda()
+    lib = lrcn_amd._lib.lib()
+    mean = (ctypes.c_float * 3)(*CONV11_MEAN)
+    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    ctx = small_ctx(lrcn_amd.LRCN_BF16)
+    y = L.jl_empty(8, 8, 64, 1)
+    y.fill_(123.0)
+    u8 = torch.as_tensor(np.zeros((1, 8, 8, 3), np.uint8)).cuda()
+    torch.cuda.synchronize()
+    for args in ((p(u8), 1, 1, 7, mean, p(w), p(b), p(y)),      # odd S
+                 (p(u8), 1, 1, 0, mean, p(w), p(b), p(y)),      # S < 2
+                 (p(u8), 1, 0, 8, mean, p(w), p(b), p(y)),      # N < 1
+                 (p(u8), 1, 1, 8, None, p(w), p(b), p(y)),      # a uint8 source needs the means
+                 (None, 0, 1, 8, None, p(w), p(b), p(y)), (p(u8), 1, 1, 8, mean, None, p(b), p(y)),
+                 (p(u8), 1, 1, 8, mean, p(w), None, p(y)), (p(u8), 1, 1, 8, mean, p(w), p(b), None)):
+        assert lib.lrcn_debug_conv11(ctx._h, *args) == -1, args[1:4]
+    assert lib.lrcn_debug_conv11(None, p(u8), 1, 1, 8, mean, p(w), p(b), p(y)) == -1
+    ctx.close()
+    f32 = small_ctx(lrcn_amd.LRCN_F32)   # the f32 stack has no conv11.hip: its conv1_1 is an im2col GEMM
+    assert lib.lrcn_debug_conv11(f32._h, p(u8), 1, 1, 8, mean, p(w), p(b), p(y)) == -1
+    f32.close()
+    torch.cuda.synchronize()
+    assert bool((y == 123.0).all())
+
+
+def test_float_input_forward_bf16(vgg_setup, monkeypatch):
+    """lrcn_vgg_forward (the entry INTEGRATION.md maps to the reference's convnet) on a bf16 context: conv11_kernel<false> in front of the
+    stack.  Two launches (LRCN_FUSE11=0): the float tensor that lrcn_preprocess_u8 makes of the crops gives the uint8 entry's bits, with the
+    channel means and with an average image (where the uint8 entry itself goes through the float route).  Default knobs: against the fp32
+    oracle and against the fused uint8 entry with this file's constants."""
+    w, img, x, ref = vgg_setup
+    imgs = torch.as_tensor(img).cuda()
+    avg = (np.random.default_rng(8).standard_normal((224, 224, 3)) * 20.0 + np.array(L.VGG_MEAN)).astype(np.float32)
+    monkeypatch.setenv("LRCN_FUSE11", "0")
+    ctx = small_ctx(lrcn_amd.LRCN_BF16, max_images=2)
+    L.vgg_load(ctx, *w)
+    got8 = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+    assert L.debug_route(ctx, 1).split(",")[0] == "conv11"
+    gotf = L.from_jl(L.convnet(ctx, L.read_image_data_u8(ctx, imgs))).copy()
+    assert L.debug_route(ctx, 1).split(",")[0] == "conv11"
+    np.testing.assert_array_equal(gotf, got8)
+    assert rel_max_err(got8, ref) <= 3e-2
+    L.set_average_image(ctx, avg)
+    a8 = L.from_jl(L.convnet_u8(ctx, imgs, mean=None)).copy()
+    af = L.from_jl(L.convnet(ctx, L.read_image_data_u8(ctx, imgs, mean=None))).copy()
+    np.testing.assert_array_equal(af, a8)
+    assert np.abs(a8 - got8).max() > 0   # the average image is not the channel means
+    ctx.close()
+    monkeypatch.delenv("LRCN_FUSE11")
+    ctx = small_ctx(lrcn_amd.LRCN_BF16, max_images=2)
+    L.vgg_load(ctx, *w)
+    fused8 = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+    assert L.debug_route(ctx, 1).split(",")[0] == "conv64-fused11"
+    gotf = L.from_jl(L.convnet(ctx, L.to_jl(x))).copy()
+    assert L.debug_route(ctx, 1).split(",")[0] == "conv11"
+    ctx.close()
+    assert gotf.shape == (2, 4096) and (gotf < 0).any()
+    assert rel_max_err(gotf, ref) <= 3e-2
+    assert float((gotf * ref).sum() / (np.linalg.norm(gotf) * np.linalg.norm(ref))) > 0.999
+    assert rel_max_err(gotf, fused8) <= 1.5e-2
+
+
+def test_float_input_forward_fp8(vgg_setup, monkeypatch):
+    # the same bitwise statement on a calibrated fp8 context: conv1_1 .. conv2_1 are bf16 there, conv11_kernel<false> in front
+    w, img, x, ref = vgg_setup
+    imgs = torch.as_tensor(img).cuda()
+    monkeypatch.setenv("LRCN_FUSE11", "0")
+    ctx = small_ctx(lrcn_amd.LRCN_FP8, max_images=2)
+    L.vgg_load(ctx, *w)
+    L.vgg_calibrate(ctx, imgs)
+    got8 = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+    gotf = L.from_jl(L.convnet(ctx, L.read_image_data_u8(ctx, imgs))).copy()
+    assert L.debug_route(ctx, 1).split(",")[0] == "conv11"
+    np.testing.assert_array_equal(gotf, got8)
+    assert np.isfinite(got8).all() and (got8 != 0).any()
+    # and with an average image, where the uint8 entry itself preprocesses into a float tensor first
+    L.set_average_image(ctx, (np.random.default_rng(8).standard_normal((224, 224, 3)) * 20.0 + np.array(L.VGG_MEAN)).astype(np.float32))
+    a8 = L.from_jl(L.convnet_u8(ctx, imgs, mean=None)).copy()
+    af = L.from_jl(L.convnet(ctx, L.read_image_data_u8(ctx, imgs, mean=None))).copy()
+    ctx.close()
+    np.testing.assert_array_equal(af, a8)
+    assert np.isfinite(a8).all() and np.abs(a8 - got8).max() > 0
+
+
+def test_fp8_conv2_2_on_the_512_row_tile_matches_emulated_arithmetic():
+    """The e4m3 convolution on the 512 x 128 tile (route 8p-f8:2): conv2_2's geometry from 17 images, the smallest batch with >= 400 row
+    tiles of 512 (416.5: the last tile is half full).  test_fp8_conv_layer_matches_emulated_arithmetic stops at 784 rows (configs 0 and 1);
+    here images 0 and 16 -- the first tiles and the half-full last one -- go through the same per-image host emulation and the same two
+    bounds."""
+    W = H = 112
+    Cin = Cout = 128
+    N = 17
+    rng = np.random.default_rng(Cin + Cout + N)
+    x = np.abs(rng.standard_normal((W, H, Cin, N), dtype=np.float32))  # post-ReLU-like inputs
+    w = (rng.standard_normal((3, 3, Cin, Cout)) * np.sqrt(2.0 / (9 * Cin))).astype(np.float32)
+    b = (rng.standard_normal(Cout) * 0.05).astype(np.float32)
+    sample = [0, N - 1]
+    xs = np.ascontiguousarray(x[..., sample])
+    tgt = orc.pool2(orc.conv3x3(xs, w, b, relu=True))
+    sa_in = np.float32(x.max() / 448.0)
+    sa_out = np.float32(1.25 * tgt.max() / 448.0)   # the two sampled images' range with a margin for the fifteen others
+    ctx = small_ctx()
+    y, sw = L.conv3x3_fp8(ctx, L.to_jl(x), L.to_jl(w), torch.as_tensor(b).cuda(), float(sa_in), float(sa_out), relu=True, pool=True)
+    assert L.debug_route(ctx) == "8p-f8:2"
+    y, sw = L.from_jl(y)[..., sample], sw.cpu().numpy()
+    ctx.close()
+    np.testing.assert_allclose(sw, np.abs(w).max(axis=(0, 1, 2)) / np.float32(448.0), rtol=1e-6)
+    xq = _e4m3(xs * (np.float32(1.0) / sa_in))
+    wq = _e4m3(w * (np.float32(1.0) / sw)[None, None, None, :])
+    acc = orc.pool2(orc.conv3x3(xq, wq, np.zeros(Cout, np.float32), relu=False))
+    v = np.maximum(acc * (sa_in * sw / sa_out)[None, None, :, None] + (b / sa_out)[None, None, :, None], 0.0).astype(np.float32)
+    emu = _e4m3(v) * sa_out
+    assert y.shape == emu.shape == (56, 56, 128, 2) and (emu > 0).mean() > 0.5
+    for k, n in enumerate(sample):
+        diff = np.abs(y[..., k] - emu[..., k])
+        assert (diff <= 0.126 * np.abs(emu[..., k]) + 2.0 ** -7 * sa_out).all(), (n, float(diff.max()))
+        assert (diff == 0).mean() > 0.99, (n, float((diff == 0).mean()))
