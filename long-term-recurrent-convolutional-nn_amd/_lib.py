@@ -17,6 +17,7 @@ NUCLEUS_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nucl
 NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.h"))    # lrcn_beam_nbest_batch (not in lrcn.h)
 DIVERSE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_diverse.h"))  # lrcn_beam_diverse_batch (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
+ACT_DROPOUT_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_act_dropout.h"))  # lrcn_act_loss_grad_drop (not in lrcn_activity.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
 CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
 WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
@@ -46,6 +47,10 @@ class Config(C.Structure):
 class ActConfig(C.Structure):   # lrcn_act_config of include/lrcn_activity.h
     _fields_ = [("device", C.c_int), ("F", C.c_int), ("H", C.c_int), ("C", C.c_int), ("max_B", C.c_int), ("max_T", C.c_int),
                 ("dtype", C.c_int), ("deterministic", C.c_int)]
+
+
+class ActDropout(C.Structure):   # lrcn_act_dropout of include/lrcn_act_dropout.h
+    _fields_ = [("p_in", C.c_float), ("p_out", C.c_float), ("seed", C.c_uint64), ("mask_in", C.c_void_p), ("mask_out", C.c_void_p)]
 
 
 class GemmDebug(C.Structure):   # lrcn_gemm_debug of include/lrcn_gemm_debug.h
@@ -199,6 +204,12 @@ ACTIVITY_SIGNATURES = {
     "lrcn_act_predict": (C.c_int, [C.c_void_p, P4, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_act_dropout.h declares (bound by lib() as well)
+ACT_DROPOUT_SIGNATURES = {
+    "lrcn_act_loss_grad_drop": (C.c_int, [C.c_void_p, P4, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                          C.POINTER(ActDropout), C.c_void_p, C.POINTER(C.c_double)]),
+}
+
 # name -> (restype, argtypes); exactly the symbols include/lrcn_varlen.h declares (bound by lib() as well)
 VARLEN_SIGNATURES = {
     "lrcn_loss_var": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int64, C.POINTER(Dropout),
@@ -272,7 +283,7 @@ CONV_DEBUG_SIGNATURES = {
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER,
-                                                                                                   ACTIVITY_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -293,7 +304,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
+                list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
                 list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res

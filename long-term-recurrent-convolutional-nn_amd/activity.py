@@ -69,6 +69,7 @@ class ActivityModel:
             self.mom = [jl_zeros(*s) for s in shapes]
             self.var = [jl_zeros(*s) for s in shapes]
         self.step = 0
+        self.drop_seed = int(seed or 0)   # train_step's dropout draws step k with drop_seed + k
         self._opt_ctx = None
         self.use_stream(torch.cuda.current_stream(self.device))
         if seed is not None:
@@ -128,8 +129,25 @@ class ActivityModel:
         for t in self.mom + self.var:
             t.zero_()
 
-    def loss_grad(self, feats, labels, lens=None, T=None, grad=True, params=None):
-        """-> loss (float); grad=True also leaves d loss / d params in self.grads.  labels / lens: host int arrays [B] (lens None = T)."""
+    def _mask(self, mask, T, B, ncols, what):
+        """A logical (T, B, ncols) multiplier array (numpy or device tensor) -> the ABI's T column-major blocks of B x ncols, on the device
+        (lrcn._dropout's conversion)."""
+        if mask is None:
+            return None
+        if torch.is_tensor(mask):
+            m = mask.to(device="cuda:%d" % self.device, dtype=torch.float32)
+        else:
+            m = torch.as_tensor(np.asarray(mask, np.float32))
+        if tuple(m.shape) != (T, B, ncols):
+            raise LrcnError("%s must be (T, B, %d) = %s, got %s" % (what, ncols, (T, B, ncols), tuple(m.shape)))
+        return m.permute(0, 2, 1).contiguous().to("cuda:%d" % self.device)
+
+    def loss_grad(self, feats, labels, lens=None, T=None, grad=True, params=None, pdrop_in=0.0, pdrop_out=0.0, drop_seed=0, masks=None):
+        """-> loss (float); grad=True also leaves d loss / d params in self.grads.  labels / lens: host int arrays [B] (lens None = T).
+        pdrop_in / pdrop_out: seeded dropout on the frame features / on the LSTM output before the classifier (include/lrcn_act_dropout.h;
+        the mask of a clip depends on its position in the batch and on B).  masks = (mask_in, mask_out): explicit multipliers in the
+        logical shapes (T, B, F) / (T, B, H), either may be None; a mask replaces (p, seed) on its side.  With all four at their defaults
+        the call is lrcn_act_loss_grad."""
         lab = np.asarray(labels, np.int32).reshape(-1)
         B = lab.size
         T = int(T if T is not None else self.max_T)
@@ -138,7 +156,15 @@ class ActivityModel:
         ln, plen = self._i32(lens, B, "lens")
         loss = C.c_double()
         g = self._p4(self.grads) if grad else None
-        self._call("lrcn_act_loss_grad", self._p4(params or self.params), _ptr(feats), plab, plen, T, B, g, C.byref(loss))
+        m_in, m_out = masks if masks is not None else (None, None)
+        if not pdrop_in and not pdrop_out and m_in is None and m_out is None:
+            self._call("lrcn_act_loss_grad", self._p4(params or self.params), _ptr(feats), plab, plen, T, B, g, C.byref(loss))
+            return loss.value
+        m_in, m_out = self._mask(m_in, T, B, self.F, "mask_in"), self._mask(m_out, T, B, self.H, "mask_out")
+        d = _lib.ActDropout(float(pdrop_in or 0.0), float(pdrop_out or 0.0), int(drop_seed or 0) & (2 ** 64 - 1),
+                            m_in.data_ptr() if m_in is not None else None, m_out.data_ptr() if m_out is not None else None)
+        self._call("lrcn_act_loss_grad_drop", self._p4(params or self.params), _ptr(feats), plab, plen, T, B, C.byref(d), g, C.byref(loss))
+        del m_in, m_out   # the device masks the struct points into: held until the call has returned (it synchronises for the loss)
         return loss.value
 
     def predict(self, feats, lens=None, T=None, B=None, frame_probs=False, params=None):
@@ -189,8 +215,9 @@ class ActivityModel:
         self._stream.synchronize()
         return lrcn.clip_stats(self._optimizer_ctx())
 
-    def train_step(self, feats, labels, lens=None, T=None, lr=1e-3, gclip=0.0):
-        loss = self.loss_grad(feats, labels, lens, T)
+    def train_step(self, feats, labels, lens=None, T=None, lr=1e-3, gclip=0.0, pdrop_in=0.0, pdrop_out=0.0):
+        """loss_grad + adam_step.  pdrop_in / pdrop_out (the paper: 0.9 / 0.5): step k draws its masks with the seed drop_seed + k."""
+        loss = self.loss_grad(feats, labels, lens, T, pdrop_in=pdrop_in, pdrop_out=pdrop_out, drop_seed=self.drop_seed + self.step)
         self.adam_step(lr, gclip=gclip)
         return loss
 
@@ -214,7 +241,8 @@ class ActivityModel:
 
     # ---- checkpoints
     def save(self, path):
-        d = {"config": np.array([self.F, self.H, self.C, self.max_B, self.max_T, self.dtype, int(self.deterministic), self.step], np.int64)}
+        d = {"config": np.array([self.F, self.H, self.C, self.max_B, self.max_T, self.dtype, int(self.deterministic), self.step], np.int64),
+             "drop_seed": np.array(self.drop_seed, np.int64)}
         for n, p, m, v in zip(PARAM_NAMES, self.params, self.mom, self.var):
             d[n] = from_jl(p)
             d["m_" + n] = from_jl(m)
@@ -231,4 +259,6 @@ class ActivityModel:
             self.mom[i].copy_(torch.as_tensor(z["m_" + n]))
             self.var[i].copy_(torch.as_tensor(z["v_" + n]))
         self.step = step
+        if "drop_seed" in z.files:   # checkpoints from before dropout have none: drop_seed stays 0
+            self.drop_seed = int(z["drop_seed"])
         return self

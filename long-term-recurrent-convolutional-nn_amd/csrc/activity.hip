@@ -7,11 +7,16 @@
 //   act_head_kernel   -- one workgroup per clip, its T logit rows in step order: log-softmax, the masked NLL term, dlogits, per-step
 //                        probabilities and the clip average (no atomics: the loss and the probabilities are reproducible bit for bit)
 //   act_loss_sum_kernel -- the per-clip NLL terms summed in clip order (double)
+// and, for dropout on the two non-recurrent connections (include/lrcn_act_dropout.h; the multipliers are drop_mult's of kernel_util.h),
+//   act_frames_kernel<T, true> -- the same tile pass with the input multiplier applied as the tile is loaded (X and X' from one masked tile)
+//   act_head_drop_kernel -- Hall -> the head's masked operand Hd [m][j] and, for dWout, its transpose Hd' (zero K padding), one LDS tile pass
+//   act_dh_mask_kernel   -- dHall *= m_out (f32), between the dh GEMM and the reverse recurrence
 #include <algorithm>
 #include <cmath>
 
-#include "../../include/lrcn_activity.h"
+#include "../../include/lrcn_act_dropout.h"
 #include "host.h"
+#include "kernel_util.h"
 
 using namespace lrcn_impl;
 
@@ -19,8 +24,10 @@ namespace {
 
 // X[m][f] = feats[f * N + b * Tn + t] with m = t * B + b, N = Tn * B; XT (optional) [f][m] with zeros for M <= m < ldxt.
 // Grid: (F / 64 tiles, m tiles of 64 up to M (X only) or ldxt (with XT)).
-template <typename T>
-__global__ __launch_bounds__(256) void act_frames_kernel(const float *feats, int F, int Tn, int B, T *X, int64_t ldx, T *XT, int64_t ldxt) {
+// DROP: v *= drop_mult(d, t, b, f) as the tile is loaded, for m < M only (the zero fill of XT stays zero, no mask is evaluated there).
+template <typename T, bool DROP>
+__global__ __launch_bounds__(256) void act_frames_kernel(const float *feats, int F, int Tn, int B, T *X, int64_t ldx, T *XT, int64_t ldxt,
+                                                         DropSpec d) {
     __shared__ float tile[64][65];
     const int f0 = blockIdx.x * 64, m0 = blockIdx.y * 64, tid = threadIdx.x;
     const int M = Tn * B;
@@ -32,6 +39,7 @@ __global__ __launch_bounds__(256) void act_frames_kernel(const float *feats, int
         if (f < F && m < M) {
             const int t = m / B, b = m - t * B;
             v = feats[(int64_t)f * M + (int64_t)b * Tn + t];
+            if (DROP) v *= drop_mult(d, t, b, f, B, F);
         }
         tile[fr][mr] = v;
     }
@@ -48,6 +56,47 @@ __global__ __launch_bounds__(256) void act_frames_kernel(const float *feats, int
         const int idx = tid + 256 * k, fr = idx >> 6, mr = idx & 63;
         const int f = f0 + fr, m = m0 + mr;
         if (f < F && m < ldxt) XT[(int64_t)f * ldxt + m] = from_f32<T>(tile[fr][mr]);
+    }
+}
+
+// Hd[m][j] = Hall[m][j] * m_out(t, b, j) with m = t * B + b (T, one rounding after the f32 product); HdT (optional) [j][m] with zeros for
+// M <= m < ldt.  Hall is only read.  Grid: (H / 64 tiles, m tiles of 64 up to M (Hd only) or ldt (with HdT)).
+template <typename T>
+__global__ __launch_bounds__(256) void act_head_drop_kernel(const T *Hall, int64_t ldh, int H, int Tn, int B, DropSpec d, T *Hd, T *HdT,
+                                                            int64_t ldt) {
+    __shared__ float tile[64][65];
+    const int j0 = blockIdx.x * 64, m0 = blockIdx.y * 64, tid = threadIdx.x;
+    const int M = Tn * B;
+#pragma unroll 4
+    for (int k = 0; k < 16; ++k) {
+        const int idx = tid + 256 * k, mr = idx >> 6, jr = idx & 63;
+        const int j = j0 + jr, m = m0 + mr;
+        float v = 0.0f;
+        if (j < H && m < M) {
+            const int t = m / B, b = m - t * B;
+            const T r = from_f32<T>(to_f32(Hall[(int64_t)m * ldh + j]) * drop_mult(d, t, b, j, B, H));
+            Hd[(int64_t)m * ldh + j] = r;
+            v = to_f32(r);
+        }
+        tile[mr][jr] = v;
+    }
+    __syncthreads();
+    if (!HdT) return;
+#pragma unroll 4
+    for (int k = 0; k < 16; ++k) {
+        const int idx = tid + 256 * k, jr = idx >> 6, mr = idx & 63;
+        const int j = j0 + jr, m = m0 + mr;
+        if (j < H && m < ldt) HdT[(int64_t)j * ldt + m] = from_f32<T>(tile[mr][jr]);
+    }
+}
+
+// dH[m][j] *= m_out(t, b, j), f32 [M][H] dense
+__global__ __launch_bounds__(256) void act_dh_mask_kernel(float *dH, int H, int Tn, int B, DropSpec d) {
+    const int64_t n = (int64_t)Tn * B * H;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int m = (int)(i / H), j = (int)(i - (int64_t)m * H);
+        const int t = m / B, b = m - t * B;
+        dH[i] *= drop_mult(d, t, b, j, B, H);
     }
 }
 
@@ -170,6 +219,7 @@ struct lrcn_act {
     void *acts = nullptr;    // [Mmax][ld4H]
     float *Call = nullptr;   // [Mmax][H]
     void *Hall = nullptr;    // [Mmax][ldH]
+    void *Hd = nullptr;      // [Mmax][ldH]: Hall with the output dropout's multipliers, the head's operand (allocated by the first call that drops)
     float *Logits = nullptr; // [Mmax][ldC]
     void *dLog = nullptr;    // [Mmax][ldC]
     float *dHall = nullptr;  // [Mmax][H]
@@ -262,8 +312,12 @@ int upload_meta(lrcn_act *a, const int32_t *labels, const int32_t *lens, int T, 
     return LRCN_OK;
 }
 
-// frames -> Gx -> recurrence -> logits.  with_xt: also the transposed frames into TB (the weight gradient's operand).
-int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T, int B, bool bwd) {
+inline bool drops(const DropSpec *d) { return d && (d->mask || d->p > 0.0f); }
+
+// frames -> Gx -> recurrence -> logits.  bwd: also the transposed frames into TB (the weight gradient's operand).
+// din / dout (may be NULL or the identity): the multipliers of the frames and of the head's operand (then Hd, and with bwd its transpose in TB).
+int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T, int B, bool bwd, const DropSpec *din = nullptr,
+                const DropSpec *dout = nullptr) {
     const int F = a->cfg.F, H = a->cfg.H, C = a->cfg.C, dt = a->dt, M = T * B;
     const int64_t ldF = a->ldF, ldH = a->ldH, ld4H = a->ld4H, ldC = a->ldC, ldM = ld64(M);
     hipStream_t st = a->stream;
@@ -276,12 +330,18 @@ int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T,
     // frames, time-major (and transposed for dW)
     {
         const dim3 grid(cdiv(F, 64), cdiv(bwd ? ldM : M, 64));
-        if (dt == GEMM_T_BF16)
-            hipLaunchKernelGGL(act_frames_kernel<bf16_t>, grid, dim3(256), 0, st, feats, F, T, B, (bf16_t *)a->X, ldF,
-                               bwd ? (bf16_t *)a->TB : nullptr, ldM);
-        else
-            hipLaunchKernelGGL(act_frames_kernel<float>, grid, dim3(256), 0, st, feats, F, T, B, (float *)a->X, ldF,
-                               bwd ? (float *)a->TB : nullptr, ldM);
+        const DropSpec none{};
+#define ACT_FRAMES(TY, DROP, D)                                                                                                  \
+    hipLaunchKernelGGL((act_frames_kernel<TY, DROP>), grid, dim3(256), 0, st, feats, F, T, B, (TY *)a->X, ldF,                   \
+                       bwd ? (TY *)a->TB : nullptr, ldM, D)
+        if (drops(din)) {
+            if (dt == GEMM_T_BF16) ACT_FRAMES(bf16_t, true, *din);
+            else ACT_FRAMES(float, true, *din);
+        } else {
+            if (dt == GEMM_T_BF16) ACT_FRAMES(bf16_t, false, none);
+            else ACT_FRAMES(float, false, none);
+        }
+#undef ACT_FRAMES
     }
     KCHK(a, "shadows / frames");
     // input projection of every frame at once: Gx = X W[0:F] + b
@@ -289,12 +349,27 @@ int act_forward(lrcn_act *a, const float *const p[4], const float *feats, int T,
     // recurrence: contracts h only
     if (int r = lstm_recurrence_fwd(a, true, rec_gemm(a), T, B, H, ldH, ld4H, a->Gx, a->Wh, a->acts, a->Call, a->Hall)) return r;
     KCHK(a, "recurrence");
-    // logits of every step: z = h Wout + bout
-    AGEMM(a, a->Hall, ldH, a->Wo, ldH, a->Logits, ldC, M, C, H, p[3]);
+    // logits of every step: z = h Wout + bout, h masked into its second copy Hd under output dropout (Hall stays as the recurrence wrote it)
+    const void *Hhead = a->Hall;
+    if (drops(dout)) {
+        if (!a->Hd) DALLOC(a, a->Hd, a->esz * (size_t)a->cfg.max_B * a->cfg.max_T * ldH);
+        const dim3 grid(cdiv(H, 64), cdiv(bwd ? ldM : M, 64));
+        void *HdT = bwd ? boff(a->TB, (int64_t)(F + H) * ldM, a->esz) : nullptr;
+        if (dt == GEMM_T_BF16)
+            hipLaunchKernelGGL(act_head_drop_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t *)a->Hall, ldH, H, T, B, *dout,
+                               (bf16_t *)a->Hd, (bf16_t *)HdT, ldM);
+        else
+            hipLaunchKernelGGL(act_head_drop_kernel<float>, grid, dim3(256), 0, st, (const float *)a->Hall, ldH, H, T, B, *dout,
+                               (float *)a->Hd, (float *)HdT, ldM);
+        KCHK(a, "head operand");
+        Hhead = a->Hd;
+    }
+    AGEMM(a, Hhead, ldH, a->Wo, ldH, a->Logits, ldC, M, C, H, p[3]);
     return LRCN_OK;
 }
 
-int act_backward(lrcn_act *a, const float *const p[4], int T, int B, float *const g[4]) {
+// dout (may be NULL or the identity): act_forward has left Hd' in TB rows [F+H, F+2H), and dh takes the same multipliers
+int act_backward(lrcn_act *a, const float *const p[4], int T, int B, float *const g[4], const DropSpec *dout = nullptr) {
     (void)p;
     const int F = a->cfg.F, H = a->cfg.H, C = a->cfg.C, dt = a->dt, M = T * B;
     const size_t es = a->esz;
@@ -305,16 +380,17 @@ int act_backward(lrcn_act *a, const float *const p[4], int T, int B, float *cons
         TrDesc &d = pl.d[pl.n++];
         d.src = src; d.ld_src = ld_src; d.R = R; d.C = Cc; d.dst = dst; d.ld_dst = ldM; d.shift = shift;
     };
-    // head: dWout = h' dlog, dbout = colsum(dlog), dh = dlog Wout'
+    // head: dWout = h' dlog (Hd' dlog under output dropout), dbout = colsum(dlog), dh = dlog Wout' (.* m_out)
     {
         TrPlan pl{};
         tr(pl, a->dLog, ldC, M, C, a->TA, 0);                                          // dlog' [C][ldM]
-        tr(pl, a->Hall, ldH, M, H, boff(a->TB, (int64_t)(F + H) * ldM, es), 0);         // h' [H][ldM]
+        if (!drops(dout)) tr(pl, a->Hall, ldH, M, H, boff(a->TB, (int64_t)(F + H) * ldM, es), 0);  // h' [H][ldM]
         k_transpose_multi(st, dt, pl);
     }
     AGEMM(a, a->TA, ldM, boff(a->TB, (int64_t)(F + H) * ldM, es), ldM, g[2], H, C, H, M, nullptr);
     k_colsum(st, dt, a->dLog, ldC, M, C, g[3], det);
     AGEMM(a, a->dLog, ldC, a->WoT, ldC, a->dHall, H, M, H, C, nullptr);
+    if (drops(dout)) hipLaunchKernelGGL(act_dh_mask_kernel, dim3(grid1d((int64_t)M * H)), dim3(256), 0, st, a->dHall, H, T, B, *dout);
     KCHK(a, "head backward");
     // reverse recurrence -> dZ
     if (int r = lstm_recurrence_bwd(a, true, rec_gemm(a), T, B, H, ld4H, a->acts, a->Call, a->dHall, a->WhT, a->dZ)) return r;
@@ -460,19 +536,16 @@ int lrcn_act_init_weights(lrcn_act *a, float *const p[4], uint64_t seed) {
     return LRCN_OK;
 }
 
-int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
-                       float *const g[4], double *loss_host) {
-    if (!a) return LRCN_EINVAL;
-    if (!labels) FAIL(a, LRCN_EINVAL, "null labels");
-    if (g && (!g[0] || !g[1] || !g[2] || !g[3])) FAIL(a, LRCN_EINVAL, "null gradient tensor");
-    int r = check_call(a, p, feats, labels, lens, T, B);
-    if (r) return r;
+// lrcn_act_loss_grad and lrcn_act_loss_grad_drop: din / dout NULL or the identity = the plain call's launches
+static int act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
+                         const DropSpec *din, const DropSpec *dout, float *const g[4], double *loss_host) {
+    int r;
     DeviceGuard dg(a->cfg.device);
     int64_t total = 0;
     for (int b = 0; b < B; ++b) total += lens ? lens[b] : T;
     if ((r = upload_meta(a, labels, lens, T, B))) return r;
     const bool bwd = g != nullptr;
-    if ((r = act_forward(a, p, feats, T, B, bwd))) return r;
+    if ((r = act_forward(a, p, feats, T, B, bwd, din, dout))) return r;
     const int nq = cdiv(a->cfg.C, 256);
     const float scale = (float)(1.0 / (double)total);
     if (a->dt == GEMM_T_BF16)
@@ -483,13 +556,39 @@ int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats,
                            a->ldC, a->loss_clip, nullptr, nullptr);
     hipLaunchKernelGGL(act_loss_sum_kernel, dim3(1), dim3(64), 0, a->stream, a->loss_clip, B, a->loss_sum);
     KCHK(a, "head");
-    if (bwd && (r = act_backward(a, p, T, B, g))) return r;
+    if (bwd && (r = act_backward(a, p, T, B, g, dout))) return r;
     if (loss_host) {
         HIPCHK(a, hipMemcpyAsync(a->hloss, a->loss_sum, sizeof(double), hipMemcpyDeviceToHost, a->stream));
         HIPCHK(a, hipStreamSynchronize(a->stream));
         *loss_host = a->hloss[0] / (double)total;
     }
     return LRCN_OK;
+}
+
+static int check_loss_grad(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
+                           float *const g[4]) {
+    if (!labels) FAIL(a, LRCN_EINVAL, "null labels");
+    if (g && (!g[0] || !g[1] || !g[2] || !g[3])) FAIL(a, LRCN_EINVAL, "null gradient tensor");
+    return check_call(a, p, feats, labels, lens, T, B);
+}
+
+int lrcn_act_loss_grad(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
+                       float *const g[4], double *loss_host) {
+    if (!a) return LRCN_EINVAL;
+    if (int r = check_loss_grad(a, p, feats, labels, lens, T, B, g)) return r;
+    return act_loss_grad(a, p, feats, labels, lens, T, B, nullptr, nullptr, g, loss_host);
+}
+
+int lrcn_act_loss_grad_drop(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *labels, const int32_t *lens, int T, int B,
+                            const lrcn_act_dropout *drop, float *const g[4], double *loss_host) {
+    if (!a) return LRCN_EINVAL;
+    if (int r = check_loss_grad(a, p, feats, labels, lens, T, B, g)) return r;
+    if (!drop) return act_loss_grad(a, p, feats, labels, lens, T, B, nullptr, nullptr, g, loss_host);
+    if (!(drop->p_in >= 0.0f && drop->p_in < 1.0f)) FAIL(a, LRCN_EINVAL, "p_in=%g outside [0,1)", (double)drop->p_in);
+    if (!(drop->p_out >= 0.0f && drop->p_out < 1.0f)) FAIL(a, LRCN_EINVAL, "p_out=%g outside [0,1)", (double)drop->p_out);
+    // which = 1 over the F frame columns, which = 2 over the H output columns; a mask given replaces (p, seed) on its side (drop_mult)
+    const DropSpec din{drop->p_in, drop->seed, drop->mask_in, 1}, dout{drop->p_out, drop->seed, drop->mask_out, 2};
+    return act_loss_grad(a, p, feats, labels, lens, T, B, &din, &dout, g, loss_host);
 }
 
 int lrcn_act_predict(lrcn_act *a, const float *const p[4], const float *feats, const int32_t *lens, int T, int B, float *clip_probs,

@@ -1,7 +1,8 @@
 """Activity recognition (include/lrcn_activity.h) timing on one GPU: ms per loss_grad + Adam step and per predict at T = 16, F = 4096,
 C = 101 (the paper's shape), H = 256 and 1024, B = 32 / 128 / 512 clips, with FLOP rates from the shapes, beside the bf16 VGG forward of
 the same B*T frames.  Prints one line per configuration and a JSON summary line.
-usage: python tools/activity_bench.py [--dtype bf16|f32] [--iters 20] [--vgg-max 2048] [--out FILE]"""
+usage: python tools/activity_bench.py [--dtype bf16|f32] [--iters 20] [--vgg-max 2048] [--drop 0.9,0.5] [--out FILE]
+--drop adds train_drop_ms: the same step with seeded dropout on the frame features and the LSTM output, timed in the same process."""
 import argparse
 import json
 import os
@@ -41,8 +42,12 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=("bf16", "f32"))
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--vgg-max", type=int, default=512, help="largest frame count whose VGG forward is timed directly (above: scaled)")
+    ap.add_argument("--drop", metavar="P_IN,P_OUT", help="also time the step with dropout (include/lrcn_act_dropout.h): train_drop_ms")
     ap.add_argument("--out")
     o = ap.parse_args()
+    drop = tuple(float(v) for v in o.drop.split(",")) if o.drop else None
+    if drop is not None and len(drop) != 2:
+        ap.error("--drop takes P_IN,P_OUT")
     dt = lrcn_amd.LRCN_BF16 if o.dtype == "bf16" else lrcn_amd.LRCN_F32
     F, C, T = 4096, 101, 16
     rng = np.random.default_rng(0)
@@ -75,6 +80,21 @@ def main():
             print("H=%4d B=%3d: loss_grad+adam %.3f ms (%.1f TFLOP/s)  predict %.3f ms (%.1f TFLOP/s)  vgg forward of the %d frames %.1f ms"
                   "  -> train %.1f %%, predict %.1f %% of it" % (H, B, tr * 1e3, r["train_tflops"], pr * 1e3, r["predict_tflops"], B * T,
                                                                  vgg * 1e3, 100 * tr / vgg, 100 * pr / vgg), flush=True)
+            if drop is not None:   # the same model and batch in the same process, a new seed every step as train_step draws it
+                seeds = iter(range(1, 1 << 30))
+                plain = lambda: (m.loss_grad(x, lab, lens, T), m.adam_step(1e-4))  # noqa: E731
+                dropped = lambda: (m.loss_grad(x, lab, lens, T, pdrop_in=drop[0], pdrop_out=drop[1], drop_seed=next(seeds)),  # noqa: E731
+                                   m.adam_step(1e-4))
+                # three alternating windows of each, so that the spread between windows of one kind stands beside the difference
+                tp, td = [], []
+                for _ in range(3):
+                    td.append(timed(dropped, o.iters) * 1e3)
+                    tp.append(timed(plain, o.iters) * 1e3)
+                r.update({"drop": list(drop), "train_drop_ms": float(np.median(td)), "train_drop_ms_windows": td, "train_ms_windows": tp,
+                          "train_drop_over_train": float(np.median(td) / np.median(tp))})
+                print("            with dropout %g / %g: %.3f ms (windows %s) against %.3f ms (windows %s): %.3f x"
+                      % (drop[0], drop[1], np.median(td), " ".join("%.3f" % v for v in td), np.median(tp), " ".join("%.3f" % v for v in tp),
+                         np.median(td) / np.median(tp)), flush=True)
             m.close()
             torch.cuda.empty_cache()
     try:

@@ -6,6 +6,8 @@
     # train the LSTM + softmax head on 16-frame clips with stride 8
     python tools/lrcn_activity.py --train --features train.npz --hidden 256 --clip 16 --stride 8 --batchsize 32 --epochs 10 \
         --lr 1e-3 --atype bf16 --savefile act.npz
+    # the same with the paper's dropout: 0.9 on the frame feature, 0.5 on the LSTM output (seeded by --seed; the reported loss is the masked one)
+    python tools/lrcn_activity.py --train --features train.npz --drop_in 0.9 --drop_out 0.5 --savefile act.npz
     # clip accuracy (mean of a clip's per-step distributions) and video accuracy (mean of its clips' distributions)
     python tools/lrcn_activity.py --eval --loadfile act.npz --features test.npz
 
@@ -46,6 +48,10 @@ def parse(argv):
     p.add_argument("--epochs", type=int, default=1)
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--gclip", type=float, default=0.0, help="Clip the global gradient norm to this on the device (0 = off).")
+    p.add_argument("--drop_in", type=float, default=0.0, metavar="P",
+                   help="--train: dropout on the frame feature that enters the LSTM (the paper: 0.9; 0 = off)")
+    p.add_argument("--drop_out", type=float, default=0.0, metavar="P",
+                   help="--train: dropout on the LSTM output before the classifier (the paper: 0.5; 0 = off)")
     p.add_argument("--atype", default="bf16", choices=("f32", "bf16"), help="arithmetic of the LSTM and the head")
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--savefile")
@@ -144,7 +150,7 @@ def train(o):
             sp = [specs[k] for k in order[i:i + o.batchsize]]
             x, lens = A.gather_clips(vf, sp, o.clip)
             lab = labels[[v for v, _, _ in sp]]
-            tot += m.train_step(x, lab, lens, o.clip, lr=o.lr, gclip=o.gclip) * float(lens.sum())
+            tot += m.train_step(x, lab, lens, o.clip, lr=o.lr, gclip=o.gclip, pdrop_in=o.drop_in, pdrop_out=o.drop_out) * float(lens.sum())
             n += int(lens.sum())
         say("epoch %d loss %.6f" % (ep, tot / max(n, 1)))
     m.sync()
