@@ -23,7 +23,7 @@ CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"
 WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
 SCHED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sched.h"))        # lrcn_*_sched (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
-CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 (not in lrcn.h)
+CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 and the fp8 seams (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -277,6 +277,10 @@ GEMM_DEBUG_SIGNATURES = {
 # name -> (restype, argtypes); exactly the symbols include/lrcn_conv_debug.h declares (bound by lib() as well)
 CONV_DEBUG_SIGNATURES = {
     "lrcn_debug_conv11": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lrcn_debug_fp8_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
+    "lrcn_debug_amax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "lrcn_debug_conv64_f8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "lrcn_debug_fp8_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 }
 
 

@@ -5,6 +5,14 @@
 //   activations  x8 = e4m3(x / sa),                    sa = margin * amax / 448        (per tensor, from lrcn_vgg_calibrate)
 //   layer        y8 = e4m3(relu(acc * escale[co] + ebias[co])),  escale = sa_in sw / sa_out,  ebias = b / sa_out
 // (the 2x2 max-pool, where fused, commutes with the positive scale and the monotone rounding).
+// conv2_1 (bf16) -> conv2_2 (e4m3) has two routes:
+//   direct  conv64.hip's epilogue writes e4m3(min(relu(acc + b) / sa, 448)) from the f32 sum (f8_inv_scale > 0; the default)
+//           -- by itself: lrcn_debug_conv64_f8, tests/test_gpu_fp8_seams.py against a float64 host emulation
+//   cast    any other conv2_1 kernel (LRCN_CONV64=0) writes bf16 and cast_bf16_fp8_kernel below quantises that ROUNDED value
+//           -- by itself: lrcn_debug_fp8_cast, bit for bit on every bf16 pattern and past the grid cap; in the stack:
+//              the cast-route test of tests/test_gpu_vgg_parity.py
+// The two agree to one e4m3 step, not bit for bit.  cast_fp8_bf16_kernel (pool5 -> fc6) runs on every fp8 forward.
+// Every conversion is clamped to +-448 first: v_cvt_pk_fp8_f32 rounds to nearest even (subnormals included) but does not saturate.
 // The reference has no reduced-precision path (lrcn.jl:724-728 runs conv4 in Float32); parity of this path is stated
 // against the fp32 CPU oracle with the tolerance written in tests/test_gpu_vgg_parity.py.
 #include "common.h"
@@ -47,7 +55,7 @@ __global__ __launch_bounds__(256) void quant_conv_w_fp8_kernel(const float *w, i
     }
 }
 
-template <typename T> __global__ __launch_bounds__(256) void amax_kernel(const T *x, int64_t n, float *out) {
+__global__ __launch_bounds__(256) void amax_kernel(const bf16_t *x, int64_t n, float *out) {
     __shared__ float sh[4];
     float m = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(to_f32(x[i])));
@@ -120,11 +128,8 @@ inline unsigned grid_for(int64_t n) {
 void k_quant_conv_w_fp8(hipStream_t st, const float *w, int Cin, int Cout, void *out, float *sw) {
     hipLaunchKernelGGL(quant_conv_w_fp8_kernel, dim3(Cout), dim3(256), 0, st, w, Cin, Cout, (unsigned char *)out, sw);
 }
-void k_amax(hipStream_t st, int in_f32, const void *x, int64_t n, float *out) {
-    if (in_f32)
-        hipLaunchKernelGGL(amax_kernel<float>, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(256), 0, st, (const float *)x, n, out);
-    else
-        hipLaunchKernelGGL(amax_kernel<bf16_t>, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(256), 0, st, (const bf16_t *)x, n, out);
+void k_amax(hipStream_t st, const void *x, int64_t n, float *out) {
+    hipLaunchKernelGGL(amax_kernel, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(256), 0, st, (const bf16_t *)x, n, out);
 }
 void k_cast_bf16_fp8(hipStream_t st, const void *x, int64_t n, float inv_scale, void *out) {
     hipLaunchKernelGGL(cast_bf16_fp8_kernel, dim3(grid_for(n / 8)), dim3(256), 0, st, (const bf16_t *)x, n / 8, inv_scale, (uint2 *)out);

@@ -250,7 +250,7 @@ int vgg_body(lrcn_ctx *c, int N, const void *src, bool src_u8, const float *mean
         if (r) return r;
         note(gemm_debug_last_route());
         std::swap(cur, nxt);
-        if (calibrate && l >= kFp8First - 1) k_amax(c->stream, 0, cur, out_count(l), c->amax_dev + l);
+        if (calibrate && l >= kFp8First - 1) k_amax(c->stream, cur, out_count(l), c->amax_dev + l);
     }
     if (fp8) {  // pool5 e4m3 -> bf16 for fc6
         k_cast_fp8_bf16(c->stream, cur, out_count(12), c->act_scale[12], nxt);
@@ -754,6 +754,77 @@ int lrcn_debug_conv11(lrcn_ctx *c, const void *src, int src_is_u8, int N, int S,
     const hipError_t e = hipGetLastError();
     cleanup();
     if (e != hipSuccess) FAIL(c, LRCN_EHIP, "debug_conv11: %s", hipGetErrorString(e));
+    return LRCN_OK;
+}
+
+// Test entries of the fp8 stack's seams (include/lrcn_conv_debug.h)
+int lrcn_debug_fp8_cast(lrcn_ctx *c, int dir, const void *src, int64_t n, float factor, void *dst) {
+    DeviceGuard dg(c);
+    if (!c || !src || !dst) return LRCN_EINVAL;
+    if (c->vdt != GEMM_T_BF16) FAIL(c, LRCN_EINVAL, "debug_fp8_cast: the context's vgg_dtype must be LRCN_BF16 or LRCN_FP8");
+    if (n < 8 || n % 8 || (reinterpret_cast<uintptr_t>(src) & 15) || (reinterpret_cast<uintptr_t>(dst) & 15))
+        FAIL(c, LRCN_EINVAL, "debug_fp8_cast: n=%lld must be a positive multiple of 8, both buffers 16-byte aligned", (long long)n);
+    if (!(factor > 0.0f) || !std::isfinite(factor)) FAIL(c, LRCN_EINVAL, "debug_fp8_cast: factor=%g must be finite and positive", factor);
+    if (dir == 0)
+        k_cast_bf16_fp8(c->stream, src, n, factor, dst);
+    else
+        k_cast_fp8_bf16(c->stream, src, n, factor, dst);
+    KCHK(c, "debug_fp8_cast");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LRCN_OK;
+}
+
+int lrcn_debug_amax(lrcn_ctx *c, const void *x_bf16, int64_t n, float *out_dev) {
+    DeviceGuard dg(c);
+    if (!c || !x_bf16 || !out_dev) return LRCN_EINVAL;
+    if (n < 1) FAIL(c, LRCN_EINVAL, "debug_amax: n=%lld < 1", (long long)n);
+    HIPCHK(c, hipMemsetAsync(out_dev, 0, sizeof(float), c->stream));
+    k_amax(c->stream, x_bf16, n, out_dev);
+    KCHK(c, "debug_amax");
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LRCN_OK;
+}
+
+int lrcn_debug_conv64_f8(lrcn_ctx *c, const float *x, int W, int H, int N, const float *w, const float *b, int Cout, float f8_inv_scale,
+                         float *y) {
+    DeviceGuard dg(c);
+    if (!c || !x || !w || !b || !y) return LRCN_EINVAL;
+    if (c->vdt != GEMM_T_BF16) FAIL(c, LRCN_EINVAL, "debug_conv64_f8: the context's vgg_dtype must be LRCN_BF16 or LRCN_FP8");
+    if (N < 1 || !conv64_eligible(GEMM_T_BF16, 64, Cout, H, W) || (int64_t)N * H * W * 64 >= (1ll << 31))
+        FAIL(c, LRCN_EINVAL, "debug_conv64_f8: W, H multiples of 16, Cout a multiple of 64, N >= 1, N*W*H*64 < 2^31");
+    if (!(f8_inv_scale > 0.0f) || !std::isfinite(f8_inv_scale))
+        FAIL(c, LRCN_EINVAL, "debug_conv64_f8: f8_inv_scale=%g must be finite and positive", f8_inv_scale);
+    void *xin = nullptr, *wp = nullptr, *out = nullptr;
+    float *bd = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(c->stream);
+        (void)hipFree(xin);
+        (void)hipFree(wp);
+        (void)hipFree(out);
+        (void)hipFree(bd);
+    };
+    if (hipMalloc(&xin, 2 * (size_t)N * H * W * 64) != hipSuccess || hipMalloc(&wp, 2 * (size_t)Cout * 9 * 64) != hipSuccess ||
+        hipMalloc(&out, (size_t)N * H * W * Cout) != hipSuccess || hipMalloc((void **)&bd, sizeof(float) * Cout) != hipSuccess) {
+        cleanup();
+        FAIL(c, LRCN_ENOMEM, "debug_conv64_f8 scratch");
+    }
+    (void)hipMemcpyAsync(bd, b, sizeof(float) * Cout, hipMemcpyDeviceToDevice, c->stream);
+    k_ref_to_nhwc(c->stream, GEMM_T_BF16, x, W, H, 64, N, xin, 64);
+    k_repack_conv_w(c->stream, GEMM_T_BF16, w, 64, Cout, 64, wp);
+    hipError_t e = launch_conv64(c->stream, xin, wp, bd, out, N, H, W, Cout, 1, 0, c->zero_page, f8_inv_scale, c->vgg_wg_cap);
+    if (e == hipSuccess) {
+        k_nhwc_fp8_to_ref(c->stream, out, W, H, Cout, N, 1.0f, y);
+        e = hipGetLastError();
+    }
+    cleanup();
+    if (e != hipSuccess) FAIL(c, LRCN_EHIP, "debug_conv64_f8: %s", hipGetErrorString(e));
+    return LRCN_OK;
+}
+
+int lrcn_debug_fp8_scales(lrcn_ctx *c, float out[13]) {
+    if (!c || !out) return LRCN_EINVAL;
+    if (!c->vgg_fp8 || !c->fp8_ready) FAIL(c, LRCN_ESTATE, "debug_fp8_scales: needs a vgg_dtype = LRCN_FP8 context after lrcn_vgg_calibrate");
+    for (int l = 0; l < 13; ++l) out[l] = l >= kFp8First - 1 ? c->act_scale[l] : 0.0f;
     return LRCN_OK;
 }
 

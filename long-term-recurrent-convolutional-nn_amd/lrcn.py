@@ -891,6 +891,46 @@ def debug_conv11(ctx, src, w11, b11, mean=VGG_MEAN):
     return y
 
 
+def debug_fp8_cast(ctx, src, factor, to_fp8):
+    """One of fp8.hip's two casts (lrcn_debug_fp8_cast, include/lrcn_conv_debug.h) on a flat device tensor: to_fp8 -- bfloat16 [n] -> e4m3
+    bytes (uint8 [n]) = e4m3(clamp(src * factor)); otherwise e4m3 bytes (uint8 [n]) -> bfloat16 [n] = bf16(src * factor)."""
+    if src.dtype != (torch.bfloat16 if to_fp8 else torch.uint8) or src.dim() != 1 or not src.is_cuda or not src.is_contiguous():
+        raise LrcnError("debug_fp8_cast takes a flat device tensor, bfloat16 towards e4m3 and uint8 from it")
+    dst = torch.empty(src.numel(), dtype=torch.uint8 if to_fp8 else torch.bfloat16, device=src.device)
+    ctx._call("lrcn_debug_fp8_cast", 0 if to_fp8 else 1, C.c_void_p(src.data_ptr()), src.numel(), float(factor), C.c_void_p(dst.data_ptr()))
+    return dst
+
+
+def debug_amax(ctx, x_bf16, out=None):
+    """max |x| of a flat bfloat16 device tensor through the calibration pass's kernel (lrcn_debug_amax) -> one-element float32 device
+    tensor (`out`, if given, is overwritten: the entry zeroes it first)."""
+    if x_bf16.dtype != torch.bfloat16 or not x_bf16.is_cuda or not x_bf16.is_contiguous():
+        raise LrcnError("debug_amax takes a contiguous bfloat16 device tensor")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=x_bf16.device)
+    ctx._call("lrcn_debug_amax", C.c_void_p(x_bf16.data_ptr()), x_bf16.numel(), C.c_void_p(out.data_ptr()))
+    return out
+
+
+def debug_conv64_f8(ctx, x, w, b, f8_inv_scale):
+    """conv2_1's e4m3 epilogue by itself (lrcn_debug_conv64_f8; conv64.hip with f8_inv_scale > 0): x (W,H,64,N), w (3,3,64,Cout), b [Cout]
+    -> (W,H,Cout,N) holding the e4m3 values e4m3(min(relu(conv + b) * f8_inv_scale, 448)), undequantised."""
+    W, H, Cin, N = x.shape
+    if Cin != 64:
+        raise LrcnError("debug_conv64_f8: Cin must be 64")
+    Cout = w.shape[3]
+    y = jl_empty(W, H, Cout, N)
+    ctx._call("lrcn_debug_conv64_f8", _ptr(x), W, H, N, _ptr(w), _ptr(b), Cout, float(f8_inv_scale), _ptr(y))
+    return y
+
+
+def debug_fp8_scales(ctx):
+    """The 13 per-layer activation scales of the last lrcn_vgg_calibrate (lrcn_debug_fp8_scales) as a float32 array; 0 below conv2_1."""
+    out = (C.c_float * 13)()
+    ctx._call("lrcn_debug_fp8_scales", out)
+    return np.array(out[:], dtype=np.float32)
+
+
 def vgg_set_wg_cap(ctx, cap):
     """Cap the VGG convolution grids at `cap` workgroups (0 = off): include/lrcn.h lrcn_vgg_set_wg_cap."""
     ctx._call("lrcn_vgg_set_wg_cap", int(cap))

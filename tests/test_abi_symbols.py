@@ -49,7 +49,11 @@ def test_conv_debug_binding_declares_exactly_its_header():
     # include/lrcn_conv_debug.h: a test entry beside the ABI -- exported by the library, bound by its own table, absent from lrcn.h
     raw = open(_lib.CONV_DEBUG_HEADER).read()
     txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.CONV_DEBUG_SIGNATURES) == ["lrcn_debug_conv11"]
-    assert "lrcn_debug_conv11" not in _lib.SIGNATURES and "lrcn_debug_conv11" not in open(_lib.HEADER).read()
+    names = ["lrcn_debug_amax", "lrcn_debug_conv11", "lrcn_debug_conv64_f8", "lrcn_debug_fp8_cast", "lrcn_debug_fp8_scales"]
+    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.CONV_DEBUG_SIGNATURES) == names
+    header = open(_lib.HEADER).read()
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    for name in names:
+        assert name not in _lib.SIGNATURES and name not in header, name
+        assert hasattr(so, name), name
     assert "#define LRCN_ABI_VERSION" not in raw and '#include "lrcn.h"' in raw
-    assert hasattr(ctypes.CDLL(_lib.LIB_PATH), "lrcn_debug_conv11")
