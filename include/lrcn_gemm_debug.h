@@ -1,6 +1,6 @@
-/* lrcn_gemm_debug.h -- one contraction through the GEMM router with caller-given operands: the test entry of the plain GEMM engines, beside the
- * C ABI of include/lrcn.h (which it includes; LRCN_ABI_VERSION is unchanged).  Implemented by liblrcn_hip.so only: the CPU oracle does not
- * implement this entry point. */
+/* lrcn_gemm_debug.h -- one contraction through the GEMM router with caller-given operands: the test entries of the GEMM engines in their
+ * plain (lrcn_debug_gemm) and 3x3-convolution (lrcn_debug_conv_gemm) operand modes, beside the C ABI of include/lrcn.h (which it includes;
+ * LRCN_ABI_VERSION is unchanged).  Implemented by liblrcn_hip.so only: the CPU oracle does not implement these entry points. */
 #ifndef LRCN_GEMM_DEBUG_H
 #define LRCN_GEMM_DEBUG_H
 
@@ -35,6 +35,30 @@ typedef struct lrcn_gemm_debug {
  * LRCN_EINVAL when ctx or g is NULL, dtype is neither LRCN_F32 nor LRCN_BF16, or the router refuses the arguments (it does so on the host,
  * before any launch: C is untouched); LRCN_EHIP for any other HIP error. */
 int lrcn_debug_gemm(lrcn_ctx *ctx, const lrcn_gemm_debug *g);
+
+/* One 3x3 convolution (stride 1, zero padding 1) (+ bias[Cout]) (ReLU) (2x2 maximum) through the same router in its CONV3 operand mode: the
+ * implicit-GEMM form every VGG layer from conv2_2 on runs in.  As above, every pointer is a device pointer that the caller allocated and
+ * filled in the ENGINE's layouts and element type; the entry allocates nothing, converts nothing and never goes to conv64.hip.
+ *   y[n][r][q][co] = sum over kh, kw, c of x[n][r + kh - 1][q + kw - 1][c] * w[co][kh * 3 + kw][c]   (terms outside the image are zero) */
+typedef struct lrcn_conv_gemm_debug {
+    int dtype;            /* LRCN_F32 or LRCN_BF16: element type of x, w and y */
+    const void *x;        /* NHWC [N][H][W][Cin] */
+    const void *w;        /* [Cout][9][Cin] */
+    const float *bias;    /* [Cout] f32, 16-byte aligned, or NULL */
+    void *y;              /* [N][H][W] rows of ldc elements; pool: [N][H/2][W/2] rows of ldc elements */
+    int64_t ldc;          /* elements, >= Cout */
+    int N, H, W, Cin, Cout;
+    int relu;
+    int pool;             /* 1: the maximum over each 2x2 window (after bias and ReLU) */
+    int wg_cap;           /* > 0: at most this many workgroups walk the tiles (what lrcn_vgg_set_wg_cap gives the layers of a forward) */
+} lrcn_conv_gemm_debug;
+
+/* Fills the router's arguments as a VGG layer's launch does (CONV3 operand mode, CONV or POOL output mode, K = ldb = 9 Cin, the context's
+ * zero page, its split-K workspace and its stream; static tile walk, no tile queues), launches, and waits for the stream.  Afterwards
+ * lrcn_debug_route(ctx, 0) names the rung that ran: "8p:<tile config>", "8p-splitk:<slices>", "glds", "glds-small", "gemm_nt".
+ * LRCN_EINVAL when ctx or g is NULL, dtype is neither LRCN_F32 nor LRCN_BF16, or the router refuses the arguments (on the host, before any
+ * launch: y is untouched); LRCN_EHIP for any other HIP error. */
+int lrcn_debug_conv_gemm(lrcn_ctx *ctx, const lrcn_conv_gemm_debug *g);
 
 #ifdef __cplusplus
 }

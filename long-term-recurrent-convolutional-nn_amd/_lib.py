@@ -60,6 +60,12 @@ class GemmDebug(C.Structure):   # lrcn_gemm_debug of include/lrcn_gemm_debug.h
                 ("free_cus", C.c_int), ("bg_cus", C.c_int), ("wg_cap", C.c_int)]
 
 
+class ConvGemmDebug(C.Structure):   # lrcn_conv_gemm_debug of include/lrcn_gemm_debug.h
+    _fields_ = [("dtype", C.c_int), ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldc", C.c_int64),
+                ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("relu", C.c_int), ("pool", C.c_int),
+                ("wg_cap", C.c_int)]
+
+
 class Dropout(C.Structure):
     _fields_ = [("pdrop", C.c_float), ("seed", C.c_uint64), ("mask1", C.c_void_p), ("mask2", C.c_void_p)]
 
@@ -272,6 +278,7 @@ CLIP_SIGNATURES = {
 # name -> (restype, argtypes); exactly the symbols include/lrcn_gemm_debug.h declares (bound by lib() as well)
 GEMM_DEBUG_SIGNATURES = {
     "lrcn_debug_gemm": (C.c_int, [C.c_void_p, C.POINTER(GemmDebug)]),
+    "lrcn_debug_conv_gemm": (C.c_int, [C.c_void_p, C.POINTER(ConvGemmDebug)]),
 }
 
 # name -> (restype, argtypes); exactly the symbols include/lrcn_conv_debug.h declares (bound by lib() as well)

@@ -472,6 +472,46 @@ int lrcn_debug_gemm(lrcn_ctx *c, const lrcn_gemm_debug *d) {
     return LRCN_OK;
 }
 
+// Test entry (include/lrcn_gemm_debug.h): ONE 3x3 convolution through launch_gemm in CONV3 mode on the caller's NHWC operands, filled as
+// conv_args / lrcn_conv3x3 fill theirs (static tile walk: no tile queues).  No allocation, no conversion, never conv64.hip; the stream is
+// drained before the call returns.
+int lrcn_debug_conv_gemm(lrcn_ctx *c, const lrcn_conv_gemm_debug *d) {
+    DeviceGuard dg(c);
+    if (!c || !d) return LRCN_EINVAL;
+    if (d->dtype != LRCN_F32 && d->dtype != LRCN_BF16) FAIL(c, LRCN_EINVAL, "debug_conv_gemm: dtype %d is neither f32 nor bf16", d->dtype);
+    if (d->N < 1 || d->H < 2 || d->W < 2 || d->Cin < 1 || d->Cout < 1 || d->ldc < d->Cout || (int64_t)d->N * d->H * d->W > 0x7FFFFFFF ||
+        (int64_t)9 * d->Cin > 0x7FFFFFFF)
+        FAIL(c, LRCN_EINVAL, "debug_conv_gemm: N=%d H=%d W=%d Cin=%d Cout=%d ldc=%lld", d->N, d->H, d->W, d->Cin, d->Cout, (long long)d->ldc);
+    GemmArgs g{};
+    g.dtype = d->dtype == LRCN_BF16 ? GEMM_T_BF16 : GEMM_T_F32;
+    g.A = d->x;
+    g.B = d->w;
+    g.ldb = 9 * (int64_t)d->Cin;
+    g.C = d->y;
+    g.ldc = d->ldc;
+    g.M = d->N * d->H * d->W;
+    g.N = d->Cout;
+    g.K = 9 * d->Cin;
+    g.bias = d->bias;
+    g.relu = d->relu != 0;
+    g.a_mode = GEMM_A_CONV3;
+    g.out_mode = d->pool ? GEMM_OUT_POOL : GEMM_OUT_CONV;
+    g.H = d->H;
+    g.W = d->W;
+    g.Cin = d->Cin;
+    g.zero_page = c->zero_page;
+    g.ws = c->gemm_ws;
+    g.ws_bytes = c->gemm_ws_bytes;
+    g.wg_cap = d->wg_cap;
+    g.tile_ctr = nullptr;
+    const hipError_t e = launch_gemm(c->stream, g);
+    if (e != hipSuccess)
+        FAIL(c, e == hipErrorInvalidValue ? LRCN_EINVAL : LRCN_EHIP, "debug_conv_gemm N=%d H=%d W=%d Cin=%d Cout=%d: %s", d->N, d->H, d->W, d->Cin,
+             d->Cout, hipGetErrorString(e));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LRCN_OK;
+}
+
 // ---- input feed (rev 4) ----
 int lrcn_host_alloc(void **host_ptr, size_t bytes) {
     if (!host_ptr) return LRCN_EINVAL;

@@ -980,6 +980,25 @@ def debug_gemm(ctx, dtype, A, B, Cmat, M, N, K, lda, ldb, ldc, bias=None, c_f32=
     return debug_route(ctx, 0)
 
 
+def debug_conv_gemm(ctx, dtype, x, w, y, N, H, W, Cin, Cout, ldc, bias=None, relu=False, pool=False, wg_cap=0):
+    """One 3x3 convolution (+ bias) (ReLU) (2x2 maximum) through the GEMM router's CONV3 mode on the caller's device operands
+    (lrcn_debug_conv_gemm, include/lrcn_gemm_debug.h): x NHWC [N][H][W][Cin], w [Cout][9][Cin], y [N][H][W] (pooled: [N][H/2][W/2]) rows
+    of ldc elements, all in the element type `dtype` names; bias f32.  Device tensors (sub-views welcome: data_ptr() is what goes down) or
+    raw addresses (int / None).  Returns the route that ran (debug_route(ctx, 0))."""
+    def addr(t):
+        if t is None:
+            return None
+        if torch.is_tensor(t):
+            if not t.is_cuda:
+                raise LrcnError("expected a CUDA (HIP) tensor")
+            return C.c_void_p(t.data_ptr())
+        return C.c_void_p(int(t))
+    g = _lib.ConvGemmDebug(int(dtype), addr(x), addr(w), addr(bias), addr(y), int(ldc), int(N), int(H), int(W), int(Cin), int(Cout),
+                           int(bool(relu)), int(bool(pool)), int(wg_cap))
+    ctx._call("lrcn_debug_conv_gemm", C.byref(g))
+    return debug_route(ctx, 0)
+
+
 def synthetic_vgg_weights(seed=1, device="cuda", bias_std=0.0):
     """He-normal(fan_in) VGG-16 weights (no pretrained file offline); biases zero, or N(0, bias_std)
     so that every bias path of the kernels sees non-zero values (parity tests)."""

@@ -80,5 +80,7 @@ def test_integer_conditions_reject_small_magnitudes():
 
 def test_binding_declares_exactly_the_header():
     txt = re.sub(r"/\*.*?\*/", "", open(_lib.GEMM_DEBUG_HEADER).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.GEMM_DEBUG_SIGNATURES) == ["lrcn_debug_gemm"]
-    assert "lrcn_debug_gemm" not in _lib.SIGNATURES and "lrcn_debug_gemm" not in open(_lib.HEADER).read()
+    names = ["lrcn_debug_conv_gemm", "lrcn_debug_gemm"]
+    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.GEMM_DEBUG_SIGNATURES) == names
+    for name in names:
+        assert name not in _lib.SIGNATURES and name not in open(_lib.HEADER).read()
