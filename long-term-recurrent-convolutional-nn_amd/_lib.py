@@ -22,6 +22,7 @@ VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varle
 CLIP_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_clip.h"))          # lrcn_clip_* / *_clipped / *_clip (not in lrcn.h)
 WEIGHTED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_weighted.h"))  # lrcn_*_w (not in lrcn.h)
 SCHED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sched.h"))        # lrcn_*_sched (not in lrcn.h)
+SMOOTH_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_smooth.h"))      # lrcn_*_smooth / lrcn_xent_logits (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 and the fp8 seams (not in lrcn.h)
 
@@ -249,6 +250,21 @@ SCHED_SIGNATURES = {
     "lrcn_sched_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_smooth.h declares (bound by lib() as well)
+SMOOTH_SIGNATURES = {
+    "lrcn_loss_smooth": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int64,
+                                   C.POINTER(Dropout), C.POINTER(Sched), C.c_void_p, C.c_float, C.POINTER(C.c_double)]),
+    "lrcn_loss_grad_smooth": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int, C.c_int,
+                                        C.c_int64, C.POINTER(Dropout), C.POINTER(Sched), C.c_void_p, C.c_float, P9, C.POINTER(C.c_double)]),
+    "lrcn_train_step_smooth": (C.c_int, [C.c_void_p, P9, P9, P9, P9, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_float), C.c_int,
+                                         C.c_int, C.c_int64, C.POINTER(Dropout), C.POINTER(Sched), C.c_float, C.c_int, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double)]),
+    "lrcn_smooth_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "lrcn_xent_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                   C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+}
+
+
 
 class ClipStats(C.Structure):
     """lrcn_clip_stats_t (include/lrcn_clip.h)."""
@@ -294,7 +310,7 @@ CONV_DEBUG_SIGNATURES = {
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER,
-                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -315,7 +331,7 @@ def lib():
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + \
-                list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + \
+                list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + list(SMOOTH_SIGNATURES.items()) + \
                 list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res

@@ -7,7 +7,7 @@
 
 #include "comm.h"
 #include "host.h"
-#include "../../include/lrcn_sched.h"
+#include "../../include/lrcn_smooth.h"
 
 namespace lrcn_impl {
 
@@ -104,6 +104,12 @@ struct lrcn_ctx {
     float *roww_dev = nullptr, *roww_pin = nullptr;
     hipEvent_t roww_up[kLenSlots] = {};
     int roww_slot = 0;
+    // include/lrcn_smooth.h, lazily: the second accumulator of a label-smoothed call (the sum of the plain log-likelihood terms), its per-row
+    // slots [maxS * maxB] under LRCN_OPT_DETERMINISTIC, and lrcn_xent_logits' scratch (checked targets, row terms nobody asked for)
+    double *nll_acc = nullptr, *ll_rows = nullptr;
+    float last_smooth = -1.0f;       // the smooth of the most recent *_smooth call (< 0: there has been none)
+    void *xl_arena = nullptr;
+    size_t xl_bytes = 0;
     long long *sched_cnt = nullptr;  // include/lrcn_sched.h, lazily: {coins taken, coins fired} of the most recent scheduled-sampling call
     int cur_B = 0;  // rows of the loss / lossgradient call in flight (gemm() picks its "beside the convolutions" hint by it)
     // single-step scratch (lrcn_lstm / lrcn_step / beam search), row-major
@@ -267,6 +273,7 @@ struct LossCall {
     const int32_t *lens = nullptr;        // host [B]: the variable-length form (include/lrcn_varlen.h)
     const float *row_w = nullptr;         // host [B], with lens: a weight per caption (include/lrcn_weighted.h)
     const lrcn_sched *ss = nullptr;       // with lens: scheduled sampling (include/lrcn_sched.h; eps > 0: the stepwise forward)
+    float smooth = 0.0f;                  // > 0, with lens: label smoothing (include/lrcn_smooth.h) -- k_softmax_xent_smooth is the loss kernel
     int32_t *fed_out = nullptr;           // device [T+1][B], with ss: the words that were fed
     float *logits_out = nullptr;          // device, (T+1) blocks of B x V column-major
     enum Form { PLAIN, VAR, WEIGHTED, SCHED } form = PLAIN;   // which of lens / row_w / ss the entry point requires (train.hip loss_entry checks it)

@@ -74,6 +74,23 @@ void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64
 // log-likelihood term row_w[b] * log p(target), in double.
 void k_softmax_xent_weighted(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
                              double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w, int B);
+// Label smoothing (include/lrcn_smooth.h), a form of the masked kernels: the row's target distribution is (1 - eps) onehot(t) + eps / V, so
+//   term = w ((1 - eps) ll + eps u),  ll = (z_t - max) - log(sum exp),  u = sum_v (z_v - max) / V - log(sum exp)
+//   dlog_v = (softmax_v - (1 - eps) [v == t] - eps / V) * (scale * w)
+// with w = row_w[m % B], or 1 when row_w is NULL.  The smoothed term goes where the other forms put theirs (logp_rows[m], else a double
+// atomic into *logp_sum) and the plain w * ll likewise into ll_rows[m], else *ll_sum; a NULL destination is left out.
+struct XentSmooth {
+    float eps;           // 0 < eps <= 1 (0 is the other launchers' business)
+    const float *row_w;  // device f32 [B] or NULL
+    int B;
+    double *ll_sum;      // the accumulator of the unsmoothed terms, or NULL
+    double *ll_rows;     // [M] with logp_rows: their per-row slots, or NULL
+};
+// logp_rows with a NULL logp_sum (and ll_rows with a NULL ll_sum): the rows are written and not summed (lrcn_xent_logits).
+void k_softmax_xent_smooth(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
+                           double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const XentSmooth &sm);
+// out[m] = tgt[m] in [0, V) ? tgt[m] : -1 (lrcn_xent_logits: a caller's target can never index outside its logits row)
+void k_xent_targets(hipStream_t st, const int32_t *tgt, int M, int V, int32_t *out);
 
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)

@@ -167,6 +167,7 @@ void lrcn_destroy(lrcn_ctx *c) {
     (void)hipDeviceSynchronize();
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->sc_arena) (void)hipFree(c->sc_arena);
+    if (c->xl_arena) (void)hipFree(c->xl_arena);
     for (auto &e : c->grad_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->wg_fork)

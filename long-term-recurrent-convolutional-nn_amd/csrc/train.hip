@@ -1,5 +1,5 @@
 // train.hip -- the caption model's forward / backward pass on one gfx950 device, and its loss and train-step entry points (include/lrcn.h,
-// lrcn_varlen.h, lrcn_clip.h, lrcn_weighted.h, lrcn_sched.h), each of which describes its call in one LossCall (ctx.h) filled by member name.
+// lrcn_varlen.h, lrcn_clip.h, lrcn_weighted.h, lrcn_sched.h, lrcn_smooth.h), each of which describes its call in one LossCall (ctx.h) filled by member name.
 //
 // Orchestration of the hot path on one gfx950 device.  The reference runs lrcn() once per timestep with ~50 tiny
 // kernels and a blocking D2H per step (lrcn.jl:560-570); here everything that does not feed back through the
@@ -20,6 +20,7 @@
 #include "../../include/lrcn_clip.h"
 #include "../../include/lrcn_weighted.h"
 #include "../../include/lrcn_sched.h"
+#include "../../include/lrcn_smooth.h"
 
 using namespace lrcn_impl;
 
@@ -207,6 +208,7 @@ int upload_row_w(lrcn_ctx *c, const float *w, int B) { return upload_rows(c, w, 
 // row_w[b]; the chain after the softmax-NLL kernel is linear in d(logits), so only that launch differs.
 // q.ss (with lens): scheduled sampling of include/lrcn_sched.h.  eps == 0 changes nothing but the counters and fed_out; eps > 0 runs
 // the forward step by step (sched_forward below) into the same buffers and rejoins at the softmax-NLL launch.
+// q.smooth > 0 (with lens): label smoothing of include/lrcn_smooth.h -- again only the softmax-NLL launch differs.
 int lrcn_impl::loss_impl(lrcn_ctx *c, const LossCall &q) {
     const int T = q.T, B = q.B;
     int r = check_shapes(c, T, B, q.norm_B);
@@ -230,6 +232,8 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const LossCall &q) {
         for (int b = 0; b < B; ++b)
             if (!std::isfinite(q.row_w[b])) FAIL(c, LRCN_EINVAL, "row_w[%d]=%g is not finite", b, (double)q.row_w[b]);
     }
+    if (!(q.smooth >= 0.0f && q.smooth <= 1.0f)) FAIL(c, LRCN_EINVAL, "smooth=%g outside [0,1]", (double)q.smooth);
+    if (q.smooth > 0.0f && !q.lens) FAIL(c, LRCN_EINVAL, "label smoothing needs lens");
     if (q.drop && (q.drop->pdrop < 0.0f || q.drop->pdrop >= 1.0f)) FAIL(c, LRCN_EINVAL, "pdrop=%g outside [0,1)", q.drop->pdrop);
     if (q.drop && c->nl == 2 && ((q.drop->mask1 == nullptr) != (q.drop->mask2 == nullptr))) FAIL(c, LRCN_EINVAL, "mask1/mask2 must both be set");
     const int dt = c->dt, E = c->E, H1 = c->H1, H2 = c->H2, h = c->h, V = c->V, X1 = c->X1;
@@ -370,7 +374,15 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const LossCall &q) {
     if (c->opt_det && !c->logp_rows) DALLOC(c, c->logp_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
     void *const dlog = bwd ? c->dLog : nullptr;
     double *const rows = c->opt_det ? c->logp_rows : nullptr;
-    if (q.row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
+    if (q.smooth > 0.0f) {  // label smoothing: the plain terms go to a second accumulator (lrcn_smooth_stats)
+        if (!c->nll_acc) DALLOC(c, c->nll_acc, sizeof(double));
+        if (rows && !c->ll_rows) DALLOC(c, c->ll_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
+        HIPCHK(c, hipMemsetAsync(c->nll_acc, 0, sizeof(double), st));
+        XentSmooth sm{};
+        sm.eps = q.smooth; sm.row_w = q.row_w ? c->roww_dev : nullptr; sm.B = B;
+        sm.ll_sum = c->nll_acc; sm.ll_rows = rows ? c->ll_rows : nullptr;
+        k_softmax_xent_smooth(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, sm);
+    } else if (q.row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
     else (q.lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows);
     c->last_norm = q.norm_B;
     c->last_S = S;
@@ -712,6 +724,105 @@ int lrcn_sched_stats(lrcn_ctx *c, int64_t *eligible, int64_t *drawn) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (eligible) *eligible = n[0];
     if (drawn) *drawn = n[1];
+    return LRCN_OK;
+}
+
+// ---- include/lrcn_smooth.h: label smoothing (row_w and ss optional) ----
+namespace {
+// the LossCall of a *_smooth entry point: the padded batch with whichever of row_w / ss is given; smooth is checked before any GPU work
+int smooth_call(lrcn_ctx *c, LossCall &q, const int32_t *lens, const float *row_w, int64_t norm_tokens, const lrcn_sched *ss, float smooth) {
+    if (!c) return LRCN_EINVAL;
+    if (!(smooth >= 0.0f && smooth <= 1.0f)) FAIL(c, LRCN_EINVAL, "smooth=%g outside [0,1]", (double)smooth);
+    q.form = LossCall::VAR; q.lens = lens; q.row_w = row_w; q.norm_tokens = norm_tokens; q.ss = ss; q.smooth = smooth;
+    return LRCN_OK;
+}
+}  // namespace
+
+int lrcn_loss_smooth(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens, const float *row_w,
+                     int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss, int32_t *fed_out, float smooth,
+                     double *loss_host) {
+    LossCall q{};
+    if (int r = smooth_call(c, q, lens, row_w, norm_tokens, ss, smooth)) return r;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.fed_out = fed_out;
+    const int r = loss_entry(c, q, loss_host);
+    if (!r) c->last_smooth = smooth;
+    return r;
+}
+
+int lrcn_loss_grad_smooth(lrcn_ctx *c, const float *const p[9], const float *feats, const int32_t *tokens, const int32_t *lens,
+                          const float *row_w, int T, int B, int64_t norm_tokens, const lrcn_dropout *drop, const lrcn_sched *ss,
+                          int32_t *fed_out, float smooth, float *const grads[9], double *loss_host) {
+    if (!grads) return LRCN_EINVAL;
+    LossCall q{};
+    if (int r = smooth_call(c, q, lens, row_w, norm_tokens, ss, smooth)) return r;
+    q.p = p; q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.fed_out = fed_out; q.grads = grads;
+    const int r = loss_entry(c, q, loss_host);
+    if (!r) c->last_smooth = smooth;
+    return r;
+}
+
+int lrcn_train_step_smooth(lrcn_ctx *c, float *const p[9], float *const g[9], float *const m[9], float *const v[9], const float *feats,
+                           const int32_t *tokens, const int32_t *lens, const float *row_w, int T, int B, int64_t norm_tokens,
+                           const lrcn_dropout *drop, const lrcn_sched *ss, float smooth, int step, float lr, float b1, float b2, float eps,
+                           float max_norm, double *loss_host) {
+    LossCall q{};
+    if (int r = smooth_call(c, q, lens, row_w, norm_tokens, ss, smooth)) return r;
+    q.feats = feats; q.tokens = tokens; q.T = T; q.B = B; q.drop = drop; q.grads = g;
+    const int r = train_step_impl(c, q, p, m, v, step, lr, b1, b2, eps, max_norm, loss_host);
+    if (!r) c->last_smooth = smooth;
+    return r;
+}
+
+int lrcn_smooth_stats(lrcn_ctx *c, double *nll, double *smoothed) {
+    DeviceGuard dg(c);
+    if (!c) return LRCN_EINVAL;
+    if (c->last_smooth < 0.0f) FAIL(c, LRCN_ESTATE, "lrcn_smooth_stats: the context has made no *_smooth call");
+    double s = 0.0, n = 0.0;
+    HIPCHK(c, hipMemcpyAsync(&s, c->logp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (c->last_smooth > 0.0f) HIPCHK(c, hipMemcpyAsync(&n, c->nll_acc, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const double norm = c->last_tokens > 0 ? (double)c->last_tokens : (double)c->last_norm * (double)c->last_S;
+    if (smoothed) *smoothed = -s / norm;
+    if (nll) *nll = -(c->last_smooth > 0.0f ? n : s) / norm;
+    return LRCN_OK;
+}
+
+int lrcn_xent_logits(lrcn_ctx *c, const float *logits, int64_t ld, const int32_t *tgt, const float *row_w, int M, int B, int V, float scale,
+                     float smooth, int out_dtype, void *dlog, int64_t ld_d, double *terms, double *ll_terms) {
+    DeviceGuard dg(c);
+    if (!c) return LRCN_EINVAL;
+    if (!logits || !tgt) FAIL(c, LRCN_EINVAL, "null argument");
+    if (M < 1 || B < 1 || V < 1 || ld < V) FAIL(c, LRCN_EINVAL, "M=%d, B=%d, V=%d must be >= 1 and ld=%lld >= V", M, B, V, (long long)ld);
+    if (dlog && ld_d < V) FAIL(c, LRCN_EINVAL, "ld_d=%lld must be >= V=%d", (long long)ld_d, V);
+    if (out_dtype != LRCN_F32 && out_dtype != LRCN_BF16) FAIL(c, LRCN_EINVAL, "out_dtype=%d is neither LRCN_F32 nor LRCN_BF16", out_dtype);
+    if (!std::isfinite(scale)) FAIL(c, LRCN_EINVAL, "scale=%g is not finite", (double)scale);
+    if (!(smooth >= 0.0f && smooth <= 1.0f)) FAIL(c, LRCN_EINVAL, "smooth=%g outside [0,1]", (double)smooth);
+    hipStream_t st = c->stream;
+    // scratch: M doubles (the row terms of the unsmoothed kernels when the caller wants none) and the M checked targets
+    const size_t need = (sizeof(double) + sizeof(int32_t)) * (size_t)M;
+    if (need > c->xl_bytes) {
+        HIPCHK(c, hipStreamSynchronize(st));  // an earlier call's launches may still read the old one
+        if (c->xl_arena) (void)hipFree(c->xl_arena);
+        c->xl_arena = nullptr;
+        c->xl_bytes = 0;
+        if (hipMalloc(&c->xl_arena, 2 * need) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipMalloc(%zu) for lrcn_xent_logits failed", 2 * need);
+        c->xl_bytes = 2 * need;
+    }
+    double *rows_scratch = reinterpret_cast<double *>(c->xl_arena);
+    int32_t *tg = reinterpret_cast<int32_t *>(rows_scratch + M);
+    k_xent_targets(st, tgt, M, V, tg);
+    const int dt = out_dtype == LRCN_BF16 ? GEMM_T_BF16 : GEMM_T_F32;
+    if (smooth > 0.0f) {
+        XentSmooth sm{};
+        sm.eps = smooth; sm.row_w = row_w; sm.B = B; sm.ll_rows = ll_terms;
+        k_softmax_xent_smooth(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, terms, sm);
+    } else {
+        double *rows = terms ? terms : ll_terms ? ll_terms : rows_scratch;
+        if (row_w) k_softmax_xent_weighted(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, rows, row_w, B);
+        else k_softmax_xent_masked(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, rows);
+        if (terms && ll_terms) HIPCHK(c, hipMemcpyAsync(ll_terms, terms, sizeof(double) * (size_t)M, hipMemcpyDeviceToDevice, st));
+    }
+    KCHK(c, "xent_logits");
     return LRCN_OK;
 }
 

@@ -145,9 +145,10 @@ class HipOps:
     def set_vgg_wg_cap(self, cap):
         self.ctx._call("lrcn_vgg_set_wg_cap", int(cap))
 
-    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None, row_weights=None, sched=None):
+    def lossgradient(self, param, feats, tokens, norm_B, pdrop, seed, grads, lens=None, norm_tokens=None, row_weights=None, sched=None,
+                     label_smoothing=0.0):
         L.lossgradient(self.ctx, param, feats, tokens, norm_B=norm_B, pdrop=pdrop, seed=seed, grads=grads,
-                       want_loss=False, lens=lens, norm_tokens=norm_tokens, row_weights=row_weights, sched=sched)
+                       want_loss=False, lens=lens, norm_tokens=norm_tokens, row_weights=row_weights, sched=sched, label_smoothing=label_smoothing)
 
     def sched_stats(self):
         """(eligible, drawn) of the most recent lossgradient with sched (waits for the context's stream)."""
@@ -650,7 +651,7 @@ class DataParallelTrainer:
         return self.ops.upload(img)
 
     def step(self, img_u8, tokens, next_img_u8=None, feats=None, prefetch_img_u8=None, lens=None, norm_tokens=None, row_weights=None,
-             sched=None):
+             sched=None, label_smoothing=0.0):
         """One synchronous-SGD step on this rank's shard.  img_u8: this rank's uint8 crops (or feats given);
         next_img_u8: the crops of the NEXT step(s), whose VGG forward runs beside this step's LSTM work and all-reduce.
         img_u8 is IGNORED when an earlier step() already produced this batch's features through its next_img_u8.
@@ -676,10 +677,21 @@ class DataParallelTrainer:
 
         sched ((eps, temperature, seed) or lrcn.Sched): scheduled sampling (include/lrcn_sched.h).  Its row0 is set here to this rank's
         first row in the global batch (shard_rows), so coins and noise are those of the single-device step on the global batch.  Without
-        lens the rows are equal-length captions: lens[b] = T and norm_tokens = B_global * (T + 1).  Not with the "abi" backend."""
+        lens the rows are equal-length captions: lens[b] = T and norm_tokens = B_global * (T + 1).  Not with the "abi" backend.
+
+        label_smoothing (0 <= eps <= 1; include/lrcn_smooth.h): the loss kernels score every active row against (1 - eps) onehot + eps / V.
+        Only d(logits) changes, so every mode of the "torch" backend exchanges and updates as before; without lens the rows are equal-length
+        captions as with sched.  The loss the step leaves behind (loss_value) is the smoothed one.  Not with the "abi" backend."""
         if row_weights is not None and lens is None and sched is None:
             raise L.LrcnError("row_weights needs lens")
         rows = int(tokens.shape[1])
+        label_smoothing = L._smooth(label_smoothing)
+        if label_smoothing > 0:
+            if self.backend == "abi" and self._multi:
+                raise L.LrcnError("the \"abi\" data-parallel backend (lrcn_train_step_dp) has no label smoothing; use backend=\"torch\"")
+            if lens is None:
+                lens = np.full(rows, int(tokens.shape[0]), np.int32)
+                norm_tokens = self.B_global * (int(tokens.shape[0]) + 1)
         if sched is not None:
             if self.backend == "abi" and self._multi:
                 raise L.LrcnError("the \"abi\" data-parallel backend (lrcn_train_step_dp) has no scheduled sampling; use backend=\"torch\"")
@@ -735,6 +747,8 @@ class DataParallelTrainer:
             kw = {} if row_weights is None else {"row_weights": row_weights}   # (an ops stand-in without the keyword keeps working)
             if sched is not None:
                 kw["sched"] = sched
+            if label_smoothing > 0:
+                kw["label_smoothing"] = label_smoothing
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads, lens=lens, norm_tokens=int(norm_tokens), **kw)
         else:
             self.ops.lossgradient(self.param, feats, tokens, self.B_global, self.pdrop, seed, self.grads)

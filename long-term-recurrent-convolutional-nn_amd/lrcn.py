@@ -219,6 +219,48 @@ def sched_stats(ctx):
     return int(e.value), int(d.value)
 
 
+def smooth_stats(ctx):
+    """(nll, smoothed) of the most recent call with label_smoothing > 0 (or a direct lrcn_*_smooth call), while no other loss call has
+    followed it: the plain negative log-likelihood of the same rows beside the smoothed loss.  Waits for the context's stream."""
+    n, s = C.c_double(), C.c_double()
+    ctx._call("lrcn_smooth_stats", C.byref(n), C.byref(s))
+    return n.value, s.value
+
+
+def xent_logits(ctx, logits, targets, row_weights=None, B=None, scale=1.0, label_smoothing=0.0, out_dtype=None, want_dlog=True, ld_d=None):
+    """The cross-entropy stage alone on the caller's own logits (lrcn_xent_logits): logits a float32 device tensor (M, V), rows stride(0)
+    apart; targets int (M) (negative, or >= V: an inactive row); row m belongs to caption m % B (default B = M) and carries
+    row_weights[m % B].  -> (dlog, terms, ll_terms): d(logits) (M, V) in out_dtype (torch.float32, the default, or torch.bfloat16; rows
+    ld_d apart, default V rounded up to a multiple of 8; None without want_dlog) and the rows' smoothed and plain terms as float64 device
+    tensors (M).  Nothing waits for the device."""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2 and logits.stride(1) == 1):
+        raise LrcnError("logits must be a float32 device tensor (M, V) with contiguous rows")
+    M, V = logits.shape
+    B = M if B is None else int(B)
+    tgt = torch.as_tensor(targets).to(device=logits.device, dtype=torch.int32).contiguous()
+    if tgt.numel() != M:
+        raise LrcnError("targets has %d entries, logits has %d rows" % (tgt.numel(), M))
+    w = None
+    if row_weights is not None:
+        w = torch.as_tensor(row_weights).to(device=logits.device, dtype=torch.float32).contiguous()
+        if w.numel() != B:
+            raise LrcnError("row_weights has %d entries, B = %d" % (w.numel(), B))
+    out_dtype = out_dtype or torch.float32
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise LrcnError("out_dtype is torch.float32 or torch.bfloat16")
+    dlog = None
+    if want_dlog:
+        ld_d = (V + 7) // 8 * 8 if ld_d is None else int(ld_d)
+        dlog = torch.empty((M, ld_d), device=logits.device, dtype=out_dtype)
+    terms = torch.empty(M, device=logits.device, dtype=torch.float64)
+    ll = torch.empty(M, device=logits.device, dtype=torch.float64)
+    ctx._call("lrcn_xent_logits", C.c_void_p(logits.data_ptr()), logits.stride(0), C.c_void_p(tgt.data_ptr()),
+              C.c_void_p(w.data_ptr()) if w is not None else None, M, B, V, C.c_float(scale), C.c_float(_smooth(label_smoothing)),
+              LRCN_BF16 if out_dtype == torch.bfloat16 else LRCN_F32, C.c_void_p(dlog.data_ptr()) if dlog is not None else None,
+              ld_d if dlog is not None else 0, C.c_void_p(terms.data_ptr()), C.c_void_p(ll.data_ptr()))
+    return (dlog[:, :V] if dlog is not None else None), terms, ll
+
+
 # ------------------------------------------------------------------------------------------------ model
 def initweights(ctx, seed=42):
     """initweights(atype, hidden, vocab, embed) (lrcn.jl:489-510) -> list of 9 column-major tensors."""
@@ -270,39 +312,58 @@ def lrcn(ctx, w, s, x_cnn, x_lstm, mask1=None, mask2=None):
     return logits
 
 
+def _smooth(label_smoothing):
+    """label_smoothing -> float in [0, 1], checked as the library checks it (a NaN fails every comparison)."""
+    eps = float(label_smoothing or 0.0)
+    if not 0.0 <= eps <= 1.0:
+        raise LrcnError("label_smoothing=%r outside [0, 1]" % (label_smoothing,))
+    return eps
+
+
 def _caption_call(ctx, param, feats, tokens, norm_B, drop, lens, norm_tokens, row_weights, sched, want_loss=True, grads=None, optim=None,
-                  gclip=0.0, return_fed=False, return_logits=False):
+                  gclip=0.0, return_fed=False, return_logits=False, label_smoothing=0.0):
     """The one path of loss / lossgradient / train_step (optim given) to the library -> (loss or None, fed, logits).  The entry point is named
-    by the first of sched, row_weights, lens that is given: lrcn_{loss, loss_grad, train_step}{_sched, _w, _var, ""}, and a step with neither
-    sched nor row_weights takes max_norm (gclip) only as lrcn_train_step[_var]_clip.  Every check runs before optim.t moves."""
+    by the first of label_smoothing > 0, sched, row_weights, lens that is given: lrcn_{loss, loss_grad, train_step}{_smooth, _sched, _w, _var,
+    ""}, and a step with none of the first three takes max_norm (gclip) only as lrcn_train_step[_var]_clip.  The _smooth entries take
+    row_weights and sched as options; without lens their rows are equal-length captions: lens[b] = T, norm_tokens = (norm_B or B) (T + 1).
+    Every check runs before optim.t moves."""
     tok = _tokens(tokens, feats.device)
     T, B = tok.shape
     ss = _sched(sched, B) if sched is not None else None
+    eps = _smooth(label_smoothing)
     if ss is None and (return_fed or return_logits):
         raise LrcnError("return_fed / return_logits need sched")
-    if ss is not None:
+    if eps > 0 and return_logits:
+        raise LrcnError("return_logits is not available with label_smoothing (include/lrcn_smooth.h has no logits_out)")
+    if eps > 0 and lens is None and norm_tokens is None:
+        norm_tokens = (norm_B or B) * (T + 1)   # the equal-length normaliser
+    if ss is not None or eps > 0:
         lens = _sched_lens(lens, T, B)
     wa = _row_weights(row_weights, lens, B) if row_weights is not None else None
     la = _lens(lens, T, B, norm_tokens) if lens is not None else None
     d, keep = _dropout(*drop)
-    form = "_sched" if ss is not None else "_w" if wa is not None else "_var" if la is not None else ""
+    form = "_smooth" if eps > 0 else "_sched" if ss is not None else "_w" if wa is not None else "_var" if la is not None else ""
     name = ("lrcn_train_step" if optim is not None else "lrcn_loss_grad" if grads is not None else "lrcn_loss") + form
     args = [_p9(param)] + ([_p9(grads), _p9(optim.m), _p9(optim.v)] if optim is not None else []) + [_ptr(feats), C.c_void_p(tok.data_ptr())]
     if la is not None:
         args.append(la[1])
-    if form in ("_sched", "_w"):
+    if form in ("_smooth", "_sched", "_w"):
         args.append(wa[1] if wa else None)
-    args += [T, B, la[2] if la is not None else norm_B or B, C.byref(d) if d else None] + ([C.byref(ss)] if ss is not None else [])
+    args += [T, B, la[2] if la is not None else norm_B or B, C.byref(d) if d else None]
+    if ss is not None or form == "_smooth":
+        args.append(C.byref(ss) if ss is not None else None)
     fed = torch.empty((T + 1, B), device=feats.device, dtype=torch.int32) if return_fed else None
     logits = torch.empty((T + 1, ctx.V, B), device=feats.device, dtype=torch.float32) if return_logits else None  # blocks of B x V column-major
     if optim is not None:
         optim.t += 1
-        args += [optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps]
-        if form in ("_sched", "_w"):   # these two always take max_norm, the others only as their _clip namesakes
+        args += ([C.c_float(eps)] if form == "_smooth" else []) + [optim.t, optim.lr, optim.beta1, optim.beta2, optim.eps]
+        if form in ("_smooth", "_sched", "_w"):   # these three always take max_norm, the others only as their _clip namesakes
             args.append(gclip)
         elif gclip > 0:
             name += "_clip"
             args.append(gclip)
+    elif form == "_smooth":
+        args += [C.c_void_p(fed.data_ptr()) if return_fed else None, C.c_float(eps)] + ([_p9(grads)] if grads is not None else [])
     else:
         args += [_p9(grads)] if grads is not None else []
         if ss is not None:
@@ -314,25 +375,30 @@ def _caption_call(ctx, param, feats, tokens, norm_B, drop, lens, norm_tokens, ro
 
 
 def loss(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, lens=None, norm_tokens=None, row_weights=None,
-         sched=None):
+         sched=None, label_smoothing=0.0):
     """loss(param,state,input,sequence,range; pdrop) (lrcn.jl:553-581).  feats: B x 4096 (column-major);
     tokens: [T][B] = sequence[range]; norm_B = the reference's global `batchsize` (default B).
     lens (int [B], 0 <= lens[b] <= T): the padded batch of include/lrcn_varlen.h -- row b counts lens[b] + 1 terms, the sum is divided by
     norm_tokens (default: this batch's sum(lens + 1); data parallelism: the global batch's) and norm_B is not used.
     row_weights (float [B], with lens): row b's terms are multiplied by row_weights[b], of either sign or 0 (include/lrcn_weighted.h).
-    sched (Sched, or (eps, temperature, seed[, row0])): scheduled sampling (include/lrcn_sched.h); lens then defaults to [T] * B."""
-    return _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, mask1, mask2), lens, norm_tokens, row_weights, sched)[0]
+    sched (Sched, or (eps, temperature, seed[, row0])): scheduled sampling (include/lrcn_sched.h); lens then defaults to [T] * B.
+    label_smoothing (0 <= eps <= 1; include/lrcn_smooth.h): every active row is scored against (1 - eps) onehot + eps / V, inside the loss
+    kernels, and the value returned is the smoothed loss (smooth_stats() has the plain one).  It combines with lens, row_weights and sched;
+    without lens the normaliser stays the equal-length one, norm_B (T + 1).  0 is the call without the keyword."""
+    return _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, mask1, mask2), lens, norm_tokens, row_weights, sched,
+                         label_smoothing=label_smoothing)[0]
 
 
 def lossgradient(ctx, param, feats, tokens, norm_B=None, pdrop=0.0, seed=0, mask1=None, mask2=None, grads=None,
-                 want_loss=True, lens=None, norm_tokens=None, row_weights=None, sched=None, return_fed=False, return_logits=False):
+                 want_loss=True, lens=None, norm_tokens=None, row_weights=None, sched=None, return_fed=False, return_logits=False,
+                 label_smoothing=0.0):
     """lossgradient = grad(loss) (lrcn.jl:583) -> (grads, loss).  `grads` may be a preallocated 9-list.  lens / norm_tokens / row_weights /
-    sched: as loss().  With sched, return_fed / return_logits append the words that were fed ((T+1, B) int32 numpy) and the logits the
+    sched / label_smoothing: as loss().  With sched, return_fed / return_logits append the words that were fed ((T+1, B) int32 numpy) and the logits the
     draws were made from ((T+1, B, V) float32 numpy) to the result."""
     if grads is None:
         grads = [jl_empty(*t.shape) for t in param]
     val, fed, logits = _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, mask1, mask2), lens, norm_tokens, row_weights, sched,
-                                     want_loss, grads, return_fed=return_fed, return_logits=return_logits)
+                                     want_loss, grads, return_fed=return_fed, return_logits=return_logits, label_smoothing=label_smoothing)
     res = (grads, val)
     if return_fed:
         res += (fed.cpu().numpy(),)
@@ -436,11 +502,12 @@ def refresh_shadows_group(ctx, param, group, stream=None):
 
 
 def train_step(ctx, param, optim, grads, feats, tokens, norm_B=None, pdrop=0.4, seed=0, want_loss=False, lens=None, norm_tokens=None,
-               gclip=0.0, row_weights=None, sched=None):
-    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights / sched: as loss().
+               gclip=0.0, row_weights=None, sched=None, label_smoothing=0.0):
+    """Body of train1's batch loop (lrcn.jl:369-394): lossgradient + update!, one C call.  lens / norm_tokens / row_weights / sched /
+    label_smoothing: as loss().
     gclip > 0: the global gradient norm is clipped to it on the device (include/lrcn_clip.h; clip_stats() has the counters)."""
     return _caption_call(ctx, param, feats, tokens, norm_B, (pdrop, seed, None, None), lens, norm_tokens, row_weights, sched, want_loss, grads,
-                         optim, float(gclip or 0.0))[0]
+                         optim, float(gclip or 0.0), label_smoothing=label_smoothing)[0]
 
 
 def comm_unique_id():

@@ -123,7 +123,7 @@ def beam_cider(ctx, param, cider, image_ids, feats_of, index_to_word, beam_width
 
 def train_epoch(trainer, image_ids, feats_of, reward, images_per_step, S, nword, seed, epoch, **kw):
     """One pass over `image_ids` (this rank's, each once) in a seeded order, images_per_step images per scst_step; a short last window
-    is dropped (every rank must take the same number of steps).  kw: scst_step's temperature / top_k / top_p / baseline.
+    is dropped (every rank must take the same number of steps).  kw: scst_step's temperature / top_k / top_p / baseline / label_smoothing.
     -> (mean sample reward, mean greedy reward or None, steps taken, images seen)."""
     ids = list(image_ids)
     order = np.random.default_rng([int(seed) & 0x7FFFFFFF, int(epoch)]).permutation(len(ids))
@@ -139,7 +139,7 @@ def train_epoch(trainer, image_ids, feats_of, reward, images_per_step, S, nword,
     return (float(np.mean(rs)) if rs else 0.0), (float(np.mean(rg)) if rg else None), steps, seen
 
 
-def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_k=0, top_p=1.0, seed=0, baseline="greedy"):
+def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_k=0, top_p=1.0, seed=0, baseline="greedy", label_smoothing=0.0):
     """One self-critical step of dp.DataParallelTrainer `trainer` on N images.  feats: N x 4096 (column-major device tensor, as every call
     takes them); image_ids [N]; reward(image_id, word ids without bos / eos) -> float, on the host.
       1. lrcn.sample_batch draws S samples per image (temperature / top_k / top_p / seed as there);
@@ -147,6 +147,7 @@ def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_
          "mean": the mean reward of the image's other samples, no second decode;
       3. the rewards, advantages() and build_batch();
       4. one trainer.step on the N S rows -- image i's feature row S times -- with lens, row_weights and norm_tokens set.
+    label_smoothing: passed to that step (include/lrcn_smooth.h).
     When every advantage is exactly 0 no step is taken and Adam's step count does not move.  N S must fit the context's max_B.  Under data
     parallelism each rank calls this on its own images (the same N and S everywhere); norm_tokens and the all-zero test are summed over the
     ranks before the step.
@@ -181,6 +182,7 @@ def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_
     if nonzero_all == 0:
         return out
     rows = feats.repeat_interleave(S, dim=0)      # row r = i S + s reads image i
-    trainer.step(None, tokens, feats=L.to_jl(rows), lens=lens, norm_tokens=norm_tokens, row_weights=weights)
+    kw = {"label_smoothing": label_smoothing} if label_smoothing else {}   # (a trainer stand-in without the keyword keeps working)
+    trainer.step(None, tokens, feats=L.to_jl(rows), lens=lens, norm_tokens=norm_tokens, row_weights=weights, **kw)
     out["loss"], out["stepped"] = trainer.loss_value(), True
     return out

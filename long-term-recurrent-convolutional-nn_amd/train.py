@@ -49,14 +49,16 @@ def batches_per_forward(rows, chunk_images=256):
     return max(1, int(chunk_images) // int(rows)) if rows <= 64 else 1
 
 
-def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1, sched=None, sched_counts=None):
+def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1, sched=None, sched_counts=None, label_smoothing=0.0):
     """One epoch (lrcn.jl:350-396).  feats_of(ids) -> this rank's feature rows on the device, or crops_of(ids) -> uint8 crops
     [len(ids)][224][224][3] (device, or pinned host): then the VGG forward of the NEXT `lookahead` batches (one forward for all of them)
     runs beside the LSTM steps of the current ones.  Returns the number of captions this rank trained on.
     sched (eps, temperature, epoch seed): scheduled sampling (include/lrcn_sched.h) on precomputed features, step k with the key
-    sched.step_seed(epoch seed, k); sched_counts (a list [eligible, drawn]) then receives this rank's counts, read after every step."""
+    sched.step_seed(epoch seed, k); sched_counts (a list [eligible, drawn]) then receives this rank's counts, read after every step.
+    label_smoothing > 0: every step's loss kernels smooth their targets (include/lrcn_smooth.h)."""
     W, r = trainer.world, trainer.rank
     n = 0
+    sm = {"label_smoothing": label_smoothing} if label_smoothing else {}   # (a trainer stand-in without the keyword keeps working)
     if sched is not None and crops_of is not None:
         raise L.LrcnError("scheduled sampling trains on precomputed features (feats_of)")
     shards = [shard_block(blocks[k], W, r) for k in order]
@@ -65,7 +67,7 @@ def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1, sc
         ids, toks = shard[0], shard[1]
         if sched is not None:
             kw = {"lens": shard[2], "norm_tokens": shard[3]} if len(shard) == 4 else {}
-            trainer.step(None, toks, feats=feats_of(ids), sched=(sched[0], sched[1], S.step_seed(sched[2], pos)), **kw)
+            trainer.step(None, toks, feats=feats_of(ids), sched=(sched[0], sched[1], S.step_seed(sched[2], pos)), **kw, **sm)
             if sched_counts is not None:
                 e, d = trainer.ops.sched_stats()
                 sched_counts[0] += e
@@ -73,16 +75,16 @@ def train1(trainer, blocks, order, feats_of=None, crops_of=None, lookahead=1, sc
         elif len(shard) == 4:   # a padded batch: precomputed features only (the crops' pipeline counts on one row count per step)
             if crops_of is not None:
                 raise L.LrcnError("variable-length batches train on precomputed features (feats_of)")
-            trainer.step(None, toks, feats=feats_of(ids), lens=shard[2], norm_tokens=shard[3])
+            trainer.step(None, toks, feats=feats_of(ids), lens=shard[2], norm_tokens=shard[3], **sm)
         elif crops_of is None:
-            trainer.step(None, toks, feats=feats_of(ids))
+            trainer.step(None, toks, feats=feats_of(ids), **sm)
         else:
             nxt_pos = max(nxt_pos, pos + 1)
             if nxt is None and nxt_pos < len(shards):
                 nxt = crops_of(sum((s[0] for s in shards[nxt_pos:nxt_pos + lookahead]), []))
             # the first batch's own crops are only read when no earlier step produced its features (the very first step of the epoch)
             cur = crops_of(ids) if (pos == 0 or not trainer._feat_q) else None
-            if trainer.step(cur, toks, next_img_u8=nxt):
+            if trainer.step(cur, toks, next_img_u8=nxt, **sm):
                 nxt_pos += lookahead
                 nxt = None
         n += len(ids)
@@ -113,13 +115,14 @@ def average_loss(trainer, blocks, feats_of):
 
 
 def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feats_of=None, save=None, log=print, sync=None, lookahead=1,
-          sched_of=None):
+          sched_of=None, label_smoothing=0.0):
     """train! (lrcn.jl:223-246).  splits: [(blocks of the training split), (blocks of the dev split)?], blocks = [(ids, tokens)] or the
     padded [(ids, tokens, lens)] of captions.minibatch_varlen.
     feats_of / crops_of: the training inputs (one of them); eval_feats_of[i](ids): features of split i for average_loss (default:
     feats_of).  save(epoch): called on every rank after each epoch (rank 0 writes; a sharded update gathers its moments first).
     sched_of(e) (e = epoch - 1, 0-based as in sched.epsilon): None, or (eps, temperature, seed) of that epoch's scheduled sampling
     (sched.sched_of); one more line per epoch then gives eps and the realised drawn / eligible over all ranks.
+    label_smoothing: of every training step (train1); the per-epoch losses are average_loss's plain NLL either way.
     Returns the list of per-epoch loss tuples."""
     import time
     history = []
@@ -129,7 +132,7 @@ def train(trainer, splits, epochs, seed, feats_of=None, crops_of=None, eval_feat
         ss = sched_of(epoch - 1) if sched_of is not None else None
         counts = [0, 0]
         n = train1(trainer, splits[0], epoch_order(len(splits[0]), seed, epoch), feats_of=feats_of, crops_of=crops_of, lookahead=lookahead,
-                   sched=ss, sched_counts=counts)
+                   sched=ss, sched_counts=counts, label_smoothing=label_smoothing)
         if sched_of is not None and trainer.world > 1:
             t = torch.tensor(counts, dtype=torch.int64, device=trainer.param[0].device if dist.get_backend(trainer.group) == "nccl" else "cpu")
             dist.all_reduce(t, group=trainer.group)

@@ -16,6 +16,8 @@ batch is split by rows over the ranks (same T everywhere, the global batch as no
 `--varlen` batches captions of mixed lengths (padded, masked loss) instead of the reference's equal-length batches: nothing is dropped.
 `--ss_start E` turns scheduled sampling on from epoch E (counted from 0): an input word is, with a probability that grows by `--ss_step`
 every `--ss_every` epochs up to `--ss_max`, drawn on the device from the model's own logits of the step before (include/lrcn_sched.h).
+`--label_smoothing E` scores every training step against (1 - E) onehot + E / V inside the loss kernels (include/lrcn_smooth.h); it combines
+with `--varlen`, `--ss_start`, `--scst` and `--gclip`, and the per-epoch loss line stays the plain NLL of average_loss.
 `--gpus N` starts the ranks itself from a parent that never touches the GPU; the torchrun form works too.  `--cnn --train --imagedir`
 trains end to end from images: the VGG forward of the next batch runs beside the LSTM step of the current one.
 
@@ -102,6 +104,9 @@ def build_parser():
     p.add_argument("--ss_step", type=float, default=0.05, help="--ss_start: eps starts at this value and grows by it")
     p.add_argument("--ss_max", type=float, default=0.25, help="--ss_start: the largest eps")
     p.add_argument("--ss_temperature", type=float, default=1.0, help="--ss_start: temperature of the draw (0 = the argmax)")
+    p.add_argument("--label_smoothing", type=float, default=0.0,
+                   help="--train: label smoothing eps in [0, 1] of every training step's loss (include/lrcn_smooth.h; 0 = off); the per-epoch "
+                        "(:epoch, n, :loss, ...) line stays the plain NLL")
     p.add_argument("--scst", action="store_true",
                    help="--train: self-critical training on the model's own samples with a CIDEr-D reward (lrcn_amd/scst.py); needs --loadfile")
     p.add_argument("--scst_samples", type=int, default=5, help="--scst: samples per image; a step takes batchsize // scst_samples images")
@@ -140,6 +145,10 @@ def main(argv=None):
         raise SystemExit("--ss_start is a mode of the cross-entropy TRAINING job (--train without --scst)")
     if o.scst and not o.train:
         raise SystemExit("--scst is a mode of the TRAINING job (--train)")
+    if not 0.0 <= o.label_smoothing <= 1.0:
+        raise SystemExit("--label_smoothing must be in [0, 1]")
+    if o.label_smoothing > 0 and not o.train:
+        raise SystemExit("--label_smoothing is an option of the TRAINING job (--train)")
     if o.scst and not o.loadfile:
         raise SystemExit("--scst starts from a trained model: give --loadfile (train with cross-entropy first)")
     world_env = os.environ.get("WORLD_SIZE")
@@ -416,7 +425,7 @@ def main(argv=None):
             t0 = time.time()
             rs, rg, steps, seen = scst.train_epoch(trainer, mine, lambda part: feature_rows(tables[0], part), reward, per_step, S, o.scst_nword,
                                                    seed + rank, epoch, temperature=o.temperature, top_k=o.topk, top_p=o.topp,
-                                                   baseline=o.scst_baseline)
+                                                   baseline=o.scst_baseline, label_smoothing=o.label_smoothing)
             ctx.sync()
             dt_s = time.time() - t0
             if o.savefile:
@@ -506,6 +515,10 @@ def main(argv=None):
                 raise SystemExit("--ss_start needs --dp_backend torch")
             from lrcn_amd import sched as ss
             kw["sched_of"] = ss.sched_of(o.ss_start, o.ss_every, o.ss_step, o.ss_max, temperature=o.ss_temperature, seed=seed)
+        if o.label_smoothing > 0:
+            if o.dp_backend == "abi" and world > 1:
+                raise SystemExit("--label_smoothing needs --dp_backend torch")
+            kw["label_smoothing"] = o.label_smoothing
         trn.train(trainer, splits, o.epochs, seed, save=save, log=say, sync=ctx.sync, lookahead=lookahead, **kw)
         trainer.close()
         if world > 1:
