@@ -273,7 +273,7 @@ struct LossCall {
     const int32_t *lens = nullptr;        // host [B]: the variable-length form (include/lrcn_varlen.h)
     const float *row_w = nullptr;         // host [B], with lens: a weight per caption (include/lrcn_weighted.h)
     const lrcn_sched *ss = nullptr;       // with lens: scheduled sampling (include/lrcn_sched.h; eps > 0: the stepwise forward)
-    float smooth = 0.0f;                  // > 0, with lens: label smoothing (include/lrcn_smooth.h) -- k_softmax_xent_smooth is the loss kernel
+    float smooth = 0.0f;                  // > 0, with lens: label smoothing (include/lrcn_smooth.h) -- XentCall::eps, the SMOOTH form of k_softmax_xent
     int32_t *fed_out = nullptr;           // device [T+1][B], with ss: the words that were fed
     float *logits_out = nullptr;          // device, (T+1) blocks of B x V column-major
     enum Form { PLAIN, VAR, WEIGHTED, SCHED } form = PLAIN;   // which of lens / row_w / ss the entry point requires (train.hip loss_entry checks it)

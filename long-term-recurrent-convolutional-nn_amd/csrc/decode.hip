@@ -518,7 +518,10 @@ int score_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, 
                 if (!k_score_pick_merge(st, c->smax_part, smax_nrec(c), Rt, acc)) FAIL(c, LRCN_EINVAL, "score merge: %d records per row", smax_nrec(c));
             } else {
                 GEMM(c, dt, h2n, ldA2, c->Wod, c->ldH2, c->st_logits, c->ldV, Rt, V, H2, p[8], true);   // lrcn.jl:550
-                k_softmax_xent(st, dt, c->st_logits, c->ldV, tgt_row, Rt, V, 1.0f, terms + maxB, nullptr, 0, terms);
+                XentCall x{};  // PLAIN: the rows' terms, then their sum behind them
+                x.logits = c->st_logits; x.ld_l = c->ldV; x.tgt = tgt_row; x.M = Rt; x.V = V; x.scale = 1.0f;
+                x.sum = terms + maxB; x.rows = terms;
+                k_softmax_xent(st, dt, x);
                 k_score_acc(st, terms, Rt, acc);
             }
             std::swap(A2c, A2n);

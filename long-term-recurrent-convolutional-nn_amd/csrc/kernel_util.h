@@ -1,4 +1,4 @@
-// kernel_util.h -- internal to kernels.hip, train_kernels.hip, decode_kernels.hip, image_kernels.hip and activity.hip, what they share: the element-type
+// kernel_util.h -- internal to kernels.hip, xent.hip, train_kernels.hip, decode_kernels.hip, image_kernels.hip and activity.hip, what they share: the element-type
 // dispatch, the dropout counter hash, wave / block reductions, the 4-element store and the launchers' grid helpers.
 #pragma once
 #include "kernels.h"

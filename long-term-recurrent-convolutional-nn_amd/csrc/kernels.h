@@ -59,39 +59,6 @@ void k_lstm_bwd(hipStream_t st, int dtype, const void *acts, int64_t ld_a, const
 void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float *xcnn, int64_t ld_xc, int S, int B,
                  int nl, int nr, DropSpec d, int s0 = 0);
 
-// Row-wise log-softmax + target pick + (optional) dlogits = (softmax - onehot) * scale   (lrcn.jl:562-567 and dual).
-// logits f32 [M][ld_l]; accumulates sum of log p(target) into *logp_sum (double).  dlog (T) may be NULL.
-// logp_rows != NULL (LRCN_OPT_DETERMINISTIC): each row's term goes to logp_rows[m] and one workgroup adds them to *logp_sum in a
-// fixed order, instead of M double atomics.
-void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                    float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
-// The same with inactive rows (tgt[m] < 0, written by k_build_tokens_var): such a row adds no loss term, gets logp_rows[m] = 0 and an
-// all-zero dlog row, and its logits are not read.  The variable-length entry points of include/lrcn_varlen.h.
-void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                           float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows = nullptr);
-// The masked form with a real weight per caption (include/lrcn_weighted.h): row m belongs to caption b = m % B, row_w device f32 [B].
-// row_w[b] == 0 makes row m inactive (logits not read); otherwise its dlog row is (softmax - onehot) * (scale * row_w[b]) and its
-// log-likelihood term row_w[b] * log p(target), in double.
-void k_softmax_xent_weighted(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                             double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w, int B);
-// Label smoothing (include/lrcn_smooth.h), a form of the masked kernels: the row's target distribution is (1 - eps) onehot(t) + eps / V, so
-//   term = w ((1 - eps) ll + eps u),  ll = (z_t - max) - log(sum exp),  u = sum_v (z_v - max) / V - log(sum exp)
-//   dlog_v = (softmax_v - (1 - eps) [v == t] - eps / V) * (scale * w)
-// with w = row_w[m % B], or 1 when row_w is NULL.  The smoothed term goes where the other forms put theirs (logp_rows[m], else a double
-// atomic into *logp_sum) and the plain w * ll likewise into ll_rows[m], else *ll_sum; a NULL destination is left out.
-struct XentSmooth {
-    float eps;           // 0 < eps <= 1 (0 is the other launchers' business)
-    const float *row_w;  // device f32 [B] or NULL
-    int B;
-    double *ll_sum;      // the accumulator of the unsmoothed terms, or NULL
-    double *ll_rows;     // [M] with logp_rows: their per-row slots, or NULL
-};
-// logp_rows with a NULL logp_sum (and ll_rows with a NULL ll_sum): the rows are written and not summed (lrcn_xent_logits).
-void k_softmax_xent_smooth(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                           double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const XentSmooth &sm);
-// out[m] = tgt[m] in [0, V) ? tgt[m] : -1 (lrcn_xent_logits: a caller's target can never index outside its logits row)
-void k_xent_targets(hipStream_t st, const int32_t *tgt, int M, int V, int32_t *out);
-
 // out[c][r + shift] = in[r][c] (0<=r<R, 0<=c<C), out[c][0..shift) = 0.  in_f32/out types: in is f32 if in_f32 else T;
 // out is always T.   (builds the K-contiguous transposed operands of the weight-gradient GEMMs)
 void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t ld_in, int R, int C, void *out,
@@ -123,12 +90,42 @@ void k_transpose_multi(hipStream_t st, int dtype, TrPlan &plan);
 void k_init_uniform(hipStream_t st, float *w, int64_t n, float scale, uint64_t seed, int tensor);
 void k_fill(hipStream_t st, float *w, int64_t n, float v);
 
+// ---- xent.hip: the loss stage (train.hip, decode.hip's unfused scoring) ----
+// Row-wise log-softmax + target pick + (optional) dlogits = (softmax - onehot) * scale   (lrcn.jl:562-567 and dual), in the form that the
+// call's members select (k_softmax_xent derives it, in this order):
+//   eps > 0   SMOOTH (include/lrcn_smooth.h), weighted exactly when row_w is non-NULL: the target distribution is (1 - eps) onehot(t) + eps / V,
+//               term = w ((1 - eps) ll + eps u),  ll = (z_t - max) - log(sum exp),  u = sum_v (z_v - max) / V - log(sum exp)
+//               dlog_v = (softmax_v - (1 - eps) [v == t] - eps / V) * (scale * w),  w = row_w[m % B], or 1 without row_w
+//             the smoothed term goes where the other forms put theirs and the plain w * ll likewise into ll_rows[m], else *ll_sum.
+//   row_w     WEIGHTED (include/lrcn_weighted.h): row m belongs to caption b = m % B.  row_w[b] == 0 makes the row inactive; otherwise its
+//             dlog row is (softmax - onehot) * (scale * row_w[b]) and its term row_w[b] * log p(target), in double.
+//   masked    MASKED (include/lrcn_varlen.h): a row with tgt[m] < 0 (written by k_build_tokens_var) is inactive -- it adds no loss term,
+//             gets rows[m] = 0 (and ll_rows[m] = 0) and an all-zero dlog row, and its logits are not read.
+//   else      PLAIN: every row active, term = z_t - (max + log(sum exp)).
+// A row's term goes to rows[m] if rows is given (LRCN_OPT_DETERMINISTIC), else as a double atomic into *sum; rows and sum both given: one
+// workgroup then adds the rows to *sum in a fixed order (ll_rows and ll_sum the same).  The smooth forms leave a NULL destination out
+// (rows with a NULL sum: written and not summed, lrcn_xent_logits); the others need one of sum and rows.
+struct XentCall {
+    const float *logits; int64_t ld_l;     // f32 [M][ld_l]
+    const int32_t *tgt;  int M, V;
+    float scale;
+    void *dlog; int64_t ld_d;              // T [M][ld_d], or NULL
+    double *sum, *rows;                    // accumulator of the terms; their per-row slots [M]
+    bool masked;                           // tgt[m] < 0 marks an inactive row
+    const float *row_w; int B;             // device f32 [B] or NULL (needs masked)
+    float eps;                             // > 0: label smoothing (needs masked)
+    double *ll_sum, *ll_rows;              // smoothing's second accumulator; NULL without eps
+};
+void k_softmax_xent(hipStream_t st, int dtype, const XentCall &x);
+// out[m] = tgt[m] in [0, V) ? tgt[m] : -1 (lrcn_xent_logits: a caller's target can never index outside its logits row)
+void k_xent_targets(hipStream_t st, const int32_t *tgt, int M, int V, int32_t *out);
+
 // ---- train_kernels.hip: the training step (train.hip, update.hip) ----
 // tok_in[s][b] = bos (s==0) | tokens[s-1][b];  tok_tgt[s][b] = tokens[s][b] (s<T) | eos.   (lrcn.jl:556,565,569,576)
 void k_build_tokens(hipStream_t st, const int32_t *tokens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt, double *zero_acc);
 // Per-row lengths (device int32 [B], 0 <= lens[b] <= T): row b's step s is active for s <= lens[b] -- tok_in / tok_tgt as above with
 // lens[b] in T's place.  An inactive step gets tok_in = eos (a valid row of the embedding gather) and tok_tgt = -1, the marker
-// k_softmax_xent_masked skips by; tokens[t][b] at t >= lens[b] is never read, so padding cannot raise the sticky flag.
+// k_softmax_xent's masked forms skip by; tokens[t][b] at t >= lens[b] is never read, so padding cannot raise the sticky flag.
 void k_build_tokens_var(hipStream_t st, const int32_t *tokens, const int32_t *lens, int T, int B, int V, int32_t *tok_in, int32_t *tok_tgt,
                         double *zero_acc);
 // dWembed(tok, e) += dXemb[m][e] * dropmask   (AutoGrad dual of the gather; Wembed is V x E column-major f32),

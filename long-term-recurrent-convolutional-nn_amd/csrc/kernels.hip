@@ -1,6 +1,7 @@
 // kernels.hip -- the HBM-bound kernels that more than one model file launches: embedding gather, LSTM cell forward / backward, [x | cnn]
-// concatenation with dropout, fused log-softmax + NLL + dlogits, layout transposes, casts, column sums, fills (one wave = 64 lanes).  What one
-// host file alone uses is beside it: train_kernels.hip (train.hip, update.hip), decode_kernels.hip (decode.hip), image_kernels.hip (the VGG side).
+// concatenation with dropout, layout transposes, casts, column sums, fills (one wave = 64 lanes).  Beside it: xent.hip (the fused log-softmax +
+// NLL + dlogits stage) and what one host file alone uses -- train_kernels.hip (train.hip, update.hip), decode_kernels.hip (decode.hip),
+// image_kernels.hip (the VGG side).
 #include "kernel_util.h"
 
 namespace {
@@ -15,20 +16,6 @@ __global__ void embed_gather_kernel(const T *wembT, int64_t ld_w, const int32_t 
     const T *src = wembT + (int64_t)tok_in[m] * ld_w;
     T *dst = xemb + (int64_t)m * ld_x;
     for (int e = threadIdx.x; e < E; e += blockDim.x) dst[e] = from_f32<T>(to_f32(src[e]) * drop_mult(d, s, b, e, B, E));
-}
-
-// LRCN_OPT_DETERMINISTIC: the loss is the sum of the per-row log p(target) taken by one workgroup in a fixed order
-__global__ __launch_bounds__(256) void sum_rows_f64_kernel(const double *rows, int M, double *out) {
-    __shared__ double sh[256];
-    double a = 0.0;
-    for (int i = threadIdx.x; i < M; i += 256) a += rows[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out += sh[0];
 }
 
 template <typename T>
@@ -86,213 +73,6 @@ __global__ void concat_x2_kernel(T *x2, int64_t ld_x2, const float *xcnn, int64_
     for (int j = threadIdx.x; j < nl + nr; j += blockDim.x) {
         const float v = (j < nl) ? to_f32(row[j]) : xcnn[(int64_t)b * ld_xc + (j - nl)];
         row[j] = from_f32<T>(v * drop_mult(d, s, b, j, B, nl + nr));
-    }
-}
-
-// A row that the length-aware token builder marked inactive (target < 0: a step past its caption's end, include/lrcn_varlen.h) has no
-// loss term: its logp_rows slot becomes exactly 0 and its dlog row all zeros (16-byte stores where the row allows), and its logits are
-// never read.  The marker is uniform over the workgroup (one row per workgroup), so the early return crosses no barrier.
-template <typename T>
-__device__ __forceinline__ void softmax_xent_inactive_row(int m, int V, T *dlog, int64_t ld_d, double *logp_rows) {
-    if (threadIdx.x == 0 && logp_rows) logp_rows[m] = 0.0;
-    if (!dlog) return;
-    T *drow = dlog + (int64_t)m * ld_d;
-    constexpr int PER = 16 / (int)sizeof(T);
-    int v = 0;
-    if ((reinterpret_cast<uintptr_t>(drow) & 15) == 0) {
-        const int nv = V / PER;
-        for (int i = threadIdx.x; i < nv; i += blockDim.x) reinterpret_cast<uint4 *>(drow)[i] = make_uint4(0u, 0u, 0u, 0u);
-        v = nv * PER;
-    }
-    for (int i = v + threadIdx.x; i < V; i += blockDim.x) drow[i] = from_f32<T>(0.0f);
-}
-
-// MASKED: the variable-length entry points' form (k_softmax_xent_masked); the equal-length launcher instantiates MASKED = false only.
-// WEIGHTED (with MASKED; include/lrcn_weighted.h): row m belongs to caption b = m % B and carries the real weight row_w[b] -- a zero
-// weight makes the row inactive (as uniform over the workgroup as the target's sign), any other one scales its d(logits) row and its
-// log-likelihood term.  With every weight 1.0f the arithmetic is the masked kernel's bit for bit (scale * 1.0f == scale).
-// Its two arguments (const float *row_w, int B) are the pack RW, which is empty otherwise: the unweighted instantiations keep their
-// arguments and compile to the instructions they had without the option.
-__device__ __forceinline__ float softmax_xent_row_weight(int m, const float *row_w, int B) { return row_w[m % B]; }
-// SMOOTH (with MASKED; include/lrcn_smooth.h): the pack is one XentSmooth (kernels.h).  The target distribution is (1 - eps) onehot(t) +
-// eps / V: one more block-wide sum, of (z_v - max), rides in the pass that forms the exponentials, d(logits) loses eps / V everywhere and
-// (1 - eps) at the target, and thread 0 emits two terms -- the smoothed one where the other forms put theirs, and the plain w * ll into
-// the pack's second accumulator.  WEIGHTED says whether the pack's row_w is read (NULL: every weight 1).
-template <typename... RW> struct softmax_xent_pack { static constexpr bool smooth = false; };
-template <> struct softmax_xent_pack<XentSmooth> { static constexpr bool smooth = true; };
-__device__ __forceinline__ float softmax_xent_row_weight(int m, const XentSmooth &sm) { return sm.row_w[m % sm.B]; }
-__device__ __forceinline__ float softmax_xent_eps(const XentSmooth &sm) { return sm.eps; }
-__device__ __forceinline__ void softmax_xent_smooth_inactive(int m, const XentSmooth &sm) {
-    if (threadIdx.x == 0 && sm.ll_rows) sm.ll_rows[m] = 0.0;
-}
-// thread 0 of an active row: ll = (z_t - max) - log se, u = sd / V - log se
-__device__ __forceinline__ void softmax_xent_smooth_terms(int m, float w, float zt_minus_max, float se, float sd, int V, double *logp_sum,
-                                                          double *logp_rows, const XentSmooth &sm) {
-    const float lg = logf(se);
-    const float ll = zt_minus_max - lg, u = sd / (float)V - lg;
-    const double term = (double)w * ((1.0 - (double)sm.eps) * (double)ll + (double)sm.eps * (double)u);
-    if (logp_rows) logp_rows[m] = term;
-    else if (logp_sum) atomicAdd(logp_sum, term);
-    if (sm.ll_rows) sm.ll_rows[m] = (double)w * (double)ll;
-    else if (sm.ll_sum) atomicAdd(sm.ll_sum, (double)w * (double)ll);
-}
-
-template <typename T, bool MASKED = false, bool WEIGHTED = false, typename... RW>
-__global__ __launch_bounds__(256) void softmax_xent_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M,
-                                                           int V, float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows,
-                                                           RW... rw) {
-    __shared__ float sh[8];
-    constexpr bool SMOOTH = softmax_xent_pack<RW...>::smooth;
-    const int m = blockIdx.x;
-    [[maybe_unused]] float w = 1.0f;
-    if constexpr (WEIGHTED) w = softmax_xent_row_weight(m, rw...);
-    if constexpr (MASKED) {
-        if (tgt[m] < 0 || (WEIGHTED && w == 0.0f)) {
-            softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
-            if constexpr (SMOOTH) softmax_xent_smooth_inactive(m, rw...);
-            return;
-        }
-    }
-    if constexpr (WEIGHTED) scale *= w;  // rs = scale * row_w[b], once per row
-    const float *row = logits + (int64_t)m * ld_l;
-    float mx = -INFINITY;
-    for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, row[v]);
-    mx = block_max(mx, sh);
-    float se = 0.0f;
-    [[maybe_unused]] float sd = 0.0f;
-    if constexpr (SMOOTH) {
-        for (int v = threadIdx.x; v < V; v += blockDim.x) {
-            const float d = row[v] - mx;
-            sd += d;
-            se += expf(d);
-        }
-        sd = block_sum(sd, sh);
-    } else {
-        for (int v = threadIdx.x; v < V; v += blockDim.x) se += expf(row[v] - mx);
-    }
-    se = block_sum(se, sh);
-    const float lse = mx + logf(se);
-    const int t = tgt[m];
-    if (threadIdx.x == 0) {
-        if constexpr (SMOOTH) {
-            softmax_xent_smooth_terms(m, w, row[t] - mx, se, sd, V, logp_sum, logp_rows, rw...);
-        } else if constexpr (WEIGHTED) {
-            if (logp_rows) logp_rows[m] = (double)w * (double)(row[t] - lse);
-            else atomicAdd(logp_sum, (double)w * (double)(row[t] - lse));
-        } else {
-            if (logp_rows) logp_rows[m] = (double)(row[t] - lse);
-            else atomicAdd(logp_sum, (double)(row[t] - lse));
-        }
-    }
-    if (dlog) {
-        T *drow = dlog + (int64_t)m * ld_d;
-        if constexpr (SMOOTH) {
-            const float eps = softmax_xent_eps(rw...), on = 1.0f - eps, uv = eps / (float)V;
-            for (int v = threadIdx.x; v < V; v += blockDim.x) {
-                const float p = expf(row[v] - lse);
-                drow[v] = from_f32<T>((p - (v == t ? on : 0.0f) - uv) * scale);
-            }
-        } else {
-            for (int v = threadIdx.x; v < V; v += blockDim.x) {
-                const float p = expf(row[v] - lse);
-                drow[v] = from_f32<T>((p - (v == t ? 1.0f : 0.0f)) * scale);
-            }
-        }
-    }
-}
-
-// The same for V <= 1024 Q with the row held in registers: one expf per element (e = expf(x - max), p = e / sum) instead of
-// two, 16-byte loads; the log-likelihood term is unchanged (x[t] - (max + logf(sum))).
-template <typename T, int Q, bool MASKED = false, bool WEIGHTED = false, typename... RW>
-__global__ __launch_bounds__(256) void softmax_xent_reg_kernel(const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                                                               float scale, double *logp_sum, T *dlog, int64_t ld_d, double *logp_rows,
-                                                               RW... rw) {
-    __shared__ float sh[8];
-    constexpr bool SMOOTH = softmax_xent_pack<RW...>::smooth;
-    const int m = blockIdx.x;
-    [[maybe_unused]] float w = 1.0f;
-    if constexpr (WEIGHTED) w = softmax_xent_row_weight(m, rw...);
-    if constexpr (MASKED) {
-        if (tgt[m] < 0 || (WEIGHTED && w == 0.0f)) {
-            softmax_xent_inactive_row<T>(m, V, dlog, ld_d, logp_rows);
-            if constexpr (SMOOTH) softmax_xent_smooth_inactive(m, rw...);
-            return;
-        }
-    }
-    if constexpr (WEIGHTED) scale *= w;  // rs = scale * row_w[b], once per row
-    const float *row = logits + (int64_t)m * ld_l;  // ld_l % 4 == 0, 16-byte aligned rows
-    float x[Q][4];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const int v0 = 4 * (threadIdx.x + 256 * q);
-        float4 f = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-        if (v0 < V) f = *reinterpret_cast<const float4 *>(row + v0);
-        x[q][0] = f.x;
-        x[q][1] = v0 + 1 < V ? f.y : -INFINITY;
-        x[q][2] = v0 + 2 < V ? f.z : -INFINITY;
-        x[q][3] = v0 + 3 < V ? f.w : -INFINITY;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mx = fmaxf(mx, x[q][j]);
-    mx = block_max(mx, sh);
-    float se = 0.0f;
-    [[maybe_unused]] float sd = 0.0f;
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if constexpr (SMOOTH) {
-                const float d = x[q][j] - mx;  // -inf for the padding: kept out of the sum
-                if (4 * ((int)threadIdx.x + 256 * q) + j < V) sd += d;
-                x[q][j] = expf(d);
-            } else {
-                x[q][j] = expf(x[q][j] - mx);  // 0 for the padding
-            }
-            se += x[q][j];
-        }
-    se = block_sum(se, sh);
-    if constexpr (SMOOTH) sd = block_sum(sd, sh);
-    const int t = tgt[m];
-    if (threadIdx.x == 0) {
-        if constexpr (SMOOTH) {
-            softmax_xent_smooth_terms(m, w, row[t] - mx, se, sd, V, logp_sum, logp_rows, rw...);
-        } else if constexpr (WEIGHTED) {
-            if (logp_rows) logp_rows[m] = (double)w * (double)(row[t] - (mx + logf(se)));
-            else atomicAdd(logp_sum, (double)w * (double)(row[t] - (mx + logf(se))));
-        } else {
-            if (logp_rows) logp_rows[m] = (double)(row[t] - (mx + logf(se)));
-            else atomicAdd(logp_sum, (double)(row[t] - (mx + logf(se))));
-        }
-    }
-    if (dlog) {
-        T *drow = dlog + (int64_t)m * ld_d;
-        const float inv = 1.0f / se;
-        [[maybe_unused]] float on = 1.0f, uv = 0.0f;  // SMOOTH: what the target column and every column lose
-        if constexpr (SMOOTH) {
-            on = 1.0f - softmax_xent_eps(rw...);
-            uv = softmax_xent_eps(rw...) / (float)V;
-        }
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int v0 = 4 * (threadIdx.x + 256 * q);
-            if (v0 >= V) continue;
-            float o[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if constexpr (SMOOTH) o[j] = (x[q][j] * inv - (v0 + j == t ? on : 0.0f) - uv) * scale;
-                else o[j] = (x[q][j] * inv - (v0 + j == t ? 1.0f : 0.0f)) * scale;
-            }
-            if (v0 + 3 < V && (ld_d % 4) == 0) {
-                store4(drow + v0, o);
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (v0 + j < V) drow[v0 + j] = from_f32<T>(o[j]);
-            }
-        }
     }
 }
 
@@ -456,90 +236,6 @@ void k_concat_x2(hipStream_t st, int dtype, void *x2, int64_t ld_x2, const float
                  DropSpec d, int s0) {
     DISPATCH_T(dtype, hipLaunchKernelGGL(concat_x2_kernel<T>, dim3(S * B), dim3(256), 0, st, (T *)x2, ld_x2, xcnn, ld_xc, S,
                                          B, nl, nr, d, s0));
-}
-namespace {
-template <bool MASKED, bool WEIGHTED = false>  // WEIGHTED: the masked form with per-caption weights row_w [B] (device)
-void launch_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                         double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w = nullptr, int B = 1) {
-    const bool reg = V <= 16384 && (ld_l % 4) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(dlog) & 15) == 0;
-    if (reg) {
-        const int q = (V + 1023) / 1024;
-#define SX_LAUNCH(QQ)                                                                                                                      \
-    DISPATCH_T(dtype, {                                                                                                                    \
-        if constexpr (WEIGHTED)                                                                                                            \
-            hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, true, true, const float *, int>), dim3(M), dim3(256), 0, st, logits, ld_l,  \
-                               tgt, M, V, scale, logp_sum, (T *)dlog, ld_d, logp_rows, row_w, B);                                          \
-        else                                                                                                                               \
-            hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,        \
-                               logp_sum, (T *)dlog, ld_d, logp_rows);                                                                      \
-    })
-        if (q <= 2) SX_LAUNCH(2);
-        else if (q <= 4) SX_LAUNCH(4);
-        else if (q <= 8) SX_LAUNCH(8);
-        else if (q <= 12) SX_LAUNCH(12);
-        else SX_LAUNCH(16);
-#undef SX_LAUNCH
-    } else {
-        DISPATCH_T(dtype, {
-            if constexpr (WEIGHTED)
-                hipLaunchKernelGGL((softmax_xent_kernel<T, true, true, const float *, int>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V,
-                                   scale, logp_sum, (T *)dlog, ld_d, logp_rows, row_w, B);
-            else
-                hipLaunchKernelGGL((softmax_xent_kernel<T, MASKED>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt, M, V, scale,
-                                   logp_sum, (T *)dlog, ld_d, logp_rows);
-        });
-    }
-    if (logp_rows && logp_sum) hipLaunchKernelGGL(sum_rows_f64_kernel, dim3(1), dim3(256), 0, st, logp_rows, M, logp_sum);
-}
-// the route of launch_softmax_xent (the register form up to V = 16384 on aligned rows, else the streaming one) for the SMOOTH form
-template <bool WEIGHTED>
-void launch_softmax_xent_smooth(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                                double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const XentSmooth &sm) {
-    const bool reg = V <= 16384 && (ld_l % 4) == 0 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0 &&
-                     (reinterpret_cast<uintptr_t>(dlog) & 15) == 0;
-    if (reg) {
-        const int q = (V + 1023) / 1024;
-#define SX_LAUNCH(QQ)                                                                                                                      \
-    DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_reg_kernel<T, QQ, true, WEIGHTED, XentSmooth>), dim3(M), dim3(256), 0, st, logits,  \
-                                         ld_l, tgt, M, V, scale, logp_sum, (T *)dlog, ld_d, logp_rows, sm))
-        if (q <= 2) SX_LAUNCH(2);
-        else if (q <= 4) SX_LAUNCH(4);
-        else if (q <= 8) SX_LAUNCH(8);
-        else if (q <= 12) SX_LAUNCH(12);
-        else SX_LAUNCH(16);
-#undef SX_LAUNCH
-    } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((softmax_xent_kernel<T, true, WEIGHTED, XentSmooth>), dim3(M), dim3(256), 0, st, logits, ld_l, tgt,
-                                             M, V, scale, logp_sum, (T *)dlog, ld_d, logp_rows, sm));
-    }
-    if (logp_rows && logp_sum) hipLaunchKernelGGL(sum_rows_f64_kernel, dim3(1), dim3(256), 0, st, logp_rows, M, logp_sum);
-    if (sm.ll_rows && sm.ll_sum) hipLaunchKernelGGL(sum_rows_f64_kernel, dim3(1), dim3(256), 0, st, sm.ll_rows, M, sm.ll_sum);
-}
-__global__ void xent_targets_kernel(const int32_t *tgt, int M, int V, int32_t *out) {
-    const int m = blockIdx.x * blockDim.x + threadIdx.x;
-    if (m < M) out[m] = (tgt[m] >= 0 && tgt[m] < V) ? tgt[m] : -1;
-}
-}  // namespace
-void k_softmax_xent_smooth(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                           double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const XentSmooth &sm) {
-    if (sm.row_w) launch_softmax_xent_smooth<true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows, sm);
-    else launch_softmax_xent_smooth<false>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows, sm);
-}
-void k_xent_targets(hipStream_t st, const int32_t *tgt, int M, int V, int32_t *out) {
-    hipLaunchKernelGGL(xent_targets_kernel, dim3(cdiv(M, 256)), dim3(256), 0, st, tgt, M, V, out);
-}
-void k_softmax_xent(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                    float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
-    launch_softmax_xent<false>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows);
-}
-void k_softmax_xent_masked(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V,
-                           float scale, double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows) {
-    launch_softmax_xent<true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows);
-}
-void k_softmax_xent_weighted(hipStream_t st, int dtype, const float *logits, int64_t ld_l, const int32_t *tgt, int M, int V, float scale,
-                             double *logp_sum, void *dlog, int64_t ld_d, double *logp_rows, const float *row_w, int B) {
-    launch_softmax_xent<true, true>(st, dtype, logits, ld_l, tgt, M, V, scale, logp_sum, dlog, ld_d, logp_rows, row_w, B);
 }
 void k_transpose(hipStream_t st, int dtype, int in_f32, const void *in, int64_t ld_in, int R, int C, void *out,
                  int64_t ld_out, int shift) {

@@ -372,18 +372,18 @@ int lrcn_impl::loss_impl(lrcn_ctx *c, const LossCall &q) {
     }
     const float scale = (float)(1.0 / (q.lens ? (double)q.norm_tokens : (double)q.norm_B * (double)S));
     if (c->opt_det && !c->logp_rows) DALLOC(c, c->logp_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
-    void *const dlog = bwd ? c->dLog : nullptr;
-    double *const rows = c->opt_det ? c->logp_rows : nullptr;
+    XentCall x{};
+    x.logits = c->Logits; x.ld_l = c->ldV; x.tgt = c->tok_tgt; x.M = M; x.V = V; x.scale = scale;
+    x.dlog = bwd ? c->dLog : nullptr; x.ld_d = c->ldV;
+    x.sum = c->logp; x.rows = c->opt_det ? c->logp_rows : nullptr;
+    x.masked = q.lens != nullptr; x.row_w = q.row_w ? c->roww_dev : nullptr; x.B = B; x.eps = q.smooth;
     if (q.smooth > 0.0f) {  // label smoothing: the plain terms go to a second accumulator (lrcn_smooth_stats)
         if (!c->nll_acc) DALLOC(c, c->nll_acc, sizeof(double));
-        if (rows && !c->ll_rows) DALLOC(c, c->ll_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
+        if (x.rows && !c->ll_rows) DALLOC(c, c->ll_rows, sizeof(double) * (size_t)c->maxS * c->maxB);
         HIPCHK(c, hipMemsetAsync(c->nll_acc, 0, sizeof(double), st));
-        XentSmooth sm{};
-        sm.eps = q.smooth; sm.row_w = q.row_w ? c->roww_dev : nullptr; sm.B = B;
-        sm.ll_sum = c->nll_acc; sm.ll_rows = rows ? c->ll_rows : nullptr;
-        k_softmax_xent_smooth(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, sm);
-    } else if (q.row_w) k_softmax_xent_weighted(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows, c->roww_dev, B);
-    else (q.lens ? k_softmax_xent_masked : k_softmax_xent)(st, dt, c->Logits, c->ldV, c->tok_tgt, M, V, scale, c->logp, dlog, c->ldV, rows);
+        x.ll_sum = c->nll_acc; x.ll_rows = x.rows ? c->ll_rows : nullptr;
+    }
+    k_softmax_xent(st, dt, x);
     c->last_norm = q.norm_B;
     c->last_S = S;
     c->last_tokens = q.lens ? q.norm_tokens : 0;
@@ -812,16 +812,13 @@ int lrcn_xent_logits(lrcn_ctx *c, const float *logits, int64_t ld, const int32_t
     int32_t *tg = reinterpret_cast<int32_t *>(rows_scratch + M);
     k_xent_targets(st, tgt, M, V, tg);
     const int dt = out_dtype == LRCN_BF16 ? GEMM_T_BF16 : GEMM_T_F32;
-    if (smooth > 0.0f) {
-        XentSmooth sm{};
-        sm.eps = smooth; sm.row_w = row_w; sm.B = B; sm.ll_rows = ll_terms;
-        k_softmax_xent_smooth(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, terms, sm);
-    } else {
-        double *rows = terms ? terms : ll_terms ? ll_terms : rows_scratch;
-        if (row_w) k_softmax_xent_weighted(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, rows, row_w, B);
-        else k_softmax_xent_masked(st, dt, logits, ld, tg, M, V, scale, nullptr, dlog, ld_d, rows);
-        if (terms && ll_terms) HIPCHK(c, hipMemcpyAsync(ll_terms, terms, sizeof(double) * (size_t)M, hipMemcpyDeviceToDevice, st));
-    }
+    const bool sm = smooth > 0.0f;  // the unsmoothed kernels write one set of terms, and need a place for it
+    XentCall x{};
+    x.logits = logits; x.ld_l = ld; x.tgt = tg; x.M = M; x.V = V; x.scale = scale; x.dlog = dlog; x.ld_d = ld_d;
+    x.rows = (sm || terms) ? terms : ll_terms ? ll_terms : rows_scratch;
+    x.masked = true; x.row_w = row_w; x.B = B; x.eps = smooth; x.ll_rows = sm ? ll_terms : nullptr;
+    k_softmax_xent(st, dt, x);
+    if (!sm && terms && ll_terms) HIPCHK(c, hipMemcpyAsync(ll_terms, terms, sizeof(double) * (size_t)M, hipMemcpyDeviceToDevice, st));
     KCHK(c, "xent_logits");
     return LRCN_OK;
 }

@@ -1,9 +1,9 @@
-"""GPU: the training-side softmax + cross-entropy ladder (launch_softmax_xent, csrc/kernels.hip) on both sides of every rung -- the
+"""GPU: the training-side softmax + cross-entropy ladder (launch_softmax_xent, csrc/xent.hip) on both sides of every rung -- the
 counterpart of tests/test_gpu_decode_wide.py's softmax_topk_rows_kernel ladder.  Cases, critical columns and references:
 tests/xent_ladder_cases.py; that its inputs are decisive is asserted on the CPU (tests/test_xent_ladder_cases.py).
 
-One context per (V, type) runs the three forms: equal lengths (softmax_xent_reg_kernel<T, Q>), lens (<T, Q, true>) and lens + row weights
-(<T, Q, true, true>); at V = 16385 the streaming softmax_xent_kernel in the same three forms.
+One context per (V, type) runs the three forms: equal lengths (softmax_xent_reg_kernel<T, Q, XENT_PLAIN>), lens (<T, Q, XENT_MASKED>) and lens + row
+weights (<T, Q, XENT_WEIGHTED>); at V = 16385 the streaming softmax_xent_kernel in the same three forms.
 
 f32: against float64 with test_gpu_production_width.py's constants -- loss 1e-5 relative, gradients rtol 1e-3 + atol 1e-5, and per tensor
 ||g - g_f64|| / ||g_f64|| <= 1e-3.  g_bout is the column sum of d(logits): it sees every column of every row.  At V = 16384 and 16385 a

@@ -1,6 +1,6 @@
 """The training softmax ladder's cases, shared by tests/test_xent_ladder_cases.py (CPU) and tests/test_gpu_xent_ladder.py (GPU).
 
-launch_softmax_xent (csrc/kernels.hip) picks softmax_xent_reg_kernel<T, Q, MASKED, WEIGHTED> with Q = 2, 4, 8, 12, 16 for V <= 2048, 4096,
+launch_softmax_xent (csrc/xent.hip) picks softmax_xent_reg_kernel<T, Q, FORM> with Q = 2, 4, 8, 12, 16 for V <= 2048, 4096,
 8192, 12288, 16384 and the streaming softmax_xent_kernel above.  VOCABS holds the last V of every rung, the first of the next, and a V that
 is no multiple of 4 inside the two widest rungs.  A thread's q-th load of the register kernel covers columns 1024 q + 4 tid .. + 3, so the
 columns where a rung can go wrong are critical_columns(V): the first and last thread of the first two slots, both sides of the rung's last

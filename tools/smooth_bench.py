@@ -11,8 +11,11 @@ steps between two device synchronisations, timed on the host clock.  Per setting
 the ratio is of the medians.  The shader clock the device held is sampled over the whole timed part (bench.HwSampler).  There is no
 pass / fail: eps = 0 runs the kernels it ran before the option existed, and the eps > 0 ratio is a number to record.
 
-Writes profiles/smooth_bench.md (--out) and prints a JSON summary line.
-usage: python tools/smooth_bench.py [--rounds 7] [--iters 200] [--steps 30] [--out profiles/smooth_bench.md]"""
+--row-weights: every call also carries per-caption weights, all 1.0 -- the WEIGHTED form of the loss kernels against its SMOOTH form.
+
+Writes profiles/smooth_bench.md (with --row-weights: profiles/smooth_bench_weighted.md; --out names another file) and prints a JSON
+summary line.
+usage: python tools/smooth_bench.py [--rounds 7] [--iters 200] [--steps 30] [--row-weights] [--out FILE]"""
 import argparse
 import json
 import os
@@ -57,7 +60,7 @@ def summary(us):
     return {"median_us": float(np.median(a)), "min_us": float(a[0]), "max_us": float(a[-1]), "rounds": len(a)}
 
 
-def bench_shape(name, rounds, iters, steps):
+def bench_shape(name, rounds, iters, steps, row_weights):
     T, B, V = SHAPES[name]
     M = (T + 1) * B
     ctx = L.Context(E, H, H, V, max_B=B, max_T=T, lstm_dtype=lrcn_amd.LRCN_BF16)
@@ -67,7 +70,9 @@ def bench_shape(name, rounds, iters, steps):
     logits = (torch.randn((M, ld), generator=g, device="cuda") * 3.0)[:, :V]
     rng = np.random.default_rng(1)
     tgt = torch.as_tensor(rng.integers(0, V, size=M).astype(np.int32)).cuda()
-    xent = {eps: (lambda eps=eps: L.xent_logits(ctx, logits, tgt, B=B, scale=1.0 / M, label_smoothing=eps, out_dtype=torch.bfloat16, ld_d=ld))
+    w = torch.ones(B, device="cuda") if row_weights else None
+    xent = {eps: (lambda eps=eps: L.xent_logits(ctx, logits, tgt, row_weights=w, B=B, scale=1.0 / M, label_smoothing=eps, out_dtype=torch.bfloat16,
+                                                ld_d=ld))
             for eps in EPS}
     res = {"xent": {str(k): summary(v) for k, v in alternate(xent, rounds, iters, 20).items()}}
     param = L.initweights(ctx, seed=42)
@@ -76,7 +81,9 @@ def bench_shape(name, rounds, iters, steps):
     feats = L.to_jl((rng.standard_normal((B, 4096)) * 0.02).astype(np.float32))
     toks = torch.as_tensor(rng.integers(3, V, size=(T, B)).astype(np.int32)).cuda()
     lens = np.full(B, T, np.int32)
-    step = {eps: (lambda eps=eps: L.train_step(ctx, param, optim, grads, feats, toks, pdrop=0.4, seed=optim.t, lens=lens, label_smoothing=eps))
+    wh = np.ones(B, np.float32) if row_weights else None
+    step = {eps: (lambda eps=eps: L.train_step(ctx, param, optim, grads, feats, toks, pdrop=0.4, seed=optim.t, lens=lens, row_weights=wh,
+                                               label_smoothing=eps))
             for eps in EPS}
     res["step"] = {str(k): summary(v) for k, v in alternate(step, rounds, steps, 10).items()}
     ctx.close()
@@ -88,17 +95,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--steps", type=int, default=30)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "smooth_bench.md"))
+    ap.add_argument("--row-weights", action="store_true", help="per-caption weights of 1.0 in every call: the weighted forms")
+    ap.add_argument("--out", default=None, help="default profiles/smooth_bench.md, with --row-weights profiles/smooth_bench_weighted.md")
     a = ap.parse_args()
     from bench import HwSampler
     hw = HwSampler(torch.cuda.current_device())
     hw.start()
-    res = {name: bench_shape(name, a.rounds, a.iters, a.steps) for name in SHAPES}
+    res = {name: bench_shape(name, a.rounds, a.iters, a.steps, a.row_weights) for name in SHAPES}
     clock = hw.stop()
     sclk = (clock.get("sclk_mhz") or {}) if clock.get("available") else {}
-    lines = ["# Label smoothing: the cost of the SMOOTH loss kernels", "",
-             "`python tools/smooth_bench.py --rounds %d --iters %d --steps %d` on %s; bf16, E = H = 1000, two layers.  eps = 0 and eps = 0.1"
-             % (a.rounds, a.iters, a.steps, torch.cuda.get_device_name()),
+    a.out = a.out or os.path.join(ROOT, "profiles", "smooth_bench_weighted.md" if a.row_weights else "smooth_bench.md")
+    lines = ["# Label smoothing: the cost of the SMOOTH loss kernels" + (", with per-caption weights" if a.row_weights else ""), "",
+             "`python tools/smooth_bench.py --rounds %d --iters %d --steps %d%s` on %s; bf16, E = H = 1000, two layers.  eps = 0 and eps = 0.1"
+             % (a.rounds, a.iters, a.steps, " --row-weights" if a.row_weights else "", torch.cuda.get_device_name()),
              "alternate round by round in one process after a warm-up of each; a round is that many launches (xent) or steps between two device",
              "synchronisations on the host clock.  Median over the rounds, spread = min .. max.  Shader clock over the timed part: %s."
              % ("median %.0f MHz (min %.0f, max %.0f)" % (sclk["median"], sclk.get("min", float("nan")), sclk.get("max", float("nan")))
