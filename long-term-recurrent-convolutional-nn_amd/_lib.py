@@ -25,6 +25,7 @@ SCHED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_sched.
 SMOOTH_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_smooth.h"))      # lrcn_*_smooth / lrcn_xent_logits (not in lrcn.h)
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 and the fp8 seams (not in lrcn.h)
+DECODE_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_decode_debug.h"))  # lrcn_debug_decode_steps (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -65,6 +66,12 @@ class ConvGemmDebug(C.Structure):   # lrcn_conv_gemm_debug of include/lrcn_gemm_
     _fields_ = [("dtype", C.c_int), ("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("ldc", C.c_int64),
                 ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("relu", C.c_int), ("pool", C.c_int),
                 ("wg_cap", C.c_int)]
+
+
+class DecodeDebug(C.Structure):   # lrcn_decode_debug of include/lrcn_decode_debug.h
+    _fields_ = [("params", C.POINTER(C.c_void_p)), ("feats", C.c_void_p), ("N", C.c_int), ("per_image", C.c_int), ("steps", C.c_int),
+                ("tokens", C.POINTER(C.c_int32)), ("parents", C.POINTER(C.c_int32)), ("h1", C.c_void_p), ("h2", C.c_void_p),
+                ("c1", C.c_void_p), ("c2", C.c_void_p), ("logits", C.c_void_p), ("route", C.c_int)]
 
 
 class Dropout(C.Structure):
@@ -306,11 +313,16 @@ CONV_DEBUG_SIGNATURES = {
     "lrcn_debug_fp8_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_decode_debug.h declares (bound by lib() as well)
+DECODE_DEBUG_SIGNATURES = {
+    "lrcn_debug_decode_steps": (C.c_int, [C.c_void_p, C.POINTER(DecodeDebug)]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER,
-                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER, DECODE_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -332,7 +344,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + list(SMOOTH_SIGNATURES.items()) + \
-                list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()):
+                list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()) + list(DECODE_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -1,9 +1,11 @@
 // decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_score.h): the batched decode's routes,
-// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams and caption scoring.
+// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams and caption scoring;
+// the step's test entry (lrcn_decode_debug.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
+#include "../../include/lrcn_decode_debug.h"
 #include "../../include/lrcn_nbest.h"
 #include "../../include/lrcn_diverse.h"
 #include "../../include/lrcn_nucleus.h"
@@ -654,6 +656,61 @@ int lrcn_beam_search_batch(lrcn_ctx *c, const float *const p[9], const float *fe
     }
     KCHK(c, "beam_search_batch");
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, N, Lh, out_tokens, out_len, out_prob);
+}
+
+// Test entry (include/lrcn_decode_debug.h): the batched decode's own begin and step on the route decode_route picks, fed the caller's
+// tokens and parents instead of a beam's or a sampler's, the states and f32 logits copied out after every step.  The plain step reads no
+// parent, so its states are gathered in front of the step -- what lrcn_beam_search_batch does behind the step before.
+int lrcn_debug_decode_steps(lrcn_ctx *c, lrcn_decode_debug *d) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!d) FAIL(c, LRCN_EINVAL, "null argument");
+    const bool two = c->nl == 2;
+    if (!d->params || !d->feats || !d->tokens || !d->parents || !d->h1 || !d->c1 || !d->logits || (two && (!d->h2 || !d->c2)))
+        FAIL(c, LRCN_EINVAL, "null argument");
+    int64_t sz[9];
+    ctx_sizes(c, sz);
+    for (int i = 0; i < 9; ++i)
+        if (sz[i] > 0 && !d->params[i]) FAIL(c, LRCN_EINVAL, "null parameter array %d", i);
+    if (d->N < 1 || d->per_image < 1 || d->steps < 1) FAIL(c, LRCN_EINVAL, "N=%d, per_image=%d, steps=%d must be >= 1", d->N, d->per_image, d->steps);
+    if ((int64_t)d->N * d->per_image > c->maxB) FAIL(c, LRCN_EINVAL, "N*per_image = %d*%d exceeds max_B = %d", d->N, d->per_image, c->maxB);
+    const int N = d->N, R = d->N * d->per_image, S = d->steps, H1 = c->H1, H2 = c->H2, V = c->V;
+    for (int s = 0; s < S; ++s)
+        for (int r = 0; r < R; ++r) {
+            const int32_t tk = d->tokens[(int64_t)s * R + r], pa = d->parents[(int64_t)s * R + r];
+            if ((unsigned)tk >= (unsigned)V) FAIL(c, LRCN_EINVAL, "token (step %d, row %d) = %d outside [0, V=%d)", s, r, tk, V);
+            if (s > 0 && (unsigned)pa >= (unsigned)R) FAIL(c, LRCN_EINVAL, "parent (step %d, row %d) = %d outside [0, R=%d)", s, r, pa, R);
+        }
+    const float *const *p = d->params;
+    const size_t es = c->esz;
+    hipStream_t st = c->stream;
+    const DecodeRoute rt = decode_route(c, R, 0);
+    int r = decode_begin(c, p, d->feats, N, d->per_image, rt);
+    if (r) return r;
+    DecodeTail tail{};   // LOGITS: f32 logits in st_logits on every route
+    for (int s = 0; s < S; ++s) {
+        HIPCHK(c, hipMemcpyAsync(c->bs_last, d->tokens + (int64_t)s * R, sizeof(int32_t) * R, hipMemcpyHostToDevice, st));
+        if (s > 0) {
+            HIPCHK(c, hipMemcpyAsync(c->st_parent, d->parents + (int64_t)s * R, sizeof(int32_t) * R, hipMemcpyHostToDevice, st));
+            if (!rt.epi) follow_parents(c, R);   // :673-676
+        }
+        if ((r = decode_step(c, p, R, rt, s + 1, tail))) return r;
+        // this step's h: the epilogues' own buffers, or the h blocks of the plain step's [x | h] operands
+        const void *h1 = rt.epi ? c->st_h1 : boff(c->st_xh1, c->ldX1, es), *h2 = rt.epi ? c->st_h2 : boff(c->st_xh2, c->ldH2, es);
+        const int64_t ld1 = rt.epi ? c->ldH1 : c->ldXH1, ld2 = rt.epi ? c->ldH2 : c->ldXH2;
+        HIPCHK(c, hipMemcpyAsync(d->c1 + (int64_t)s * R * H1, c->st_f32[1], sizeof(float) * (size_t)R * H1, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpy2DAsync(boff(d->h1, (int64_t)s * R * H1, es), es * H1, h1, es * ld1, es * H1, R, hipMemcpyDeviceToDevice, st));
+        if (two) {
+            HIPCHK(c, hipMemcpyAsync(d->c2 + (int64_t)s * R * H2, c->st_f32[3], sizeof(float) * (size_t)R * H2, hipMemcpyDeviceToDevice, st));
+            HIPCHK(c, hipMemcpy2DAsync(boff(d->h2, (int64_t)s * R * H2, es), es * H2, h2, es * ld2, es * H2, R, hipMemcpyDeviceToDevice, st));
+        }
+        HIPCHK(c, hipMemcpy2DAsync(d->logits + (int64_t)s * R * V, sizeof(float) * V, c->st_logits, sizeof(float) * c->ldV, sizeof(float) * V, R,
+                                   hipMemcpyDeviceToDevice, st));
+    }
+    KCHK(c, "debug_decode_steps");
+    HIPCHK(c, hipStreamSynchronize(st));
+    d->route = rt.tables ? 2 : rt.epi ? 1 : 0;
+    return LRCN_OK;
 }
 
 }  // extern "C"

@@ -1066,6 +1066,44 @@ def debug_conv_gemm(ctx, dtype, x, w, y, N, H, W, Cin, Cout, ldc, bias=None, rel
     return debug_route(ctx, 0)
 
 
+def debug_decode_steps(ctx, param, feats, per_image, tokens, parents, out=None):
+    """The batched decode step on caller-given tokens and parents (lrcn_debug_decode_steps, include/lrcn_decode_debug.h): feats N x 4096 on
+    the device, tokens / parents [steps][N * per_image] host ints (row r of step s feeds tokens[s][r] and continues the states row
+    parents[s][r] had after step s-1; parents[0] is not read).  Returns a dict of NumPy arrays -- "h1", "c1", "h2", "c2" [steps][R][H] (h2,
+    c2 None on LRCN-1f), "logits" [steps][R][V], float32, a bfloat16 h widened on the host -- and "route": 0 plain, 1 cell epilogue, 2 tables.
+    out: the device tensors the call writes ("h1", "h2" in the LSTM element type, "c1", "c2", "logits" float32) instead of fresh ones."""
+    tok = np.ascontiguousarray(np.asarray(tokens, dtype=np.int32))
+    par = np.ascontiguousarray(np.asarray(parents, dtype=np.int32))
+    N = feats.shape[0]
+    R = N * int(per_image)
+    if tok.ndim != 2 or tok.shape != par.shape or tok.shape[1] != R:
+        raise LrcnError("tokens and parents must both be [steps][N * per_image]")
+    S, two = tok.shape[0], ctx.n_layers != 1
+    ht = torch.bfloat16 if ctx.lstm_dtype == LRCN_BF16 else torch.float32
+    dev = feats.device
+    if out is None:
+        out = {"h1": torch.empty((S, R, ctx.H1), dtype=ht, device=dev), "c1": torch.empty((S, R, ctx.H1), dtype=torch.float32, device=dev),
+               "h2": torch.empty((S, R, ctx.H2), dtype=ht, device=dev) if two else None,
+               "c2": torch.empty((S, R, ctx.H2), dtype=torch.float32, device=dev) if two else None,
+               "logits": torch.empty((S, R, ctx.V), dtype=torch.float32, device=dev)}
+    addr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    p9 = _p9(param)
+    d = _lib.DecodeDebug(C.cast(p9, C.POINTER(C.c_void_p)), _ptr(feats), N, int(per_image), S, tok.ctypes.data_as(C.POINTER(C.c_int32)),
+                         par.ctypes.data_as(C.POINTER(C.c_int32)), addr(out["h1"]), addr(out.get("h2")), addr(out["c1"]), addr(out.get("c2")),
+                         addr(out["logits"]), -1)
+    ctx._call("lrcn_debug_decode_steps", C.byref(d))
+    def host(t):   # copied as stored; bfloat16 bits widened to float32 here, on the host
+        if t is None:
+            return None
+        if t.dtype == torch.bfloat16:
+            bits = t.view(torch.int16).cpu().numpy().view(np.uint16).astype(np.uint32) << 16
+            return bits.view(np.float32)
+        return t.cpu().numpy()
+    res = {k: host(out.get(k)) for k in ("h1", "c1", "h2", "c2", "logits")}
+    res["route"] = d.route
+    return res
+
+
 def synthetic_vgg_weights(seed=1, device="cuda", bias_std=0.0):
     """He-normal(fan_in) VGG-16 weights (no pretrained file offline); biases zero, or N(0, bias_std)
     so that every bias path of the kernels sees non-zero values (parity tests)."""

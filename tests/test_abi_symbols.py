@@ -57,3 +57,21 @@ def test_conv_debug_binding_declares_exactly_its_header():
         assert name not in _lib.SIGNATURES and name not in header, name
         assert hasattr(so, name), name
     assert "#define LRCN_ABI_VERSION" not in raw and '#include "lrcn.h"' in raw
+
+
+def test_decode_debug_binding_declares_exactly_its_header():
+    # include/lrcn_decode_debug.h: the batched decode step's test entry beside the ABI -- exported by the library, bound by its own table,
+    # absent from lrcn.h; the binding's structure has the header's fields in the header's order
+    raw = open(_lib.DECODE_DEBUG_HEADER).read()
+    txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
+    names = ["lrcn_debug_decode_steps"]
+    assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.DECODE_DEBUG_SIGNATURES) == names
+    header = open(_lib.HEADER).read()
+    so = ctypes.CDLL(_lib.LIB_PATH)
+    for name in names:
+        assert name not in _lib.SIGNATURES and name not in header, name
+        assert hasattr(so, name), name
+    assert "#define LRCN_ABI_VERSION" not in raw and '#include "lrcn.h"' in raw
+    body = re.search(r"typedef struct lrcn_decode_debug \{(.*?)\} lrcn_decode_debug;", txt, flags=re.S).group(1)
+    fields = [f.strip(" *") for decl in body.split(";") if decl.strip() for f in re.sub(r"^.*?(\**\w+\s*(,|$))", r"\1", decl.strip(), count=1).split(",")]
+    assert fields == [f[0] for f in _lib.DecodeDebug._fields_], fields
