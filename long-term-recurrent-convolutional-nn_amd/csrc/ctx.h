@@ -134,6 +134,10 @@ struct lrcn_ctx {
     int4 *nb_pool = nullptr, *nb_img = nullptr;
     float *nb_cum = nullptr, *nb_res_score = nullptr;
     int32_t *dv_done = nullptr;   // lrcn_beam_diverse_batch (include/lrcn_diverse.h), lazily: one done flag per image [maxB]; the rest is nb_*
+    // include/lrcn_constrain.h: the call's static ban bitmap [(V + 31) / 32] words, and behind it lrcn_constrained_topk_logits' scratch of
+    // the general form (V > 16384); one device buffer, grown to the largest call's need, freed by lrcn_destroy
+    void *cn_arena = nullptr;
+    size_t cn_bytes = 0;
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;

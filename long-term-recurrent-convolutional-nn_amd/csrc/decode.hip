@@ -1,10 +1,12 @@
-// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_score.h): the batched decode's routes,
-// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams and caption scoring;
+// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_constrain.h, lrcn_score.h): the batched decode's routes,
+// tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams (and their
+// constrained form, lrcn_constrain.h) and caption scoring;
 // the step's test entry (lrcn_decode_debug.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
+#include "../../include/lrcn_constrain.h"
 #include "../../include/lrcn_decode_debug.h"
 #include "../../include/lrcn_nbest.h"
 #include "../../include/lrcn_diverse.h"
@@ -830,13 +832,61 @@ int lrcn_sample_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int 
     return LRCN_OK;
 }
 
+// ---------------------------------------------------------------------------- constrained top-K (include/lrcn_constrain.h, constrain.hip)
+// The checks of a constraint set for a vocabulary of V, a width K and histories of at most `words` words (the feasibility bound
+// V - nbanned - 1 - words >= K; K = 0: not asked); max_min_len < 0: min_len is not bounded.  bits: the list as a bitmap of (V + 31) / 32 words.
+static int constraints_check(lrcn_ctx *c, const lrcn_constraints *cons, int V, int K, int words, int max_min_len, std::vector<uint32_t> &bits) {
+    if (cons->nbanned < 0 || cons->min_len < 0 || cons->no_repeat_ngram < 0)
+        FAIL(c, LRCN_EINVAL, "constraints: nbanned=%d, min_len=%d, no_repeat_ngram=%d must be >= 0", cons->nbanned, cons->min_len, cons->no_repeat_ngram);
+    if (cons->nbanned > 0 && !cons->banned) FAIL(c, LRCN_EINVAL, "constraints: nbanned=%d with a NULL list", cons->nbanned);
+    if (max_min_len >= 0 && cons->min_len > max_min_len) FAIL(c, LRCN_EINVAL, "constraints: min_len=%d exceeds nword=%d", cons->min_len, max_min_len);
+    bits.assign(((size_t)V + 31) / 32, 0u);
+    for (int q = 0; q < cons->nbanned; ++q) {
+        const int32_t v = cons->banned[q];
+        if (v < 1 || v >= V) FAIL(c, LRCN_EINVAL, "constraints: banned[%d]=%d outside [1, V=%d) (eos: use min_len)", q, v, V);
+        if ((bits[v >> 5] >> (v & 31)) & 1u) FAIL(c, LRCN_EINVAL, "constraints: banned[%d]=%d is a duplicate", q, v);
+        bits[v >> 5] |= 1u << (v & 31);
+    }
+    if (K > 0 && (int64_t)V - cons->nbanned - 1 - words < K)
+        FAIL(c, LRCN_EINVAL, "constraints: V - nbanned - 1 - %d = %lld leaves fewer than K=%d allowed words", words,
+             (long long)V - cons->nbanned - 1 - words, K);
+    return LRCN_OK;
+}
+// the bitmap into the context's buffer, with `scratch` bytes behind it (*scratch_out); the call's only wait besides its results
+static int constraints_upload(lrcn_ctx *c, const std::vector<uint32_t> &bits, size_t scratch, float **scratch_out) {
+    const size_t b_bits = (sizeof(uint32_t) * bits.size() + 255) & ~(size_t)255, need = b_bits + scratch;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // a previous call may still read the buffer
+    if (need > c->cn_bytes) {
+        if (c->cn_arena) (void)hipFree(c->cn_arena);
+        c->cn_arena = nullptr;
+        c->cn_bytes = 0;
+        if (hipMalloc(&c->cn_arena, need) != hipSuccess) FAIL(c, LRCN_ENOMEM, "hipMalloc(%zu) for the constraints failed", need);
+        c->cn_bytes = need;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->cn_arena, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vector is read before it goes out of scope
+    if (scratch_out) *scratch_out = reinterpret_cast<float *>(reinterpret_cast<char *>(c->cn_arena) + b_bits);
+    return LRCN_OK;
+}
+// topk_rows' LOGP form on the allowed columns: one pass where the rows kernel fits, else log-softmax into `scratch` [R][ld], -inf over the
+// banned columns, and the plain top-K
+static void constrained_topk_rows(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int K, const ConstrainArgs &a, float *scratch,
+                                  int32_t *idx, float *val) {
+    if (k_constrained_topk_rows(c->stream, logits, ld, R, V, K, a, idx, val)) return;
+    k_log_softmax_rows(c->stream, logits, ld, R, V, scratch, ld);
+    k_constrain_mask_rows(c->stream, scratch, ld, R, V, a);
+    k_topk_rows(c->stream, scratch, ld, R, V, K, idx, val);
+}
+
 // The n-best beam search (include/lrcn_nbest.h): the batched decode of lrcn_beam_search_batch (decode_begin / decode_step on the route
 // decode_route picks, N*K rows) with log-probability top-K (the LOGP forms of the records merge and the rows kernel) and its own per-step
 // bookkeeping (nbest.hip): live slots in log space, a pool of finished hypotheses with length normalisation, the exact early stop.
 // G > 0 (0: the n-best beam): diverse beam search (include/lrcn_diverse.h) -- the same decode and top-K at the full width K, the bookkeeping
 // of diverse.hip.
+// cons != NULL (include/lrcn_constrain.h; its entry point passes NULL for an empty set): the record epilogue is off, as for a nucleus call
+// of sample_impl, the step leaves f32 logits, and constrained_topk_rows on them and the histories in bs_seq takes topk_rows' place.
 static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
-                          int32_t *out_tokens, int *out_len, float *out_logp, float *out_score) {
+                          int32_t *out_tokens, int *out_len, float *out_logp, float *out_score, const lrcn_constraints *cons = nullptr) {
     if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
     if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
     if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d must be in [1, max_B = %d]", N, K, c->maxB);
@@ -847,10 +897,15 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     if (diverse && (!std::isfinite(lambda) || lambda < 0.0f)) FAIL(c, LRCN_EINVAL, "lambda=%g must be finite and >= 0", (double)lambda);
     const int R = N * K, Lh = nword + 2;
     hipStream_t st = c->stream;
-    int r = nbest_alloc(c);
-    if (r) return r;
+    int r;
+    std::vector<uint32_t> bits;
+    if (cons && (r = constraints_check(c, cons, c->V, K, nword, nword, bits))) return r;
+    if ((r = nbest_alloc(c))) return r;
     if (diverse && !c->dv_done) DALLOC(c, c->dv_done, sizeof(int32_t) * (size_t)c->maxB);
-    const DecodeRoute rt = decode_route(c, R, K);
+    if (cons && (r = constraints_upload(c, bits, 0, nullptr))) return r;
+    ConstrainArgs ca{reinterpret_cast<const uint32_t *>(c->cn_arena), nullptr, Lh, 0, cons ? cons->min_len : 0, cons ? cons->no_repeat_ngram : 0, LRCN_EOS};
+    DecodeRoute rt = decode_route(c, R, K);
+    if (cons) rt.smax = false;
     if ((r = decode_begin(c, p, feats, N, K, rt))) return r;
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
     DiverseState ds{};
@@ -870,9 +925,15 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     tail.K = K;
     tail.logp = true;
     tail.records = rt.smax;
+    if (cons) tail = DecodeTail{};   // LOGITS: the top-K follows the step, from st_logits
     int cur = 0;
     for (int current = 1; current <= nword + 1; ++current) {
         if ((r = decode_step(c, p, R, rt, current, tail))) return r;
+        if (cons) {
+            ca.hist = c->bs_seq[cur];
+            ca.current = current;
+            constrained_topk_rows(c, c->st_logits, c->ldV, R, c->V, K, ca, c->st_prob, c->st_topi, c->st_topv);
+        }
         ns.seq_in = c->bs_seq[cur];
         ns.seq_out = c->bs_seq[cur ^ 1];
         ns.current = current;
@@ -885,7 +946,7 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
         if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
         if (done) break;
     }
-    KCHK(c, diverse ? "beam_diverse_batch" : "beam_nbest_batch");
+    KCHK(c, cons ? "beam_constrained_batch" : diverse ? "beam_diverse_batch" : "beam_nbest_batch");
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, R, Lh, out_tokens, out_len, out_logp, c->nb_res_score, out_score);
 }
 
@@ -902,6 +963,40 @@ int lrcn_beam_diverse_batch(lrcn_ctx *c, const float *const p[9], const float *f
     DeviceGuard dg(c);
     if (G < 1) FAIL(c, LRCN_EINVAL, "groups G=%d must be >= 1", G);
     return pool_beam_impl(c, p, feats, N, K, G, lambda, nword, alpha, out_tokens, out_len, out_logp, out_score);
+}
+
+// include/lrcn_constrain.h.  An empty set is the unconstrained call itself.
+int lrcn_beam_constrained_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
+                                const lrcn_constraints *cons, int32_t *out_tokens, int *out_len, float *out_logp, float *out_score) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (G < 0) FAIL(c, LRCN_EINVAL, "groups G=%d must be >= 0 (0: the n-best beam)", G);
+    if (cons && cons->nbanned == 0 && cons->min_len == 0 && cons->no_repeat_ngram == 0) cons = nullptr;   // (a negative field is not empty: rejected below)
+    return pool_beam_impl(c, p, feats, N, K, G, G ? lambda : 0.0f, nword, alpha, out_tokens, out_len, out_logp, out_score, cons);
+}
+
+int lrcn_constrained_topk_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int K, const lrcn_constraints *cons, const int32_t *hist,
+                                 int64_t ld_hist, int current, int32_t *out_idx, float *out_logp) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!logits || !hist || !out_idx || !out_logp) FAIL(c, LRCN_EINVAL, "null argument");
+    if (R < 1 || V < 1 || ld < V || (ld & 3)) FAIL(c, LRCN_EINVAL, "R=%d, V=%d must be >= 1, ld=%lld >= V and a multiple of 4", R, V, (long long)ld);
+    if (K < 1 || K > 32 || K > V) FAIL(c, LRCN_EINVAL, "K=%d must be in [1, min(32, V=%d)]", K, V);
+    if (current < 1 || current > ld_hist || current > LRCN_BEAM_MAXLEN - 1)
+        FAIL(c, LRCN_EINVAL, "current=%d outside [1, min(ld_hist=%lld, %d)]", current, (long long)ld_hist, LRCN_BEAM_MAXLEN - 1);
+    const lrcn_constraints none{nullptr, 0, 0, 0};
+    if (!cons) cons = &none;
+    const bool empty = cons->nbanned == 0 && cons->min_len == 0 && cons->no_repeat_ngram == 0;   // then K <= V is all it takes
+    std::vector<uint32_t> bits;
+    int r = constraints_check(c, cons, V, empty ? 0 : K, current - 1, -1, bits);
+    if (r) return r;
+    const bool general = V > 16384 || (reinterpret_cast<uintptr_t>(logits) & 15);
+    float *scratch = nullptr;
+    if ((r = constraints_upload(c, bits, general ? sizeof(float) * (size_t)R * ld : 0, &scratch))) return r;
+    const ConstrainArgs ca{reinterpret_cast<const uint32_t *>(c->cn_arena), hist, ld_hist, current, cons->min_len, cons->no_repeat_ngram, LRCN_EOS};
+    constrained_topk_rows(c, logits, ld, R, V, K, ca, scratch, out_idx, out_logp);
+    KCHK(c, "constrained_topk_logits");
+    return LRCN_OK;
 }
 
 // Caption scoring (include/lrcn_score.h; paper section 5.1 / Table 2 -- not in lrcn.jl): see score_impl

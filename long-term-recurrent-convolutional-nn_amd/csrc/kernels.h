@@ -279,6 +279,24 @@ void k_repeat_rows(hipStream_t st, int dtype, const void *in, int64_t ld, int N,
 // out[r][0..C) = in[src_row[r]][0..C)  (beam search parent-state gather, lrcn.jl:673-676); in != out.
 void k_gather_rows_f32(hipStream_t st, const float *in, int64_t ld, const int32_t *src_row, int R, int C, float *out);
 
+// ---- constrain.hip: the constrained top-K of a decode step (include/lrcn_constrain.h) ----
+// What is not allowed at step `current` (1-based) for row r, whose history (bos first) is hist[r * ld_hist + 0 .. current - 1]: the columns
+// of the static bitmap ban [(V + 31) / 32] (NULL: none; bits past V are zero), eos while current <= min_len, and with ngram = n >= 1 every
+// word that would complete an n-gram the history already holds.  current <= 257.
+struct ConstrainArgs {
+    const uint32_t *ban;
+    const int32_t *hist;
+    int64_t ld_hist;
+    int current, min_len, ngram, eos;
+};
+// For each of R rows of f32 logits [R][ld]: the K best allowed columns by logp = (z - max z) - log(sum exp(z - max z)) over ALL V columns,
+// descending, ties to the lower column -- k_softmax_topk_rows' LOGP form (the same normaliser, bit for bit) on the allowed columns.
+// false: V too large for the register-resident form; then k_log_softmax_rows, k_constrain_mask_rows on its output and k_topk_rows.
+bool k_constrained_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, const ConstrainArgs &a, int32_t *idx,
+                             float *val);
+// lp[r][v] = -inf for every column v that is not allowed for row r (any V)
+void k_constrain_mask_rows(hipStream_t st, float *lp, int64_t ld, int R, int V, const ConstrainArgs &a);
+
 // ---- image_kernels.hip: the VGG side (vgg.hip, conv64.hip, conv64f.hip) ----
 // conv weight (3,3,Cin,Cout) column-major f32 -> [Cout][tap = b*3+a][Cin_pad] T (zero padded channels)
 void k_repack_conv_w(hipStream_t st, int dtype, const float *w, int Cin, int Cout, int Cin_pad, void *out);

@@ -168,6 +168,7 @@ void lrcn_destroy(lrcn_ctx *c) {
     for (void *p : c->allocs) (void)hipFree(p);
     if (c->sc_arena) (void)hipFree(c->sc_arena);
     if (c->xl_arena) (void)hipFree(c->xl_arena);
+    if (c->cn_arena) (void)hipFree(c->cn_arena);
     for (auto &e : c->grad_ev)
         if (e) (void)hipEventDestroy(e);
     for (auto &e : c->wg_fork)

@@ -734,6 +734,72 @@ def diverse_captions(ctx, param, feats, index_to_word, beam_width, groups, stren
             for img in beam_diverse_batch(ctx, param, feats, beam_width, groups, strength, nword, alpha)]
 
 
+def _constraints(banned, min_len, no_repeat_ngram):
+    """-> (lrcn_constraints, the array its list points to, which the caller keeps alive over the call)"""
+    ids = [int(v) for v in banned]
+    arr = (C.c_int32 * max(len(ids), 1))(*ids)
+    return _lib.Constraints(arr if ids else None, len(ids), int(min_len), int(no_repeat_ngram)), arr
+
+
+def beam_constrained_batch(ctx, param, feats, beam_width, nword, alpha=0.0, banned=(), min_len=0, no_repeat_ngram=0, groups=0, strength=0.0):
+    """Constrained beam search (lrcn_beam_constrained_batch, include/lrcn_constrain.h): the n-best beam (groups 0) or diverse beam search
+    (groups >= 1, with `strength`) that never proposes a word of `banned` (token ids in [1, V); not eos), never ends a caption in eos
+    before it has min_len words, and with no_repeat_ngram = n >= 1 never completes an n-gram the caption already holds.  logp stays the
+    model's log-likelihood of the caption (the bans do not renormalise).  Returns what beam_nbest_batch returns for groups == 0 and what
+    beam_diverse_batch returns for groups >= 1; with nothing constrained it is that call, bit for bit."""
+    N, K, G, L = feats.shape[0], beam_width, int(groups), nword + 2
+    out = (C.c_int32 * (N * K * L))()
+    n = (C.c_int * (N * K))()
+    lp = (C.c_float * (N * K))()
+    sc = (C.c_float * (N * K))()
+    cons, keep = _constraints(banned, min_len, no_repeat_ngram)
+    ctx._call("lrcn_beam_constrained_batch", _p9(param), _ptr(feats), N, K, G, float(strength), nword, float(alpha), C.byref(cons), out, n, lp, sc)
+    del keep
+    toks = np.ctypeslib.as_array(out).reshape(N * K, L).tolist()
+    n, lp, sc = list(n), list(lp), list(sc)
+    if G == 0:
+        return [[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K, (i + 1) * K) if n[r] > 0] for i in range(N)]
+    Kp = K // G
+    return [[[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K + g * Kp, i * K + (g + 1) * Kp) if n[r] > 0] for g in range(G)] for i in range(N)]
+
+
+def constrained_captions(ctx, param, feats, index_to_word, beam_width, nword, alpha=0.0, banned=(), min_len=0, no_repeat_ngram=0, groups=0,
+                         strength=0.0, normalize=False):
+    """beam_constrained_batch as caption text: as nbest_captions (groups == 0) or diverse_captions (groups >= 1)."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    res = beam_constrained_batch(ctx, param, feats, beam_width, nword, alpha, banned, min_len, no_repeat_ngram, groups, strength)
+    if groups == 0:
+        return [[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in entries] for entries in res]
+    return [[[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in grp] for grp in img] for img in res]
+
+
+def constrained_topk_logits(ctx, logits, K, hist, current, banned=(), min_len=0, no_repeat_ngram=0):
+    """One step of the constrained top-K on the caller's own logits (lrcn_constrained_topk_logits, include/lrcn_constrain.h): logits numpy
+    [R][V] f32 (V % 4 == 0, or a torch device tensor whose row stride is a multiple of 4 and >= V = its column count), hist numpy [R][>=
+    current] int32 with bos at position 0 -> numpy (columns [R][K] int32, logp [R][K] f32).  Independent of the context's model sizes."""
+    dev = "cuda:%d" % ctx.device
+    if isinstance(logits, torch.Tensor):
+        z = logits
+    else:
+        a = np.ascontiguousarray(logits, dtype=np.float32)
+        ld = (a.shape[1] + 3) // 4 * 4   # rows 16 bytes apart
+        z = torch.zeros((a.shape[0], ld), dtype=torch.float32, device=dev)[:, :a.shape[1]]
+        z.copy_(torch.from_numpy(a))
+    R, V = z.shape
+    h = torch.from_numpy(np.ascontiguousarray(hist, dtype=np.int32)).to(dev)
+    idx = torch.empty((R, K), dtype=torch.int32, device=z.device)
+    lp = torch.empty((R, K), dtype=torch.float32, device=z.device)
+    cons, keep = _constraints(banned, min_len, no_repeat_ngram)
+    torch.cuda.synchronize(z.device)   # the uploads have landed whichever stream the context runs on
+    ctx._call("lrcn_constrained_topk_logits", C.c_void_p(z.data_ptr()), z.stride(0), R, V, int(K), C.byref(cons), C.c_void_p(h.data_ptr()),
+              h.shape[1], int(current), C.c_void_p(idx.data_ptr()), C.c_void_p(lp.data_ptr()))
+    del keep
+    ctx.sync()
+    return idx.cpu().numpy(), lp.cpu().numpy()
+
+
 def _caption(seq, index_to_word):
     words = []
     for t in seq[1:]:

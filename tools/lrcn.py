@@ -78,6 +78,11 @@ def build_parser():
                         "best-scoring entry over all groups (0 = off)")
     p.add_argument("--diverse_strength", type=float, default=0.5,
                    help="--diverse_groups: what a word loses per beam of an earlier group that took it at the same step")
+    p.add_argument("--ban_words", default="",
+                   help="--nbest: constrained beam search (include/lrcn_constrain.h) -- comma-separated vocabulary words that no caption may "
+                        "hold (their probability is not given to the others: logp stays the model's)")
+    p.add_argument("--min_len", type=int, default=0, help="--nbest: a caption does not end before it has this many words (at most --generate)")
+    p.add_argument("--no_repeat_ngram", type=int, default=0, help="--nbest: no caption holds the same N words in a row twice (0 = off; 1 = no word twice)")
     p.add_argument("--retrieval", action="store_true",
                    help="image-caption retrieval (paper section 5.1 / Table 2): score --capnumber images of the --generate split, drawn as --generate "
                         "draws them (a permutation seeded by --seed), against all their captions; R@1/5/10 and Medr both ways, "
@@ -138,7 +143,14 @@ def tokenize_all(o, cap):
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    o = build_parser().parse_args(argv)
+    parser = build_parser()
+    o = parser.parse_args(argv)
+    ban_words = [w for w in o.ban_words.split(",") if w]
+    constrained = bool(ban_words) or o.min_len != 0 or o.no_repeat_ngram != 0
+    if constrained and not (o.nbest and o.generate > 0 and o.sample <= 0):
+        parser.error("--ban_words / --min_len / --no_repeat_ngram constrain the n-best beam: give --generate N --nbest (without --sample)")
+    if o.min_len < 0 or o.no_repeat_ngram < 0 or o.min_len > max(o.generate, 0):
+        parser.error("--min_len must be in [0, --generate] and --no_repeat_ngram >= 0")
     if o.varlen and not o.train:
         raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
     if o.ss_start >= 0 and (not o.train or o.scst):
@@ -206,6 +218,12 @@ def main(argv=None):
         raise SystemExit("need --datafiles or --loadfile (no vocabulary)")
     V = len(vocab)
     say("%d unique words" % V)
+    ban_ids = []
+    for w in ban_words:   # 0-based ABI ids; the end of a caption is --min_len's business
+        if w in ("<eos>", cap.EOS_WORD) or w not in vocab:
+            parser.error("--ban_words: %r %s" % (w, "ends a caption: use --min_len" if w in ("<eos>", cap.EOS_WORD) else "is not in the vocabulary"))
+        if vocab[w] - 1 not in ban_ids:
+            ban_ids.append(vocab[w] - 1)
     if len(o.hidden) != 2 or o.hidden[1] % 2:
         raise SystemExit("--hidden takes two sizes, the second even (LRCN-2f, lrcn.jl:496-504)")
     H1, H2 = o.hidden
@@ -257,6 +275,17 @@ def main(argv=None):
     def feature_rows(table, ids):
         return L.to_jl(np.stack([table[i].reshape(-1) for i in ids]).astype(np.float32))
 
+    def nbest_lists(f):     # --nbest, under --ban_words / --min_len / --no_repeat_ngram the constrained beam
+        if constrained:
+            return L.beam_constrained_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm, ban_ids, o.min_len, o.no_repeat_ngram)
+        return L.beam_nbest_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm)
+
+    def diverse_lists(f):   # --nbest --diverse_groups, likewise
+        if constrained:
+            return L.beam_constrained_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm, ban_ids, o.min_len, o.no_repeat_ngram,
+                                            groups=o.diverse_groups, strength=o.diverse_strength)
+        return L.beam_diverse_batch(ctx, param, f, o.beam_width, o.diverse_groups, o.diverse_strength, o.generate, o.length_norm)
+
     # ---------------------------------------------------------------- generate (lrcn.jl:127-160)
     if o.generate > 0:
         sample_seed = o.seed if o.seed > 0 else 0
@@ -270,12 +299,12 @@ def main(argv=None):
                     print(line)
                 return 0
             if o.nbest and o.diverse_groups > 0:   # the groups in order, each best score first: group<TAB>score<TAB>logp<TAB>caption
-                for g, grp in enumerate(L.beam_diverse_batch(ctx, param, f, o.beam_width, o.diverse_groups, o.diverse_strength, o.generate, o.length_norm)[0]):
+                for g, grp in enumerate(diverse_lists(f)[0]):
                     for toks, lp, sc in grp:
                         print("%d\t%.6f\t%.6f\t%s" % (g, sc, lp, cap.caption_text(toks, idx2word)))
                 return 0
             if o.nbest:   # the n-best list, best score first: score<TAB>logp<TAB>caption
-                for toks, lp, sc in L.beam_nbest_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm)[0]:
+                for toks, lp, sc in nbest_lists(f)[0]:
                     print("%.6f\t%.6f\t%s" % (sc, lp, cap.caption_text(toks, idx2word)))
                 return 0
             toks, _ = L.beam_search(ctx, param, f, o.beam_width, o.generate)
@@ -316,7 +345,7 @@ def main(argv=None):
                 if dvf is not None:
                     # candidates / ids keep the best-scoring entry over all groups (the earlier group wins a tie); `diverse` holds the groups
                     # in order, each best first: "id<TAB>group<TAB>score<TAB>logp<TAB>caption"
-                    res = L.beam_diverse_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.diverse_groups, o.diverse_strength, o.generate, o.length_norm)
+                    res = diverse_lists(feature_rows(table, chunk))
                     for i, groups in zip(chunk, res):
                         best = max((grp[0] for grp in groups if grp), key=lambda e: e[2])
                         ido.write("%d\n" % i)
@@ -327,7 +356,7 @@ def main(argv=None):
                     continue
                 if nbf is not None:
                     # candidates / ids keep each image's best entry; `nbest` holds the list: "id<TAB>score<TAB>logp<TAB>caption", best first
-                    for i, entries in zip(chunk, L.beam_nbest_batch(ctx, param, feature_rows(table, chunk), o.beam_width, o.generate, o.length_norm)):
+                    for i, entries in zip(chunk, nbest_lists(feature_rows(table, chunk))):
                         ido.write("%d\n" % i)
                         out.write(cap.caption_text(entries[0][0], idx2word) + "\n")
                         for toks, lp, sc in entries:
