@@ -1,6 +1,6 @@
 /* lrcn_conv_debug.h -- test entries of the convolution stack's pieces that no other entry reaches alone, beside the C ABI of include/lrcn.h
  * (which it includes; LRCN_ABI_VERSION is unchanged): conv1_1 of the bf16 stack by itself (conv11.hip), from either of its two source
- * forms, and the seams of the fp8 stack (fp8.hip's two casts and its amax, conv2_1's e4m3 epilogue in conv64.hip, the calibrated scales).
+ * forms, conv64.hip's plain halo-patch kernel on the caller's operands under a workgroup cap, and the seams of the fp8 stack (fp8.hip's two casts and its amax, conv2_1's e4m3 epilogue in conv64.hip, the calibrated scales).
  * Implemented by liblrcn_hip.so only: the CPU oracle does not implement these entry points. */
 #ifndef LRCN_CONV_DEBUG_H
 #define LRCN_CONV_DEBUG_H
@@ -41,6 +41,29 @@ int lrcn_debug_amax(lrcn_ctx *ctx, const void *x_bf16, int64_t n, float *out_dev
  * multiple of 64, N < 1, N * W * H * 64 does not fit 31 bits, or f8_inv_scale is not finite or not positive. */
 int lrcn_debug_conv64_f8(lrcn_ctx *ctx, const float *x, int W, int H, int N, const float *w, const float *b, int Cout, float f8_inv_scale,
                          float *y);
+
+/* One 3x3 convolution (stride 1, zero padding 1) (+ bias[Cout]) (ReLU) (2x2 maximum) of 64 input channels on conv64.hip's halo-patch kernel
+ * (conv64_kernel<pool, false>: conv1_2 and conv2_1 of the bf16 stack), on the caller's operands in the KERNEL's layouts, in the style of
+ * lrcn_debug_conv_gemm (include/lrcn_gemm_debug.h): every pointer is a device pointer that the caller allocated and filled; the entry
+ * allocates nothing and converts nothing.
+ *   y[n][r][q][co] = sum over kh, kw, c of x[n][r + kh - 1][q + kw - 1][c] * w[co][kh * 3 + kw][c]   (terms outside the image are zero) */
+typedef struct lrcn_conv64_debug {
+    const void *x;        /* bf16, NHWC [N][H][W][64], 16-byte aligned */
+    const void *w;        /* bf16, [Cout][9][64], 16-byte aligned */
+    const float *bias;    /* [Cout] f32, or NULL: zeros (the launch then carries no bias pointer) */
+    void *y;              /* bf16, [N][H][W][Cout]; pool: [N][H/2][W/2][Cout]; 16-byte aligned */
+    int N, H, W, Cout;
+    int relu;
+    int pool;             /* 1: the maximum over each 2x2 window (after bias and ReLU) */
+    int wg_cap;           /* what lrcn_vgg_set_wg_cap gives a forward's layers: >= 8 caps the grid at wg_cap / (Cout / 64) workgroups (at
+                             least 1) per 64-channel chunk, each walking tiles b, b + G, ...; below 8: 256 / (Cout / 64) */
+} lrcn_conv64_debug;
+
+/* launch_conv64 with the context's zero page and stream and the given cap, then waits for the stream.  Afterwards lrcn_debug_route(ctx, 0)
+ * is "conv64".  LRCN_EINVAL on the host, before any launch (y is untouched), when ctx, d, x, w or y is NULL, the context's vgg_dtype is
+ * LRCN_F32, W or H is no multiple of 16 or below 16, Cout no multiple of 64 or below 64, N < 1, N * H * W * 64 does not fit 31 bits, or x, w
+ * or y is not 16-byte aligned; LRCN_EHIP for any HIP error. */
+int lrcn_debug_conv64(lrcn_ctx *ctx, const lrcn_conv64_debug *d);
 
 /* Host copy of the per-layer activation scales sa of the most recent lrcn_vgg_calibrate: out[l] for conv layer l = 0 .. 12; entries below
  * conv2_1 (l = 2), whose outputs stay bf16, are 0.  LRCN_ESTATE when the context is not LRCN_FP8 or not yet calibrated. */

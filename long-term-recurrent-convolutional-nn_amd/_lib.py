@@ -69,6 +69,11 @@ class ConvGemmDebug(C.Structure):   # lrcn_conv_gemm_debug of include/lrcn_gemm_
                 ("wg_cap", C.c_int)]
 
 
+class Conv64Debug(C.Structure):   # lrcn_conv64_debug of include/lrcn_conv_debug.h
+    _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p), ("y", C.c_void_p), ("N", C.c_int), ("H", C.c_int), ("W", C.c_int),
+                ("Cout", C.c_int), ("relu", C.c_int), ("pool", C.c_int), ("wg_cap", C.c_int)]
+
+
 class DecodeDebug(C.Structure):   # lrcn_decode_debug of include/lrcn_decode_debug.h
     _fields_ = [("params", C.POINTER(C.c_void_p)), ("feats", C.c_void_p), ("N", C.c_int), ("per_image", C.c_int), ("steps", C.c_int),
                 ("tokens", C.POINTER(C.c_int32)), ("parents", C.POINTER(C.c_int32)), ("h1", C.c_void_p), ("h2", C.c_void_p),
@@ -323,6 +328,7 @@ CONV_DEBUG_SIGNATURES = {
     "lrcn_debug_fp8_cast": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "lrcn_debug_amax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "lrcn_debug_conv64_f8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "lrcn_debug_conv64": (C.c_int, [C.c_void_p, C.POINTER(Conv64Debug)]),
     "lrcn_debug_fp8_scales": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
 }
 

@@ -861,6 +861,28 @@ int lrcn_debug_conv64_f8(lrcn_ctx *c, const float *x, int W, int H, int N, const
     return LRCN_OK;
 }
 
+// Test entry (include/lrcn_conv_debug.h): conv64.hip's plain kernel on the caller's NHWC bf16 operands under the caller's workgroup cap.
+// No allocation, no conversion; every refusal happens here, before launch_conv64 is called; the stream is drained before the call returns.
+int lrcn_debug_conv64(lrcn_ctx *c, const lrcn_conv64_debug *d) {
+    DeviceGuard dg(c);
+    if (!c || !d) return LRCN_EINVAL;
+    if (!d->x || !d->w || !d->y) FAIL(c, LRCN_EINVAL, "debug_conv64: x, w and y must not be NULL");
+    if (c->vdt != GEMM_T_BF16) FAIL(c, LRCN_EINVAL, "debug_conv64: the context's vgg_dtype must be LRCN_BF16 or LRCN_FP8");
+    if (d->N < 1 || !conv64_eligible(GEMM_T_BF16, 64, d->Cout, d->H, d->W) || (int64_t)d->N * d->H * d->W * 64 >= (1ll << 31))
+        FAIL(c, LRCN_EINVAL, "debug_conv64: W, H multiples of 16, Cout a multiple of 64, N >= 1, N*W*H*64 < 2^31 (N=%d H=%d W=%d Cout=%d)", d->N, d->H,
+             d->W, d->Cout);
+    if ((reinterpret_cast<uintptr_t>(d->x) | reinterpret_cast<uintptr_t>(d->w) | reinterpret_cast<uintptr_t>(d->y)) & 15)
+        FAIL(c, LRCN_EINVAL, "debug_conv64: x, w and y must be 16-byte aligned");
+    // bias == NULL: no bias pointer goes down, and the kernel's bias stage then holds zeros
+    const hipError_t e = launch_conv64(c->stream, d->x, d->w, d->bias, d->y, d->N, d->H, d->W, d->Cout, d->relu != 0, d->pool != 0, c->zero_page, 0.0f,
+                                       d->wg_cap);
+    if (e != hipSuccess)
+        FAIL(c, e == hipErrorInvalidValue ? LRCN_EINVAL : LRCN_EHIP, "debug_conv64 N=%d H=%d W=%d Cout=%d: %s", d->N, d->H, d->W, d->Cout,
+             hipGetErrorString(e));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return LRCN_OK;
+}
+
 int lrcn_debug_fp8_scales(lrcn_ctx *c, float out[13]) {
     if (!c || !out) return LRCN_EINVAL;
     if (!c->vgg_fp8 || !c->fp8_ready) FAIL(c, LRCN_ESTATE, "debug_fp8_scales: needs a vgg_dtype = LRCN_FP8 context after lrcn_vgg_calibrate");

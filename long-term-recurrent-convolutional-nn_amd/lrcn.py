@@ -1132,6 +1132,24 @@ def debug_conv_gemm(ctx, dtype, x, w, y, N, H, W, Cin, Cout, ldc, bias=None, rel
     return debug_route(ctx, 0)
 
 
+def debug_conv64(ctx, x, w, y, N, H, W, Cout, bias=None, relu=False, pool=False, wg_cap=0):
+    """One 3x3 convolution of 64 input channels (+ bias) (ReLU) (2x2 maximum) on conv64.hip's halo-patch kernel, on the caller's device
+    operands (lrcn_debug_conv64, include/lrcn_conv_debug.h): x bfloat16 NHWC [N][H][W][64], w bfloat16 [Cout][9][64], y bfloat16
+    [N][H][W][Cout] (pooled: [N][H/2][W/2][Cout]), bias float32 or None; wg_cap as lrcn_vgg_set_wg_cap's.  Device tensors (sub-views welcome:
+    data_ptr() is what goes down) or raw addresses (int / None).  Returns the route that ran (debug_route(ctx, 0))."""
+    def addr(t):
+        if t is None:
+            return None
+        if torch.is_tensor(t):
+            if not t.is_cuda:
+                raise LrcnError("expected a CUDA (HIP) tensor")
+            return C.c_void_p(t.data_ptr())
+        return C.c_void_p(int(t))
+    d = _lib.Conv64Debug(addr(x), addr(w), addr(bias), addr(y), int(N), int(H), int(W), int(Cout), int(bool(relu)), int(bool(pool)), int(wg_cap))
+    ctx._call("lrcn_debug_conv64", C.byref(d))
+    return debug_route(ctx, 0)
+
+
 def debug_decode_steps(ctx, param, feats, per_image, tokens, parents, out=None):
     """The batched decode step on caller-given tokens and parents (lrcn_debug_decode_steps, include/lrcn_decode_debug.h): feats N x 4096 on
     the device, tokens / parents [steps][N * per_image] host ints (row r of step s feeds tokens[s][r] and continues the states row

@@ -49,7 +49,7 @@ def test_conv_debug_binding_declares_exactly_its_header():
     # include/lrcn_conv_debug.h: a test entry beside the ABI -- exported by the library, bound by its own table, absent from lrcn.h
     raw = open(_lib.CONV_DEBUG_HEADER).read()
     txt = re.sub(r"/\*.*?\*/", "", raw, flags=re.S)
-    names = ["lrcn_debug_amax", "lrcn_debug_conv11", "lrcn_debug_conv64_f8", "lrcn_debug_fp8_cast", "lrcn_debug_fp8_scales"]
+    names = ["lrcn_debug_amax", "lrcn_debug_conv11", "lrcn_debug_conv64", "lrcn_debug_conv64_f8", "lrcn_debug_fp8_cast", "lrcn_debug_fp8_scales"]
     assert sorted(set(re.findall(r"\b(lrcn_[a-z0-9_]+)\s*\(", txt))) == sorted(_lib.CONV_DEBUG_SIGNATURES) == names
     header = open(_lib.HEADER).read()
     so = ctypes.CDLL(_lib.LIB_PATH)
