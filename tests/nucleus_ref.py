@@ -58,15 +58,21 @@ def excused(sc):
 
 
 # ------------------------------------------------------------------------------------------------ fixtures by construction
+STAGE_BOUNDARY_V = (15360, 15361)   # at these widths every decisive row's largest share sits in the LAST column: a staged copy of the row that
+#                                     drops its last element loses the row maximum (the n* = 1 rows then draw nothing else)
 GAP = 6e-3           # every prefix share of a decisive row is at least this far from its top_p
 HEAD = 60            # distinct, decreasing head shares, each >= MIN_SHARE; the rest of the mass is spread over the tail
 MIN_SHARE = 0.012
 
 
-def _row_from_shares(shares, T, rng):
-    """z = T log(share) scattered over the columns by a seeded permutation; returns (z f32, perm) with column perm[m] holding rank m."""
+def _row_from_shares(shares, T, rng, top_at=None):
+    """z = T log(share) scattered over the columns by a seeded permutation; returns (z f32, perm) with column perm[m] holding rank m.
+    top_at: the column that holds rank 0 (the permutation's own holder of rank 0 takes that column's rank)."""
     V = shares.shape[0]
     perm = rng.permutation(V)
+    if top_at is not None:
+        j = int(np.nonzero(perm == top_at)[0][0])
+        perm[0], perm[j] = perm[j], perm[0]
     z = np.empty(V, np.float32)
     z[perm] = (float(T) * np.log(shares)).astype(np.float32)
     return z, perm
@@ -89,7 +95,7 @@ def decisive_row(V, T, n_star, rng):
     """(z, top_p, n_star): top_p in the middle of the gap below the intended boundary -- between the shares of the first n_star - 1 and of the
     first n_star columns -- and the gap asserted in float64 on the f32 logits the device will read."""
     sh = head_shares(V, rng, head=min(HEAD, V))
-    z, _ = _row_from_shares(sh, T, rng)
+    z, _ = _row_from_shares(sh, T, rng, top_at=V - 1 if V in STAGE_BOUNDARY_V else None)
     G = nucleus_size(z, T, 0, 1.0)[1]
     top_p = float(np.float32(0.5 * (G[n_star - 1] + G[n_star])))
     assert top_p < 1.0
@@ -169,7 +175,9 @@ def check_draws(z_rows, S, T, top_k, top_p, seed, current, counts=None):
 
 
 # ------------------------------------------------------------------------------------------------ the decisive set of the exact-size test
-DECISIVE_V = (37, 203, 10640, 16411)   # below the thread count and odd; several columns per thread; the production width; unstaged (> 15360)
+# below the thread count and odd; several columns per thread; the production width; the last staged and the first unstaged width (k_sample_nucleus
+# keeps a row of up to 15360 logits in LDS); unstaged
+DECISIVE_V = (37, 203, 10640, 15360, 15361, 16411)
 DECISIVE_T = (1.0, 0.7)
 DECISIVE_S = 4                         # samples per row: every case is one call of S rows of the same logits
 DECISIVE_SEED = 0x5EED0123456789AB

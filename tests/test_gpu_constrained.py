@@ -67,11 +67,8 @@ def check_rows(ctx, z, K, hist, current, banned=(), min_len=0, n=0, label=""):
     return idx, lp
 
 
-@pytest.mark.parametrize("K", [1, 5, 32])
-# V: off the grids of 4 and 32 (Q = 4); the first Q = 8 shape, with a partial last bitmap word; the first Q = 12 shape; the largest one-pass
-# shape (Q = 16); the general form
-@pytest.mark.parametrize("V", [203, 4100, 8196, 16384, 16390])
-def test_kernel_on_given_logits_exact(V, K):
+def given_logits_exact(V, K, plant_last=False):
+    """The body of the two tests below.  plant_last: the two best columns of every row are the row's last two (see the second test)."""
     R = 7
     ctx = logit_ctx()
     rng = np.random.default_rng([V, K])
@@ -79,11 +76,22 @@ def test_kernel_on_given_logits_exact(V, K):
     # normaliser's rounding on either side, so the ranking is (z descending, column ascending)
     z = (rng.integers(-128, 129, size=(R, V)) / 8.0).astype(np.float32)
     bos = np.full((R, 1), BOS, np.int32)
-    top = [int(np.argmax(z[r])) for r in range(R)]
-    check_rows(ctx, z, K, bos, 1, label="no constraint")
+    top = [int(np.argmax(z[r])) for r in range(R)]   # before planting: the word-edge call below bans V - 1 and these, never V - 2
+    if plant_last:
+        mx = z.max(axis=1)
+        z[:, V - 1] = mx + 0.125
+        z[:, V - 2] = mx + 0.25
+        assert float(z.max()) <= 16.25 and np.array_equal(z * 8, np.round(z * 8))   # still multiples of 1/8: the ranking argument holds
+        assert all(V - 2 != t for t in top)
+    idx, _ = check_rows(ctx, z, K, bos, 1, label="no constraint")
+    if plant_last:   # what the host rules give, spelled out: the last slot's two columns lead every row
+        assert all(list(idx[r][:2]) == [V - 2, V - 1][:K] for r in range(R)), idx[:, :2]
     check_rows(ctx, z, K, bos, 1, n=1, min_len=0, label="current 1, n 1")
     check_rows(ctx, z, K, bos, 1, min_len=1, label="current 1, eos banned")
-    check_rows(ctx, z, K, bos, 1, banned=sorted({1, 31, 32, V - 1} | {t for t in top if t != EOS}), label="bans on word edges and every argmax")
+    idx, _ = check_rows(ctx, z, K, bos, 1, banned=sorted({1, 31, 32, V - 1} | {t for t in top if t != EOS}),
+                        label="bans on word edges and every argmax")
+    if plant_last:   # V - 1 banned, V - 2 left: one of the last slot's two columns masked, the other the winner
+        assert all(idx[r][0] == V - 2 and V - 1 not in idx[r] for r in range(R)), idx[:, 0]
     # exactly K columns left: every word but K + 2 kept ones is on the list (nbanned = V - K - current, current = 3), eos falls to min_len and
     # the two history words -- kept ones -- to n = 1
     keep = sorted(int(v) for v in rng.choice(np.arange(1, V), size=K + 2, replace=False))
@@ -95,7 +103,7 @@ def test_kernel_on_given_logits_exact(V, K):
     assert all(sorted(idx[r]) == keep[2:] for r in range(R))
     # eos the argmax: banned while current <= min_len, the winner at current = min_len + 1
     ze = z.copy()
-    ze[:, EOS] = 16.0
+    ze[:, EOS] = float(z.max()) + 0.5 if plant_last else 16.0   # (planted rows reach 16.25)
     h3 = np.array([[BOS, 5, 6]] * R, np.int32)
     idx, _ = check_rows(ctx, ze, K, h3, 2, min_len=2, label="eos argmax, current = min_len")
     assert EOS not in idx
@@ -117,6 +125,29 @@ def test_kernel_on_given_logits_exact(V, K):
     h = np.array([[BOS, 5, -1, 7, V, 5, -1]] * R, np.int32)
     check_rows(ctx, z, K, h, 7, n=2, label="stale tokens, n 2")
     check_rows(ctx, z, K, h, 7, n=1, label="stale tokens, n 1")
+
+
+@pytest.mark.parametrize("K", [1, 5, 32])
+# V: off the grids of 4 and 32 (Q = 4); the first Q = 8 shape, with a partial last bitmap word; the first Q = 12 shape; the largest one-pass
+# shape (Q = 16); the general form
+@pytest.mark.parametrize("V", [203, 4100, 8196, 16384, 16390])
+def test_kernel_on_given_logits_exact(V, K):
+    given_logits_exact(V, K)
+
+
+@pytest.mark.parametrize("K", [1, 32])
+# V: both sides of every boundary of k_constrained_topk_rows' ladder, q = ceil(V / 1024) <= 4 | 8 | 12 (| 16: 16384 | 16390 above).  At
+# V = 1024 Q the last column is thread 255's fourth element of slot Q - 1; at 1024 Q + 1 it is thread 0's first element of slot Q, the only
+# live element of that slot, in a bitmap word of its own.
+@pytest.mark.parametrize("V", [4096, 4097, 8192, 8193, 12288, 12289])
+def test_kernel_on_given_logits_exact_at_the_ladder_boundaries(V, K):
+    """The same calls with the decisive columns in the last slot: z[:, V - 2] and z[:, V - 1] are the row maximum + 0.25 and + 0.125, and the
+    word-edge call bans V - 1.  A rung that drops or mis-masks its last slot fails on the column list.
+
+    A local build (not kept) whose constrained_topk_rows_kernel<8> did not load its last slot failed [8192-1] and [8192-32] at the first
+    call (column 259 for 8190; the list without 8190 and 8191) and passed everything else, test_kernel_on_given_logits_exact included: at
+    V = 4097 and 4100 slot 7 holds no column, and the other widths are other instantiations."""
+    given_logits_exact(V, K, plant_last=True)
 
 
 # ------------------------------------------------------------------------------------------------ 2. end to end, f32, against the reference

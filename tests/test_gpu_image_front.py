@@ -93,6 +93,36 @@ def test_full_vgg_with_average_image_vs_oracle(dtype, tol):
     ctx.close()
 
 
+def test_full_vgg_fp8_with_average_image_vs_oracle():
+    """The fp8 twin of the test above: uint8 source, an average image, the default (fused) first launch -- the one branch of vgg_body that
+    no test ran.  Calibrated on the same two images under the same average image.  Bound: the fp8 path's stated one
+    (test_full_vgg_fp8_vs_oracle: cosine >= 0.99 and relative L2 <= 0.15 per image against the fp32 oracle).  tests/avg_image_case.py's
+    average image makes that bound decisive: the features of the transposed average image lie more than 0.30 from the reference (asserted
+    here and, without a GPU, in tests/test_avg_image_case.py), so a forward within 0.15 of one is not within 0.15 of the other."""
+    import avg_image_case as ac
+    wh = ac.weights()
+    w = ([t.cuda() for t in wh[0]], [t.cuda() for t in wh[1]], (wh[2][0].cuda(), wh[2][1].cuda()), (wh[3][0].cuda(), wh[3][1].cuda()))
+    img, avg = ac.inputs()
+    ref, wrong = ac.features(), ac.features(True)
+    ctx = small_ctx(vgg_dtype=lrcn_amd.LRCN_FP8, max_images=2)
+    L.vgg_load(ctx, *w)
+    L.set_average_image(ctx, avg)
+    imgs = torch.as_tensor(img).cuda()
+    L.vgg_calibrate(ctx, imgs, mean=None)
+    got = L.from_jl(L.convnet_u8(ctx, imgs, mean=None)).copy()
+    routes = L.debug_route(ctx, 1).split(",")
+    ctx.close()
+    assert routes[0] == "conv64-fused11", routes
+    assert np.isfinite(got).all()
+    for n in range(2):
+        assert ac.rel_l2(wrong[n], ref[n]) > ac.SEPARATION, (n, ac.rel_l2(wrong[n], ref[n]))
+        cos = float((got[n] * ref[n]).sum() / (np.linalg.norm(got[n]) * np.linalg.norm(ref[n])))
+        rel = ac.rel_l2(got[n], ref[n])
+        print("fp8 vgg with an average image, image %d: cosine %.5f rel L2 %.4f (transposed average image: %.4f from the reference, %.4f from the device)"
+              % (n, cos, rel, ac.rel_l2(wrong[n], ref[n]), ac.rel_l2(got[n], wrong[n])))
+        assert cos >= 0.99 and rel <= 0.15, (n, cos, rel)
+
+
 def _write_images(tmp_path, ids, rng):
     from PIL import Image
     d = tmp_path / "imgs"

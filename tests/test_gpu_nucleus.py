@@ -54,6 +54,11 @@ def check_logp(z_rows, tok, lp):
 @pytest.mark.parametrize("T", nr.DECISIVE_T)
 @pytest.mark.parametrize("V", nr.DECISIVE_V)
 def test_exact_size_on_decisive_rows(V, T):
+    """V = 15360 | 15361 sit on both sides of the `stage` flag (the row kept in LDS up to 15360 columns); their rows carry the largest share
+    in column V - 1 (nucleus_ref.STAGE_BOUNDARY_V).  A local build (not kept) whose staged copy lost its last element (row_max_stage read
+    it as -inf) failed [15360-1.0] and [15360-0.7] on the n* = 1 row's draw (10953 and 3991 for the host's 15359), [37-*] and [203-*] on
+    the log-probability (2e-3 .. 2.7e-2 > 1.3e-3), and passed [10640-*], where the last column holds 1e-4 of the row, and the unstaged
+    15361 and 16411."""
     ctx, S = small_ctx(), nr.DECISIVE_S
     host = nr.decisive_host_draws(V, T)
     excused = 0

@@ -16,6 +16,7 @@ from oracle import oracle as orc
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import philox_ref as ph  # noqa: E402
+import stage_boundary as sb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -158,6 +159,27 @@ def test_replay_small_f32(n_layers, T, top_k):
     exact, steps = replay(m, feats, res, S, T, top_k, seed, list(range(N * S)), bf16=False)
     assert exact == steps, (exact, steps)
     ctx.close()
+
+
+@pytest.mark.parametrize("T,top_k", sb.DRAWS)
+@pytest.mark.parametrize("V", sb.STAGE_V)
+def test_replay_f32_at_the_stage_boundary(V, T, top_k):
+    """k_sample_rows (the row-kernel route: an f32 context) at the last width whose logits row it stages in LDS and at the first it does
+    not, on tests/stage_boundary.py's model: the last word holds a quarter of every row (tests/test_sample_host.py shows that the host's
+    own sampler draws it).  Every step of every sample must be the host's argmax under the device's own prefix, and the device must have
+    drawn the last word too.
+
+    A local build (not kept) whose staged copy lost its last element (row_max_stage read it as -inf) failed both cases at V = 15360 (top_k
+    0: a drawn word 1.5 below the host's best score; top_k 3: word 15343 drawn, the host's admitted columns 9993, 14720, 15359) and passed
+    both at 15361."""
+    m, feats = sb.model(V), sb.feats()
+    ctx = L.Context(sb.E, sb.H, sb.H, V, max_B=sb.N * sb.S, max_T=2, lstm_dtype=lrcn_amd.LRCN_F32)
+    res = L.sample_batch(ctx, L.model_from_arrays(m.p), L.to_jl(feats), sb.S, sb.NWORD, temperature=T, top_k=top_k, seed=sb.SEED)
+    ctx.close()
+    assert len(res) == sb.N and all(len(img) == sb.S for img in res)
+    exact, steps = replay(m, feats, res, sb.S, T, top_k, sb.SEED, list(range(sb.N * sb.S)), bf16=False)
+    assert exact == steps, (exact, steps)
+    assert any(t == V - 1 for seq, _ in flat(res) for t in seq[1:])
 
 
 @pytest.mark.parametrize("route", ["fused-gumbel", "fused-topk3", "row-kernel"])

@@ -151,6 +151,10 @@ def test_stepwise_route_without_draws_bf16(B):
 # ------------------------------------------------------------------------------------------------ 4. coins and draws
 @pytest.mark.parametrize("name", sorted(sr.CASES))
 def test_every_coin_and_every_draw_from_the_device_logits(name):
+    """The V = 15360 | 15361 cases sit on both sides of k_sched_next_input's `stage` flag, bf16-V16400 runs its unstaged form in bf16; their
+    models give the last word a quarter of every row (sched_ref.LAST_COLUMN_CASES).  A local build (not kept) whose staged copy lost its
+    last element (row_max_stage read it as -inf) failed every staged case -- [f32-V15360-eps1-t1] at its first call (word 7777 drawn for
+    the host's 15359) -- and passed the three unstaged ones."""
     dtype, nl, B, T, E, H, V, eps, temp, row0, mixed, calls = sr.CASES[name]
     m, feats, tokens, lens, seeds = sr.case_inputs(name)
     ctx = L.Context(E, H, H, V, max_B=B, max_T=T, lstm_dtype=BF16 if dtype == "bf16" else F32, n_layers=nl)

@@ -12,6 +12,8 @@ from lrcn_amd import _lib
 from lrcn_amd import lrcn as L
 from oracle import oracle as orc
 
+import score_blocks_case as sc
+
 pytestmark = pytest.mark.gpu
 
 E = H = 1000
@@ -89,9 +91,10 @@ def production():
 
 
 def teardown_module(module):
-    if _production:
-        _production["ctx"].close()
-        _production.clear()
+    for d in (_production, _ride):
+        if d:
+            d["ctx"].close()
+            d.clear()
 
 
 def step_counts(caps):
@@ -116,6 +119,137 @@ def test_f32_matrix_matches_oracle():
     # the same through lrcn_loss with one row: s = -(L + 1) * loss
     lc = -(len(caps[2]) + 1) * orc.loss(m, feats[3:4], np.array(caps[2], np.int32).reshape(-1, 1))
     assert abs(s[3, 2] - lc) <= 1e-5 * (1 + abs(lc))
+
+
+# ------------------------------------------------------------------------------------------------ 1b. every block loop more than once
+def test_f32_every_block_loop_runs_more_than_once_vs_oracle():
+    """score_impl cuts captions and images into blocks of max_B and pair rows into pieces of max_B.  max_B = 8 with 19 images (blocks of 8,
+    8, 3) and 21 captions (8, 8, 5): the second and third iterations of the caption loop (`off[t] + j0` into the step inputs and into P_t)
+    and of the image loop (`U2 + n0 * 4 * H2`, `feats + n0`), 50 pieces of the matrix and 5 of the pairs.  Every one of the 399 pairs against
+    the oracle, test_f32_matrix_matches_oracle's bound; 37 pairs through score_pairs, the corners among them.
+
+    A local build (not kept) whose caption loop read `d_in + off[t]` without `+ j0` failed here at the first pair of a caption outside
+    block 0 (image 0, caption 12: -26.56923 against -26.57141, 2.2e-3 > 2.8e-4); every score test before this one passed it."""
+    m = small_model()
+    N, M = 19, 21
+    lens = np.array([4, 1, 9, 3, 7, 9, 2, 1, 5, 6, 3, 8, 4, 2, 7, 1, 5, 9, 6, 3, 8])
+    assert len(lens) == M and lens.min() == 1 and lens.max() == 9 and len(set(lens.tolist())) < M
+    caps = captions_of(M, 203, 15, lens)
+    feats = feats_of(N, 16)
+    ctx = L.Context(64, 64, 64, 203, max_B=8, lstm_dtype=lrcn_amd.LRCN_F32)
+    param = L.model_from_arrays(m.p)
+    fj = L.to_jl(feats)
+    s = L.score_matrix(ctx, param, fj, caps)
+    rng = np.random.default_rng(17)
+    pi, pc = rng.integers(0, N, size=37), rng.integers(0, M, size=37)
+    pi[:4], pc[:4] = [0, N - 1, 5, 11], [M - 1, 0, 0, M - 1]
+    assert {0, N - 1} <= set(pi.tolist()) and {0, M - 1} <= set(pc.tolist())
+    sp = L.score_pairs(ctx, param, fj, caps, pi, pc)
+    ctx.close()
+    assert s.shape == (N, M) and sp.shape == (37,)
+    ref = oracle_scores(m, feats, caps, [(n, c) for n in range(N) for c in range(M)])
+    assert len(ref) == 399
+    gap = max(abs(s[n, c] - v) / (1 + abs(v)) for (n, c), v in ref.items())
+    print("f32, max_B 8: 399 pairs, max |gap| / (1 + |s|) = %.3g" % gap)
+    for (n, c), v in ref.items():
+        assert abs(s[n, c] - v) <= 1e-5 * (1 + abs(v)), (n, c, s[n, c], v)
+    for q, (n, c) in enumerate(zip(pi.tolist(), pc.tolist())):
+        v = ref[(n, c)]
+        assert abs(sp[q] - v) <= 1e-5 * (1 + abs(v)), (q, n, c, sp[q], v)
+
+
+# ------------------------------------------------------------------------------------------------ 1c. bf16: the caption-side cell epilogue
+RA_LONG, RA_SHORT, RA_N, RA_P = sc.N_LONG, len(sc.SHORT_LENS), sc.N, sc.P   # 40, 260, 260, 520
+_ride = {}
+
+
+def ride_along():
+    """tests/score_blocks_case.py -- edge68 at V = 300 (H = 68, every route predicate accepts), a model in which the fed word matters -- on
+    a bf16 context of max_B = 256; 300 captions, 40 of length 6 and 260 of lengths 1 .. 5; 260 images; 520 pairs in which every caption
+    and every image occurs.  score_impl then runs (tests/test_score_blocks_case.py restates the plan on the CPU)
+      caption block 0   256 captions (the 40 long ones first) through decode_gates_epi with the token table gathered by `gx_idx = tok`:
+                        256, then fewer active rows, 40 at the last step -- up to 216 rows ride along, reading indices past the step's own
+      caption block 1   44 captions of one and two words: table gather + GEMM + cell kernel
+      image blocks      256 and 4
+      pieces            256 and 256 pair rows (cell epilogue + record epilogue, shrinking below 256 active rows) and 8 (GEMM + cell kernel,
+                        f32 logits + k_softmax_xent)
+    Returns the shared context and inputs (and, once the first test has run, its scores)."""
+    if not _ride:
+        c, m = sc.case(), sc.model()
+        ctx = L.Context(m.E, m.H1, m.H2, sc.V, max_B=sc.MAX_B, max_T=2, lstm_dtype=lrcn_amd.LRCN_BF16, n_layers=m.n_layers)
+        _ride.update(m=m, ctx=ctx, param=L.model_from_arrays(m.p), feats=c.feats, caps=c.caps, pi=c.pi, pc=c.pc, H=m.H1, V=sc.V)
+    return _ride
+
+
+def trace_lines(err):
+    """[(M, N, K)] of LRCN_TRACE_ROUTES' lines: the contractions that went through the router (the cell-epilogue and record-epilogue GEMMs
+    are launched directly and print nothing)."""
+    out = []
+    for line in err.splitlines():
+        if line.startswith("gemm M="):
+            f = line.split()
+            out.append(tuple(int(x.split("=")[1]) for x in f[1:4]))
+    return out
+
+
+def test_bf16_caption_side_epilogue_with_ride_along_rows_vs_emulating_oracle(monkeypatch, capfd):
+    """The call of ride_along() against the bf16-emulating oracle, all 520 pairs, test_bf16_production_matches_emulating_oracle's bound.
+
+    The route: lrcn_debug_route names the call's last contraction only, and LRCN_TRACE_ROUTES prints the routed GEMMs, not the two epilogue
+    launches.  So the trace shows the routes by what is absent: a gate GEMM (N = 4 H = 272) of 256 rows besides the image table's, or a
+    logits GEMM (N = V) of more than 8, would be the GEMM + cell route in caption block 0 or in the 256-row pieces.
+
+    A local build (not kept) whose caption loop read `d_in + off[t]` without `+ j0` PASSED a first version of this test, whose model was
+    width_cases.decode_model as it stands: there the fed word moves a score by a hundredth of this bound.  Hence the rescaled model of
+    tests/score_blocks_case.py, at which the same misread lies 3.5 bounds away in the median (tests/test_score_blocks_case.py, on the
+    CPU) and the same wrong build fails here (pair 12, image 3, caption 179: -36.111 against -32.807, 3.30 > 0.71)."""
+    R = ride_along()
+    monkeypatch.setenv("LRCN_TRACE_ROUTES", "1")
+    capfd.readouterr()
+    s = L.score_pairs(R["ctx"], R["param"], L.to_jl(R["feats"]), R["caps"], R["pi"], R["pc"])
+    err = capfd.readouterr().err
+    monkeypatch.delenv("LRCN_TRACE_ROUTES")
+    R["scores"] = s
+    assert s.shape == (RA_P,) and np.isfinite(s).all()
+    gemms = trace_lines(err)
+    gates = sorted(g[0] for g in gemms if g[1] == 4 * R["H"])
+    logits = sorted(g[0] for g in gemms if g[1] == R["V"])
+    # routed GEMMs of 4 H columns: the token table (V rows), the image table (256 and 4), caption block 1's two recurrent steps (44
+    # captions, 36 of them of two words) and the last piece's three (8 pairs of one-word captions: P_0; P_1 and h2).  Nothing of 256 rows
+    # besides the image table: caption block 0 and the two 256-row pieces ran the cell epilogue.  Logits: the last piece's two steps.
+    assert gates == sorted([R["V"], 256, RA_N - 256, 44, 36, 8, 8, 8]), gates
+    assert logits == [8, 8], logits
+    pairs = list(zip(R["pi"].tolist(), R["pc"].tolist()))
+    ref = oracle_scores(R["m"], R["feats"], R["caps"], pairs, bf16=True)
+    gap = 0.0
+    for q, (n, c) in enumerate(pairs):
+        v = ref[(n, c)]
+        gap = max(gap, abs(s[q] - v) / (1 + abs(v)))
+    print("bf16, max_B 256: %d pairs, max |gap| / (1 + |s|) = %.3g" % (RA_P, gap))
+    for q, (n, c) in enumerate(pairs):
+        v = ref[(n, c)]
+        assert abs(s[q] - v) <= 5e-2 + 2e-2 * abs(v), (q, n, c, s[q], v)
+
+
+def test_ride_along_rows_cannot_reach_active_rows_bit_exact():
+    """The same call twice on the same context; the second with other (valid) word ids in the 260 short captions, lengths and pairs as they
+    were.  A long caption's rows share their launches with the short ones' rows -- active at first, riding along once they have ended -- and
+    must not see them: the scores of every pair of a long caption are the same bits.  (The call's GEMMs take their ordered forms.)"""
+    R = ride_along()
+    fj = L.to_jl(R["feats"])
+    a = R.get("scores")
+    if a is None:
+        a = L.score_pairs(R["ctx"], R["param"], fj, R["caps"], R["pi"], R["pc"])
+    rng = np.random.default_rng(44)
+    caps2 = [list(c) if len(c) == 6 else [3 + (int(w) - 3 + int(rng.integers(1, R["V"] - 3))) % (R["V"] - 3) for w in c] for c in R["caps"]]
+    assert all(len(x) == len(y) and all(3 <= w < R["V"] for w in x) for x, y in zip(caps2, R["caps"]))
+    assert all((x == list(y)) == (len(y) == 6) for x, y in zip(caps2, R["caps"]))
+    b = L.score_pairs(R["ctx"], R["param"], fj, caps2, R["pi"], R["pc"])
+    long_pair = np.array([len(R["caps"][c]) == 6 for c in R["pc"]])
+    assert long_pair.sum() >= RA_LONG and (~long_pair).sum() >= RA_SHORT
+    assert np.asarray(a, np.float32)[long_pair].tobytes() == np.asarray(b, np.float32)[long_pair].tobytes(), \
+        np.abs(np.asarray(a) - np.asarray(b))[long_pair].max()
+    assert (np.asarray(a)[~long_pair] != np.asarray(b)[~long_pair]).any()
 
 
 # ------------------------------------------------------------------------------------------------ 2. bf16, fused route, production width

@@ -450,6 +450,34 @@ def test_capped_persistent_conv_grids_are_bit_identical(vgg_setup):
         ctx.close()
 
 
+def test_pulled_tiles_under_a_cap_are_bit_identical(vgg_setup, monkeypatch):
+    """LRCN_DYN_TILES=1 under a cap: the workgroups of gemm8p_kernel PULL their tiles from eight per-XCD queues (atomic claims, the claimed
+    id handed to the other waves through a per-workgroup global slot) instead of walking static shares.  An opt-in knob, measured and
+    left off -- and until now run by no test.  Which workgroup computes a tile does not enter its arithmetic: for bf16 and fp8, 4 images,
+    caps 8 and 224, the features are the bits of the uncapped forward of the same context, on the same routes as with the knob unset."""
+    w, img, x, ref = vgg_setup
+    imgs = torch.as_tensor(np.concatenate([img, img[::-1]])).cuda()
+    for dt in (lrcn_amd.LRCN_BF16, lrcn_amd.LRCN_FP8):
+        ctx = small_ctx(dt, max_images=4)
+        L.vgg_load(ctx, *w)
+        if dt == lrcn_amd.LRCN_FP8:
+            L.vgg_calibrate(ctx, imgs)
+        base = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+        assert np.isfinite(base).all() and (base != 0).any()
+        for cap in (8, 224):
+            L.vgg_set_wg_cap(ctx, cap)
+            walked = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+            routes = L.debug_route(ctx, 1)
+            monkeypatch.setenv("LRCN_DYN_TILES", "1")
+            pulled = L.from_jl(L.convnet_u8(ctx, imgs)).copy()
+            pulled_routes = L.debug_route(ctx, 1)
+            monkeypatch.delenv("LRCN_DYN_TILES")
+            assert pulled_routes == routes and any(r.startswith("8p") for r in routes.split(",")), (cap, routes, pulled_routes)
+            np.testing.assert_array_equal(walked, base)
+            np.testing.assert_array_equal(pulled, base)
+        ctx.close()
+
+
 def test_config2_end_to_end_fp32_images_to_loss(vgg_setup):
     # BASELINE configs[1] composed end to end in fp32 on the parity scale: uint8 crops -> VGG-16 -> fc7 (exact-fp32 MFMA)
     # -> LSTM-512 loss and gradients, against the CPU oracle run on the same crops (features and loss from the oracle's

@@ -107,6 +107,23 @@ def test_decisive_fixture_gaps_and_excused_draws():
     assert exc < 0.01 * draws, (exc, draws)
 
 
+def test_stage_boundary_rows_put_their_mass_in_the_last_column():
+    """V = 15360 | 15361, the last staged and the first unstaged width of k_sample_nucleus: every decisive row's largest share is column
+    V - 1, and at each (V, T) the host draws that column -- all S draws of the n* = 1 row, which admits nothing else, and some of the wider
+    rows'.  A device copy of the row that stops at V - 1 cannot give these draws."""
+    assert set(nr.STAGE_BOUNDARY_V) <= set(nr.DECISIVE_V) and nr.STAGE_BOUNDARY_V == (15360, 15361)
+    for V in nr.STAGE_BOUNDARY_V:
+        for T in nr.DECISIVE_T:
+            last = 0
+            for (z, top_p, n), (toks, ex) in zip(nr.decisive_cases(V, T), nr.decisive_host_draws(V, T)):
+                assert int(np.argmax(z)) == V - 1 and (z[:V - 1] < z[V - 1]).all()
+                if n == 1:
+                    assert (toks == V - 1).all() and not ex.any()
+                last += int((toks == V - 1).sum())
+            print("V %d T %.1f: %d host draws of column V - 1" % (V, T, last))
+            assert last >= nr.DECISIVE_S
+
+
 def test_tie_and_combination_fixtures():
     for V in (203, 10640):
         rng = np.random.default_rng([V, 7])

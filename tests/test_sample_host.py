@@ -77,3 +77,20 @@ def test_sample_batch_is_exported_and_bound():
     assert L.lrcn_sample_batch.argtypes == _lib.SAMPLE_SIGNATURES["lrcn_sample_batch"][1]
     hdr = open(os.path.join(os.path.dirname(HERE), "include", "lrcn_sample.h")).read()
     assert "int lrcn_sample_batch(" in hdr and '#include "lrcn.h"' in hdr
+
+
+def test_stage_boundary_fixture_draws_the_last_column():
+    """tests/stage_boundary.py, the fixture of test_gpu_sample.py::test_replay_f32_at_the_stage_boundary: at V = 15360 and 15361 and both
+    draw settings, the last word holds between 0.1 and 0.5 of every row the host sampler reads, and the host draws it at least once."""
+    import stage_boundary as sb
+    assert sb.STAGE_V == (15360, 15361)
+    for V in sb.STAGE_V:
+        for T, top_k in sb.DRAWS:
+            res = sb.host_samples(V, T, top_k)
+            assert len(res) == sb.N * sb.S
+            shares = [p for _, sh in res for p in sh]
+            last = sum(int(t == V - 1) for seq, _ in res for t in seq[1:])
+            print("V %d T %.1f top_k %d: p(V - 1) in [%.3f, %.3f], %d of %d host draws are column V - 1"
+                  % (V, T, top_k, min(shares), max(shares), last, len(shares)))
+            assert sb.LAST_SHARE[0] <= min(shares) and max(shares) <= sb.LAST_SHARE[1]
+            assert last >= 1

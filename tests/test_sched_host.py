@@ -129,3 +129,30 @@ def test_seeded_cases_hold_enough_draws_and_few_near_ties(name):
     assert near <= sr.EXCUSED_SHARE * draws
     if temp == 0:
         assert near == 0
+
+
+def test_input_seeds_of_the_first_five_cases_are_their_old_ranks():
+    first = ["bf16-B48-eps.5-t1", "f32-1layer-eps1-t1-row1000", "f32-V16400-eps1-t1", "f32-eps.5-t1", "f32-eps1-t0-row1000"]
+    assert first == sorted(first) and [sr._INPUT_SEED[n] for n in first] == list(range(5))
+    assert set(sr._INPUT_SEED) == set(sr.CASES) and len(set(sr._INPUT_SEED.values())) == len(sr.CASES)
+
+
+@pytest.mark.parametrize("name", sr.LAST_COLUMN_CASES)
+def test_last_column_cases_draw_the_last_column(name):
+    """The cases on both sides of k_sched_next_input's staging boundary (and the unstaged bf16 one): the last word holds between 0.1 and
+    0.5 of every logits row the draws read, and the host simulation draws it -- about a quarter of the case's draws."""
+    dtype, nl, B, T, E, H, V, eps, temp, row0, mixed, calls = sr.CASES[name]
+    m, feats, tokens, lens, seeds = sr.case_inputs(name)
+    assert (V in (15360, 15361)) == (dtype == "f32") and eps == 1.0 and temp == 1.0
+    lo, hi = sr.LAST_COLUMN_SHARE
+    last = draws = 0
+    for seed in seeds:
+        fed, logits, fire, _ = sr.simulate(m, feats, tokens, lens, eps, temp, seed, row0)
+        z = logits[:T].astype(np.float64)          # the rows of steps 0 .. T - 1 decide inputs 1 .. T
+        p = np.exp(z - z.max(axis=2, keepdims=True))
+        share = p[:, :, V - 1] / p.sum(axis=2)
+        assert lo <= share.min() and share.max() <= hi, (name, share.min(), share.max())
+        draws += int(fire.sum())
+        last += int((fed[fire] == V - 1).sum())
+    print(name, "draws", draws, "of column V - 1:", last)
+    assert last >= 1 and draws >= sr.MIN_DRAWS
