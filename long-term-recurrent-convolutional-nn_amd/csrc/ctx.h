@@ -138,6 +138,7 @@ struct lrcn_ctx {
     // the general form (V > 16384); one device buffer, grown to the largest call's need, freed by lrcn_destroy
     void *cn_arena = nullptr;
     size_t cn_bytes = 0;
+    float *ens_mix = nullptr;   // include/lrcn_ensemble.h, lazily on a leader's first call: the mixture rows [maxB][ldV]
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;
     size_t sc_bytes = 0;

@@ -1,12 +1,13 @@
-// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_constrain.h, lrcn_score.h): the batched decode's routes,
+// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_constrain.h, lrcn_ensemble.h, lrcn_score.h): the batched decode's routes,
 // tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams (and their
-// constrained form, lrcn_constrain.h) and caption scoring;
+// constrained form, lrcn_constrain.h, and their ensemble form, lrcn_ensemble.h) and caption scoring;
 // the step's test entry (lrcn_decode_debug.h).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 #include "../../include/lrcn_constrain.h"
+#include "../../include/lrcn_ensemble.h"
 #include "../../include/lrcn_decode_debug.h"
 #include "../../include/lrcn_nbest.h"
 #include "../../include/lrcn_diverse.h"
@@ -885,8 +886,26 @@ static void constrained_topk_rows(lrcn_ctx *c, const float *logits, int64_t ld, 
 // of diverse.hip.
 // cons != NULL (include/lrcn_constrain.h; its entry point passes NULL for an empty set): the record epilogue is off, as for a nucleus call
 // of sample_impl, the step leaves f32 logits, and constrained_topk_rows on them and the histories in bs_seq takes topk_rows' place.
+// ens != NULL (include/lrcn_ensemble.h; its entry point has checked the members): c and p are member 0, the leader.  Every member runs the
+// decode -- begin and step, f32 logits -- in its own context on its own route, one launch mixes their st_logits into the leader's ens_mix,
+// and from there on the call is the constrained one on the leader (an empty constraint set if cons == NULL) with the mixture for logits.
+// The other members get the leader's parents and next tokens by device copies behind the bookkeeping kernel.
+static_assert(kEnsembleMax == LRCN_ENSEMBLE_MAX, "EnsembleMixArgs holds LRCN_ENSEMBLE_MAX members");
+struct Ensemble {
+    int M;
+    lrcn_ctx *const *ctx;
+    const float *const *const *p;
+    float w[LRCN_ENSEMBLE_MAX];   // normalised
+    bool log_mean;
+};
+// a failure inside member m's context, told where the caller looks: the leader's last error
+static int member_fail(lrcn_ctx *c, const lrcn_ctx *cm, int m, int r) {
+    if (cm != c) c->err = "ensemble member " + std::to_string(m) + ": " + cm->err;
+    return r;
+}
 static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
-                          int32_t *out_tokens, int *out_len, float *out_logp, float *out_score, const lrcn_constraints *cons = nullptr) {
+                          int32_t *out_tokens, int *out_len, float *out_logp, float *out_score, const lrcn_constraints *cons = nullptr,
+                          const Ensemble *ens = nullptr) {
     if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
     if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
     if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d must be in [1, max_B = %d]", N, K, c->maxB);
@@ -903,10 +922,27 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     if ((r = nbest_alloc(c))) return r;
     if (diverse && !c->dv_done) DALLOC(c, c->dv_done, sizeof(int32_t) * (size_t)c->maxB);
     if (cons && (r = constraints_upload(c, bits, 0, nullptr))) return r;
-    ConstrainArgs ca{reinterpret_cast<const uint32_t *>(c->cn_arena), nullptr, Lh, 0, cons ? cons->min_len : 0, cons ? cons->no_repeat_ngram : 0, LRCN_EOS};
-    DecodeRoute rt = decode_route(c, R, K);
-    if (cons) rt.smax = false;
-    if ((r = decode_begin(c, p, feats, N, K, rt))) return r;
+    if (ens && !c->ens_mix) DALLOC(c, c->ens_mix, sizeof(float) * (size_t)c->maxB * c->ldV);
+    ConstrainArgs ca{cons ? reinterpret_cast<const uint32_t *>(c->cn_arena) : nullptr, nullptr, Lh, 0, cons ? cons->min_len : 0,
+                     cons ? cons->no_repeat_ngram : 0, LRCN_EOS};
+    // the members of the decode: the context itself, or the ensemble's (member 0 is c)
+    const int M = ens ? ens->M : 1;
+    lrcn_ctx *const one_c[1] = {c};
+    const float *const *const one_p[1] = {p};
+    lrcn_ctx *const *mc = ens ? ens->ctx : one_c;
+    const float *const *const *mp = ens ? ens->p : one_p;
+    const bool f32_logits = cons || ens;   // the top-K follows the step, from f32 logits
+    DecodeRoute rt[LRCN_ENSEMBLE_MAX];
+    EnsembleMixArgs mix{};
+    mix.M = M;
+    for (int m = 0; m < M; ++m) {
+        rt[m] = decode_route(mc[m], R, K);
+        if (f32_logits) rt[m].smax = false;
+        if ((r = decode_begin(mc[m], mp[m], feats, N, K, rt[m]))) return member_fail(c, mc[m], m, r);
+        mix.z[m] = mc[m]->st_logits;
+        mix.ld[m] = mc[m]->ldV;
+        mix.w[m] = ens ? ens->w[m] : 1.0f;
+    }
     HIPCHK(c, hipMemsetAsync(c->bs_ndone, 0, sizeof(int32_t), st));
     DiverseState ds{};
     NbestState &ns = ds.nb;
@@ -920,19 +956,23 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     // histories = [bos], cum 0, next input = bos, one live slot (per group), empty pools
     if (diverse) k_diverse_init(st, ds, N, LRCN_BOS);
     else k_nbest_init(st, ns, N, LRCN_BOS);
+    for (int m = 1; m < M; ++m)   // the first step's input tokens of the other members
+        HIPCHK(c, hipMemcpyAsync(mc[m]->bs_last, c->bs_last, sizeof(int32_t) * R, hipMemcpyDeviceToDevice, st));
     DecodeTail tail{};   // log-probability top-K (in the logits GEMM's epilogue + merge on the record route)
     tail.kind = DecodeTail::TOPK;
     tail.K = K;
     tail.logp = true;
-    tail.records = rt.smax;
-    if (cons) tail = DecodeTail{};   // LOGITS: the top-K follows the step, from st_logits
+    tail.records = rt[0].smax;
+    if (f32_logits) tail = DecodeTail{};   // LOGITS: the top-K follows the step, from st_logits
     int cur = 0;
     for (int current = 1; current <= nword + 1; ++current) {
-        if ((r = decode_step(c, p, R, rt, current, tail))) return r;
-        if (cons) {
+        for (int m = 0; m < M; ++m)
+            if ((r = decode_step(mc[m], mp[m], R, rt[m], current, tail))) return member_fail(c, mc[m], m, r);
+        if (ens) k_ensemble_mix_rows(st, mix, ens->log_mean, R, c->V, c->ens_mix, c->ldV);
+        if (f32_logits) {
             ca.hist = c->bs_seq[cur];
             ca.current = current;
-            constrained_topk_rows(c, c->st_logits, c->ldV, R, c->V, K, ca, c->st_prob, c->st_topi, c->st_topv);
+            constrained_topk_rows(c, ens ? c->ens_mix : c->st_logits, c->ldV, R, c->V, K, ca, c->st_prob, c->st_topi, c->st_topv);
         }
         ns.seq_in = c->bs_seq[cur];
         ns.seq_out = c->bs_seq[cur ^ 1];
@@ -941,12 +981,18 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
         if (diverse) k_diverse_update(st, c->st_topi, c->st_topv, ds, N);
         else k_nbest_update(st, c->st_topi, c->st_topv, ns, N);
         cur ^= 1;
-        if (!rt.epi) follow_parents(c, R);
+        for (int m = 0; m < M; ++m) {
+            if (m > 0) {   // the leader's parents and next tokens: what every member's next step continues from
+                HIPCHK(c, hipMemcpyAsync(mc[m]->st_parent, c->st_parent, sizeof(int32_t) * R, hipMemcpyDeviceToDevice, st));
+                HIPCHK(c, hipMemcpyAsync(mc[m]->bs_last, c->bs_last, sizeof(int32_t) * R, hipMemcpyDeviceToDevice, st));
+            }
+            if (!rt[m].epi) follow_parents(mc[m], R);
+        }
         bool done = false;   // every image finished early?
         if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
         if (done) break;
     }
-    KCHK(c, cons ? "beam_constrained_batch" : diverse ? "beam_diverse_batch" : "beam_nbest_batch");
+    KCHK(c, ens ? "beam_ensemble_batch" : cons ? "beam_constrained_batch" : diverse ? "beam_diverse_batch" : "beam_nbest_batch");
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, R, Lh, out_tokens, out_len, out_logp, c->nb_res_score, out_score);
 }
 
@@ -973,6 +1019,74 @@ int lrcn_beam_constrained_batch(lrcn_ctx *c, const float *const p[9], const floa
     if (G < 0) FAIL(c, LRCN_EINVAL, "groups G=%d must be >= 0 (0: the n-best beam)", G);
     if (cons && cons->nbanned == 0 && cons->min_len == 0 && cons->no_repeat_ngram == 0) cons = nullptr;   // (a negative field is not empty: rejected below)
     return pool_beam_impl(c, p, feats, N, K, G, G ? lambda : 0.0f, nword, alpha, out_tokens, out_len, out_logp, out_score, cons);
+}
+
+// ---------------------------------------------------------------------------------- ensembles (include/lrcn_ensemble.h, ensemble.hip)
+// M, the weights (NULL: uniform; normalised in double, then rounded, into w) and the mode of both entry points
+static int ensemble_check(lrcn_ctx *c, int M, const float *weights, int mode, float w[LRCN_ENSEMBLE_MAX]) {
+    if (M < 1 || M > LRCN_ENSEMBLE_MAX) FAIL(c, LRCN_EINVAL, "ensemble: M=%d members outside [1, %d]", M, LRCN_ENSEMBLE_MAX);
+    if (mode != LRCN_ENSEMBLE_PROB && mode != LRCN_ENSEMBLE_LOGPROB)
+        FAIL(c, LRCN_EINVAL, "ensemble: mode=%d is neither LRCN_ENSEMBLE_PROB (0) nor LRCN_ENSEMBLE_LOGPROB (1)", mode);
+    double sum = 0.0;
+    for (int m = 0; m < M; ++m) {
+        if (weights && !(std::isfinite(weights[m]) && weights[m] > 0.0f))
+            FAIL(c, LRCN_EINVAL, "ensemble: the weight of member %d = %g must be positive and finite", m, (double)weights[m]);
+        sum += weights ? (double)weights[m] : 1.0;
+    }
+    for (int m = 0; m < M; ++m) w[m] = (float)((weights ? (double)weights[m] : 1.0) / sum);
+    return LRCN_OK;
+}
+
+int lrcn_beam_ensemble_batch(lrcn_ctx *const ctx[], const float *const *params[], int M, const float *weights, int mode, const float *feats, int N,
+                             int K, int G, float lambda, int nword, float alpha, const lrcn_constraints *cons, int32_t *out_tokens, int *out_len,
+                             float *out_logp, float *out_score) {
+    if (!ctx || !ctx[0]) return LRCN_EINVAL;
+    lrcn_ctx *c = ctx[0];
+    DeviceGuard dg(c);
+    Ensemble ens{};
+    int r = ensemble_check(c, M, weights, mode, ens.w);
+    if (r) return r;
+    if (!params) FAIL(c, LRCN_EINVAL, "null argument");
+    for (int m = 0; m < M; ++m) {
+        if (!ctx[m] || !params[m]) FAIL(c, LRCN_EINVAL, "ensemble member %d: null context or parameter set", m);
+        for (int q = 0; q < m; ++q)
+            if (ctx[q] == ctx[m]) FAIL(c, LRCN_EINVAL, "ensemble member %d: the context of member %d (every member needs its own)", m, q);
+        if (ctx[m]->V != c->V) FAIL(c, LRCN_EINVAL, "ensemble member %d: V=%d, member 0 has V=%d", m, ctx[m]->V, c->V);
+        if (ctx[m]->cfg.device != c->cfg.device)
+            FAIL(c, LRCN_EINVAL, "ensemble member %d: device %d, member 0 is on device %d", m, ctx[m]->cfg.device, c->cfg.device);
+        if (ctx[m]->stream != c->stream) FAIL(c, LRCN_EINVAL, "ensemble member %d: its stream is not member 0's", m);
+        if (N >= 1 && K >= 1 && (int64_t)N * K > ctx[m]->maxB)
+            FAIL(c, LRCN_EINVAL, "ensemble member %d: N*K = %d*%d exceeds its max_B = %d", m, N, K, ctx[m]->maxB);
+    }
+    if (M == 1) return lrcn_beam_constrained_batch(c, params[0], feats, N, K, G, lambda, nword, alpha, cons, out_tokens, out_len, out_logp, out_score);
+    if (G < 0) FAIL(c, LRCN_EINVAL, "groups G=%d must be >= 0 (0: the n-best beam)", G);
+    if (cons && cons->nbanned == 0 && cons->min_len == 0 && cons->no_repeat_ngram == 0) cons = nullptr;
+    ens.M = M;
+    ens.ctx = ctx;
+    ens.p = params;
+    ens.log_mean = mode == LRCN_ENSEMBLE_LOGPROB;
+    return pool_beam_impl(c, params[0], feats, N, K, G, G ? lambda : 0.0f, nword, alpha, out_tokens, out_len, out_logp, out_score, cons, &ens);
+}
+
+int lrcn_ensemble_mix_logits(lrcn_ctx *c, const float *const logits[], const int64_t ld[], int M, const float *weights, int mode, int R, int V,
+                             float *out, int64_t ld_out) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    EnsembleMixArgs a{};
+    int r = ensemble_check(c, M, weights, mode, a.w);
+    if (r) return r;
+    if (!logits || !ld || !out) FAIL(c, LRCN_EINVAL, "null argument");
+    if (R < 1 || V < 1 || ld_out < V) FAIL(c, LRCN_EINVAL, "R=%d, V=%d must be >= 1 and ld_out=%lld >= V", R, V, (long long)ld_out);
+    for (int m = 0; m < M; ++m) {
+        if (!logits[m]) FAIL(c, LRCN_EINVAL, "ensemble member %d: null logits", m);
+        if (ld[m] < V) FAIL(c, LRCN_EINVAL, "ensemble member %d: ld=%lld below V=%d", m, (long long)ld[m], V);
+        a.z[m] = logits[m];
+        a.ld[m] = ld[m];
+    }
+    a.M = M;
+    k_ensemble_mix_rows(c->stream, a, mode == LRCN_ENSEMBLE_LOGPROB, R, V, out, ld_out);
+    KCHK(c, "ensemble_mix_logits");
+    return LRCN_OK;
 }
 
 int lrcn_constrained_topk_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int K, const lrcn_constraints *cons, const int32_t *hist,

@@ -297,6 +297,19 @@ bool k_constrained_topk_rows(hipStream_t st, const float *logits, int64_t ld, in
 // lp[r][v] = -inf for every column v that is not allowed for row r (any V)
 void k_constrain_mask_rows(hipStream_t st, float *lp, int64_t ld, int R, int V, const ConstrainArgs &a);
 
+// ---- ensemble.hip: the mixture row of an ensemble decode step (include/lrcn_ensemble.h) ----
+// The M members' f32 logits z[m] [R][ld[m]] and normalised weights, by value: no pointer table is uploaded.  Entries from M on are not read.
+constexpr int kEnsembleMax = 8;   // LRCN_ENSEMBLE_MAX
+struct EnsembleMixArgs {
+    const float *z[kEnsembleMax];
+    int64_t ld[kEnsembleMax];
+    float w[kEnsembleMax];
+    int M;
+};
+// out[r][v] = the mixture of the members' log-softmax rows (log_mean: the weighted sum of the log-probabilities, else the log of the
+// weighted sum of the probabilities), any R >= 1, V >= 1, ld >= V and alignment; `out` overlaps no input.  One workgroup per row, no atomics.
+void k_ensemble_mix_rows(hipStream_t st, const EnsembleMixArgs &a, bool log_mean, int R, int V, float *out, int64_t ld_out);
+
 // ---- image_kernels.hip: the VGG side (vgg.hip, conv64.hip, conv64f.hip) ----
 // conv weight (3,3,Cin,Cout) column-major f32 -> [Cout][tap = b*3+a][Cin_pad] T (zero padded channels)
 void k_repack_conv_w(hipStream_t st, int dtype, const float *w, int Cin, int Cout, int Cin_pad, void *out);

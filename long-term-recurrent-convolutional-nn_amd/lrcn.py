@@ -800,6 +800,94 @@ def constrained_topk_logits(ctx, logits, K, hist, current, banned=(), min_len=0,
     return idx.cpu().numpy(), lp.cpu().numpy()
 
 
+_ENSEMBLE_MODES = {"prob": 0, "logprob": 1}   # LRCN_ENSEMBLE_PROB / LRCN_ENSEMBLE_LOGPROB
+
+
+def _ensemble_args(M, weights, mode):
+    """-> (float array of M weights or None for uniform, the mode's number); the library checks the values"""
+    if mode not in _ENSEMBLE_MODES:
+        raise LrcnError("ensemble mode %r: 'prob' or 'logprob'" % (mode,))
+    if weights is None:
+        return None, _ENSEMBLE_MODES[mode]
+    w = [float(x) for x in weights]
+    if len(w) != M:
+        raise LrcnError("%d ensemble weights for %d members" % (len(w), M))
+    return (C.c_float * M)(*w), _ENSEMBLE_MODES[mode]
+
+
+def ensemble_mix_logits(ctx, logits_list, weights=None, mode="prob", out=None):
+    """The mixture rows of M members' logits (lrcn_ensemble_mix_logits, include/lrcn_ensemble.h): each member numpy [R][V] f32 or a torch
+    device tensor [R][V] f32 with any row stride >= V and unit column stride -> numpy [R][V] f32.  mode 'prob': the log of the weighted
+    mean of the members' softmax rows; 'logprob': the weighted sum of their log-softmax rows.  Independent of the context's model sizes.
+    out: a device tensor [R][V] f32 of the same kind to write into (default: rows 16 bytes apart)."""
+    dev = "cuda:%d" % ctx.device
+    zs = []
+    for z in logits_list:
+        if not isinstance(z, torch.Tensor):
+            z = torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(dev)
+        if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1:
+            raise LrcnError("ensemble logits: [R][V] float32 with unit column stride")
+        zs.append(z)
+    M = len(zs)
+    if M < 1 or any(z.shape != zs[0].shape for z in zs):
+        raise LrcnError("ensemble logits: at least one member, all of one shape")
+    R, V = zs[0].shape
+    w, md = _ensemble_args(M, weights, mode)
+    if out is None:
+        out = torch.empty((R, (V + 3) // 4 * 4), dtype=torch.float32, device=zs[0].device)[:, :V]   # rows 16 bytes apart
+    elif out.dtype != torch.float32 or tuple(out.shape) != (R, V) or out.stride(1) != 1 or not out.is_cuda:
+        raise LrcnError("ensemble out: a device tensor [R][V] float32 with unit column stride")
+    ptrs = (C.c_void_p * M)(*[z.data_ptr() for z in zs])
+    lds = (C.c_int64 * M)(*[z.stride(0) for z in zs])
+    torch.cuda.synchronize(zs[0].device)   # the uploads have landed whichever stream the context runs on
+    ctx._call("lrcn_ensemble_mix_logits", ptrs, lds, M, w, md, R, V, C.c_void_p(out.data_ptr()), out.stride(0))
+    ctx.sync()
+    return out.cpu().numpy()
+
+
+def beam_ensemble_batch(ctxs, params, feats, beam_width, nword, alpha=0.0, weights=None, mode="prob", banned=(), min_len=0, no_repeat_ngram=0,
+                        groups=0, strength=0.0):
+    """Ensemble beam search (lrcn_beam_ensemble_batch, include/lrcn_ensemble.h): member m is the context ctxs[m] with the model params[m];
+    every step the members' next-word distributions are mixed (mode 'prob': weighted arithmetic mean, 'logprob': weighted geometric mean;
+    weights None: uniform) and beam_constrained_batch's search runs on the mixture.  The members share the vocabulary, the device and the
+    stream and may differ in everything else.  Returns what beam_constrained_batch returns; logp is the mixture's log-likelihood."""
+    M = len(ctxs)
+    if M < 1 or len(params) != M:
+        raise LrcnError("ensemble: %d contexts, %d models" % (M, len(params)))
+    N, K, G, L = feats.shape[0], beam_width, int(groups), nword + 2
+    out = (C.c_int32 * (N * K * L))()
+    n = (C.c_int * (N * K))()
+    lp = (C.c_float * (N * K))()
+    sc = (C.c_float * (N * K))()
+    cons, keep = _constraints(banned, min_len, no_repeat_ngram)
+    w, md = _ensemble_args(M, weights, mode)
+    p9s = [_p9(p) for p in params]
+    hs = (C.c_void_p * M)(*[c._h.value for c in ctxs])
+    ps = (C.c_void_p * M)(*[C.addressof(p) for p in p9s])
+    rc = _lib.lib().lrcn_beam_ensemble_batch(hs, ps, M, w, md, _ptr(feats), N, K, G, float(strength), nword, float(alpha), C.byref(cons), out, n,
+                                             lp, sc)
+    _lib.check(ctxs[0]._h, rc)
+    del keep, p9s
+    toks = np.ctypeslib.as_array(out).reshape(N * K, L).tolist()
+    n, lp, sc = list(n), list(lp), list(sc)
+    if G == 0:
+        return [[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K, (i + 1) * K) if n[r] > 0] for i in range(N)]
+    Kp = K // G
+    return [[[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K + g * Kp, i * K + (g + 1) * Kp) if n[r] > 0] for g in range(G)] for i in range(N)]
+
+
+def ensemble_captions(ctxs, params, feats, index_to_word, beam_width, nword, alpha=0.0, weights=None, mode="prob", banned=(), min_len=0,
+                      no_repeat_ngram=0, groups=0, strength=0.0, normalize=False):
+    """beam_ensemble_batch as caption text: as constrained_captions."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    res = beam_ensemble_batch(ctxs, params, feats, beam_width, nword, alpha, weights, mode, banned, min_len, no_repeat_ngram, groups, strength)
+    if groups == 0:
+        return [[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in entries] for entries in res]
+    return [[[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in grp] for grp in img] for img in res]
+
+
 def _caption(seq, index_to_word):
     words = []
     for t in seq[1:]:

@@ -16,6 +16,8 @@ batch is split by rows over the ranks (same T everywhere, the global batch as no
 `--varlen` batches captions of mixed lengths (padded, masked loss) instead of the reference's equal-length batches: nothing is dropped.
 `--ss_start E` turns scheduled sampling on from epoch E (counted from 0): an input word is, with a probability that grows by `--ss_step`
 every `--ss_every` epochs up to `--ss_max`, drawn on the device from the model's own logits of the step before (include/lrcn_sched.h).
+`--generate N --nbest --loadfile m0.npz --ensemble m1.npz ...` decodes several checkpoints of one vocabulary as one model
+(include/lrcn_ensemble.h).
 `--label_smoothing E` scores every training step against (1 - E) onehot + E / V inside the loss kernels (include/lrcn_smooth.h); it combines
 with `--varlen`, `--ss_start`, `--scst` and `--gclip`, and the per-epoch loss line stays the plain NLL of average_loss.
 `--gpus N` starts the ranks itself from a parent that never touches the GPU; the torchrun form works too.  `--cnn --train --imagedir`
@@ -83,6 +85,12 @@ def build_parser():
                         "hold (their probability is not given to the others: logp stays the model's)")
     p.add_argument("--min_len", type=int, default=0, help="--nbest: a caption does not end before it has this many words (at most --generate)")
     p.add_argument("--no_repeat_ngram", type=int, default=0, help="--nbest: no caption holds the same N words in a row twice (0 = off; 1 = no word twice)")
+    p.add_argument("--ensemble", nargs="+", default=[], metavar="CHECKPOINT",
+                   help="--nbest: ensemble beam search (include/lrcn_ensemble.h) -- further checkpoints of the same vocabulary that decode "
+                        "together with --loadfile, one context each, sized from the checkpoint; the files --nbest / --diverse_groups write")
+    p.add_argument("--ensemble_weights", default="", help="--ensemble: comma-separated positive weights, --loadfile's first (default: uniform)")
+    p.add_argument("--ensemble_mode", choices=["prob", "logprob"], default="prob",
+                   help="--ensemble: mix the members' word distributions by their arithmetic (prob) or geometric (logprob) mean")
     p.add_argument("--retrieval", action="store_true",
                    help="image-caption retrieval (paper section 5.1 / Table 2): score --capnumber images of the --generate split, drawn as --generate "
                         "draws them (a permutation seeded by --seed), against all their captions; R@1/5/10 and Medr both ways, "
@@ -151,6 +159,20 @@ def main(argv=None):
         parser.error("--ban_words / --min_len / --no_repeat_ngram constrain the n-best beam: give --generate N --nbest (without --sample)")
     if o.min_len < 0 or o.no_repeat_ngram < 0 or o.min_len > max(o.generate, 0):
         parser.error("--min_len must be in [0, --generate] and --no_repeat_ngram >= 0")
+    ens_weights = None
+    if o.ensemble and not (o.nbest and o.generate > 0 and o.sample <= 0 and o.loadfile):
+        parser.error("--ensemble decodes several checkpoints with the n-best beam: give --loadfile m0 --generate N --nbest (without --sample)")
+    if o.ensemble_weights:
+        if not o.ensemble:
+            parser.error("--ensemble_weights weighs the members of --ensemble")
+        try:
+            ens_weights = [float(w) for w in o.ensemble_weights.split(",")]
+        except ValueError:
+            parser.error("--ensemble_weights: comma-separated numbers")
+        if len(ens_weights) != 1 + len(o.ensemble):
+            parser.error("--ensemble_weights: %d weights for %d members (--loadfile and --ensemble)" % (len(ens_weights), 1 + len(o.ensemble)))
+        if not all(0.0 < w < float("inf") for w in ens_weights):
+            parser.error("--ensemble_weights must be positive and finite")
     if o.varlen and not o.train:
         raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
     if o.ss_start >= 0 and (not o.train or o.scst):
@@ -233,6 +255,15 @@ def main(argv=None):
     ctx = L.Context(o.embed, H1, H2, V, max_B=max(o.batchsize, (o.sample or o.beam_width) * (gen_chunk if o.generate > 0 or o.retrieval else 1), 10), lstm_dtype=dt, vgg_dtype=vdt,
                     max_images=max(o.batchsize, 256 if o.train else 1) if o.cnn else 0)   # training: room for the crops of several batches per forward
     param = L.initweights(ctx, seed=o.seed if o.seed > 0 else 42) if host_model is None else L.model_from_arrays(host_model)
+    ens_ctxs, ens_params = [ctx], [param]
+    for path in o.ensemble:   # one context per checkpoint, sized from its arrays: Wembed (V, E), b1 (1, 4 H1), Wout (H2, V); no W2: one layer
+        say("Loading ensemble member from", path)
+        m_model, m_vocab, _, _ = fmt.load_checkpoint(path)
+        if m_vocab != vocab:   # the word lists, not only their length: column v must be the same word in every member
+            parser.error("--ensemble: the vocabulary of %s is not that of %s" % (path, o.loadfile))
+        ens_ctxs.append(L.Context(m_model[6].shape[1], m_model[1].shape[1] // 4, m_model[7].shape[0], V, max_B=max(o.beam_width * gen_chunk, 10),
+                                  lstm_dtype=dt, n_layers=2 if m_model[2].size else 1))
+        ens_params.append(L.model_from_arrays(m_model))
     say("LSTM is initialized")
     mean = L.VGG_MEAN
     if o.cnn:
@@ -275,12 +306,20 @@ def main(argv=None):
     def feature_rows(table, ids):
         return L.to_jl(np.stack([table[i].reshape(-1) for i in ids]).astype(np.float32))
 
+    def ensemble_lists(f, groups):   # --nbest --ensemble: every member's context behind one search, constraints and groups included
+        return L.beam_ensemble_batch(ens_ctxs, ens_params, f, o.beam_width, o.generate, o.length_norm, ens_weights, o.ensemble_mode, ban_ids,
+                                     o.min_len, o.no_repeat_ngram, groups=groups, strength=o.diverse_strength)
+
     def nbest_lists(f):     # --nbest, under --ban_words / --min_len / --no_repeat_ngram the constrained beam
+        if o.ensemble:
+            return ensemble_lists(f, 0)
         if constrained:
             return L.beam_constrained_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm, ban_ids, o.min_len, o.no_repeat_ngram)
         return L.beam_nbest_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm)
 
     def diverse_lists(f):   # --nbest --diverse_groups, likewise
+        if o.ensemble:
+            return ensemble_lists(f, o.diverse_groups)
         if constrained:
             return L.beam_constrained_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm, ban_ids, o.min_len, o.no_repeat_ngram,
                                             groups=o.diverse_groups, strength=o.diverse_strength)
