@@ -18,6 +18,7 @@ NBEST_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_nbest.
 DIVERSE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_diverse.h"))  # lrcn_beam_diverse_batch (not in lrcn.h)
 CONSTRAIN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_constrain.h"))  # lrcn_beam_constrained_batch / lrcn_constrained_topk_logits (not in lrcn.h)
 ENSEMBLE_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_ensemble.h"))  # lrcn_beam_ensemble_batch / lrcn_ensemble_mix_logits (not in lrcn.h)
+FORCED_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_forced.h"))  # lrcn_beam_forced_batch / lrcn_forced_topk_logits (not in lrcn.h)
 ACTIVITY_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_activity.h"))  # lrcn_act_* (not in lrcn.h)
 ACT_DROPOUT_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_act_dropout.h"))  # lrcn_act_loss_grad_drop (not in lrcn_activity.h)
 VARLEN_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_varlen.h"))      # lrcn_*_var (not in lrcn.h)
@@ -83,6 +84,10 @@ class DecodeDebug(C.Structure):   # lrcn_decode_debug of include/lrcn_decode_deb
 
 class Constraints(C.Structure):   # lrcn_constraints of include/lrcn_constrain.h
     _fields_ = [("banned", C.POINTER(C.c_int32)), ("nbanned", C.c_int), ("min_len", C.c_int), ("no_repeat_ngram", C.c_int)]
+
+
+class Forced(C.Structure):   # lrcn_forced of include/lrcn_forced.h
+    _fields_ = [("words", C.POINTER(C.c_int32)), ("C", C.c_int), ("A", C.c_int)]
 
 
 class Dropout(C.Structure):
@@ -233,6 +238,14 @@ ENSEMBLE_SIGNATURES = {
                                            C.c_int, C.c_int, C.c_void_p, C.c_int64]),
 }
 
+# name -> (restype, argtypes); exactly the symbols include/lrcn_forced.h declares (bound by lib() as well)
+FORCED_SIGNATURES = {
+    "lrcn_beam_forced_batch": (C.c_int, [C.c_void_p, P9, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(Constraints), C.POINTER(Forced),
+                                         C.POINTER(C.c_int32), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "lrcn_forced_topk_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(Constraints), C.POINTER(C.c_int32),
+                                          C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
 # name -> (restype, argtypes); exactly the symbols include/lrcn_activity.h declares (bound by lib() as well)
 ACTIVITY_SIGNATURES = {
     "lrcn_act_create": (C.c_int, [C.POINTER(ActConfig), C.POINTER(C.c_void_p)]),
@@ -350,7 +363,7 @@ DECODE_DEBUG_SIGNATURES = {
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER, CONSTRAIN_HEADER, ENSEMBLE_HEADER,
+    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER, CONSTRAIN_HEADER, ENSEMBLE_HEADER, FORCED_HEADER,
                                                                                                    ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER, DECODE_DEBUG_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
@@ -371,7 +384,7 @@ def lib():
         # the one this process uses: import torch BEFORE the library so the dynamic linker binds to that instance.
         import torch  # noqa: F401
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + \
+        for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(FORCED_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + list(SMOOTH_SIGNATURES.items()) + \
                 list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()) + list(DECODE_DEBUG_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported

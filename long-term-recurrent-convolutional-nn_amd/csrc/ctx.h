@@ -138,6 +138,10 @@ struct lrcn_ctx {
     // the general form (V > 16384); one device buffer, grown to the largest call's need, freed by lrcn_destroy
     void *cn_arena = nullptr;
     size_t cn_bytes = 0;
+    // include/lrcn_forced.h, lazily on the first forced call: a step's move values [maxB][LRCN_FORCED_MAXSETS * LRCN_FORCED_MAXALT] and row
+    // states [maxB].  The call's word table rides in cn_arena behind the bitmap; the done flags are dv_done, the rest is nb_*.
+    float *fc_move = nullptr;
+    int32_t *fc_state = nullptr;
     float *ens_mix = nullptr;   // include/lrcn_ensemble.h, lazily on a leader's first call: the mixture rows [maxB][ldV]
     // lrcn_score_matrix / lrcn_score_pairs: one device arena, grown to the largest call's need (include/lrcn_score.h), freed by lrcn_destroy
     void *sc_arena = nullptr;

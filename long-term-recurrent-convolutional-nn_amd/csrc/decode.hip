@@ -1,6 +1,6 @@
-// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_constrain.h, lrcn_ensemble.h, lrcn_score.h): the batched decode's routes,
+// decode.hip -- the caption model's decoding (include/lrcn.h, lrcn_sample.h, lrcn_nucleus.h, lrcn_nbest.h, lrcn_diverse.h, lrcn_constrain.h, lrcn_ensemble.h, lrcn_forced.h, lrcn_score.h): the batched decode's routes,
 // tables, begin and step, and on top of them the single-image and batched beam search, sampling, the n-best and diverse beams (and their
-// constrained form, lrcn_constrain.h, and their ensemble form, lrcn_ensemble.h) and caption scoring;
+// constrained form, lrcn_constrain.h, their ensemble form, lrcn_ensemble.h, and the forced-word form, lrcn_forced.h) and caption scoring;
 // the step's test entry (lrcn_decode_debug.h).
 #include <algorithm>
 #include <cmath>
@@ -8,6 +8,7 @@
 
 #include "../../include/lrcn_constrain.h"
 #include "../../include/lrcn_ensemble.h"
+#include "../../include/lrcn_forced.h"
 #include "../../include/lrcn_decode_debug.h"
 #include "../../include/lrcn_nbest.h"
 #include "../../include/lrcn_diverse.h"
@@ -879,6 +880,59 @@ static void constrained_topk_rows(lrcn_ctx *c, const float *logits, int64_t ld, 
     k_topk_rows(c->stream, scratch, ld, R, V, K, idx, val);
 }
 
+// -------------------------------------------------------------------------------------------- forced words (include/lrcn_forced.h)
+static_assert(kForcedMaxSets == LRCN_FORCED_MAXSETS && kForcedMaxAlt == LRCN_FORCED_MAXALT, "ForcedArgs holds the header's limits");
+// The id rules of n_img images' sets words [n_img][C][A] against a vocabulary of V and the ban bitmap `bits`: an id is negative (no word)
+// or in [1, V), occurs once within its image and is not banned.  table: the device form, [n_img][C*A] with -1 for no word.
+static int forced_check(lrcn_ctx *c, const int32_t *words, int n_img, int C, int A, int V, const std::vector<uint32_t> &bits,
+                        std::vector<int32_t> &table) {
+    const int CA = C * A;
+    table.assign((size_t)n_img * CA, -1);
+    for (int n = 0; n < n_img; ++n)
+        for (int q = 0; q < CA; ++q) {
+            const int32_t v = words[(size_t)n * CA + q];
+            if (v < 0) continue;
+            if (v < 1 || v >= V) FAIL(c, LRCN_EINVAL, "forced words: image %d, set %d: id %d outside [1, V=%d)", n, q / A, v, V);
+            if ((bits[v >> 5] >> (v & 31)) & 1u) FAIL(c, LRCN_EINVAL, "forced words: image %d, set %d: id %d is banned", n, q / A, v);
+            for (int o = 0; o < q; ++o)
+                if (table[(size_t)n * CA + o] == v) FAIL(c, LRCN_EINVAL, "forced words: image %d: id %d occurs twice", n, v);
+            table[(size_t)n * CA + q] = v;
+        }
+    return LRCN_OK;
+}
+// the word table behind the bitmap in the constraint arena (constraints_upload has made room at `dst`)
+static int forced_upload(lrcn_ctx *c, const std::vector<int32_t> &table, int32_t *dst) {
+    if (table.empty()) return LRCN_OK;
+    HIPCHK(c, hipMemcpyAsync(dst, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // the host vector is read before it goes out of scope
+    return LRCN_OK;
+}
+// constrained_topk_rows for rows that know their state: the stay proposals, the move values and the states
+static void forced_topk_rows(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int K, const ConstrainArgs &a, const ForcedArgs &f,
+                             float *scratch, int32_t *idx, float *val, float *move, int32_t *state) {
+    if (k_forced_topk_rows(c->stream, logits, ld, R, V, K, a, f, idx, val, move, state)) return;
+    k_log_softmax_rows(c->stream, logits, ld, R, V, scratch, ld);
+    k_forced_mask_rows(c->stream, scratch, ld, R, V, a, f, move, state);
+    k_topk_rows(c->stream, scratch, ld, R, V, K, idx, val);
+}
+// decode_results_to_host for a forced call: the results are in the first K of every image's `per` rows, and the host arrays are [N][K]
+static int forced_results_to_host(lrcn_ctx *c, int N, int K, int per, int Lh, int32_t *out_tok, int *out_len, float *out_logp, float *out_score) {
+    const size_t w_tok = sizeof(int32_t) * (size_t)K * Lh, w_n = sizeof(int32_t) * (size_t)K, nb_tok = w_tok * N, nb_n = w_n * N;
+    int r = pin_reserve(c, nb_tok + 3 * nb_n);
+    if (r) return r;
+    unsigned char *pin = reinterpret_cast<unsigned char *>(c->pin);
+    HIPCHK(c, hipMemcpy2DAsync(pin, w_tok, c->bs_res_tok, sizeof(int32_t) * (size_t)per * Lh, w_tok, N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(pin + nb_tok, w_n, c->bs_res_len, sizeof(int32_t) * (size_t)per, w_n, N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(pin + nb_tok + nb_n, w_n, c->bs_res_p, sizeof(float) * (size_t)per, w_n, N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(pin + nb_tok + 2 * nb_n, w_n, c->nb_res_score, sizeof(float) * (size_t)per, w_n, N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(out_tok, pin, nb_tok);
+    memcpy(out_len, pin + nb_tok, nb_n);
+    if (out_logp) memcpy(out_logp, pin + nb_tok + nb_n, nb_n);
+    if (out_score) memcpy(out_score, pin + nb_tok + 2 * nb_n, nb_n);
+    return LRCN_OK;
+}
+
 // The n-best beam search (include/lrcn_nbest.h): the batched decode of lrcn_beam_search_batch (decode_begin / decode_step on the route
 // decode_route picks, N*K rows) with log-probability top-K (the LOGP forms of the records merge and the rows kernel) and its own per-step
 // bookkeeping (nbest.hip): live slots in log space, a pool of finished hypotheses with length normalisation, the exact early stop.
@@ -890,6 +944,9 @@ static void constrained_topk_rows(lrcn_ctx *c, const float *logits, int64_t ld, 
 // decode -- begin and step, f32 logits -- in its own context on its own route, one launch mixes their st_logits into the leader's ens_mix,
 // and from there on the call is the constrained one on the leader (an empty constraint set if cons == NULL) with the mixture for logits.
 // The other members get the leader's parents and next tokens by device copies behind the bookkeeping kernel.
+// forced != NULL (include/lrcn_forced.h; its entry point has checked C and A and passes NULL for no sets; G = 0, no ensemble): an image owns
+// S = 2^C banks of K rows, the decode runs on N*S*K rows on the route of that row count, forced_topk_rows takes constrained_topk_rows'
+// place and forced.hip's bookkeeping nbest.hip's; the results are gathered from the first K rows of every image.
 static_assert(kEnsembleMax == LRCN_ENSEMBLE_MAX, "EnsembleMixArgs holds LRCN_ENSEMBLE_MAX members");
 struct Ensemble {
     int M;
@@ -905,7 +962,7 @@ static int member_fail(lrcn_ctx *c, const lrcn_ctx *cm, int m, int r) {
 }
 static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int G, float lambda, int nword, float alpha,
                           int32_t *out_tokens, int *out_len, float *out_logp, float *out_score, const lrcn_constraints *cons = nullptr,
-                          const Ensemble *ens = nullptr) {
+                          const Ensemble *ens = nullptr, const lrcn_forced *forced = nullptr) {
     if (!p || !feats || !out_tokens || !out_len) FAIL(c, LRCN_EINVAL, "null argument");
     if (K < 1 || K > 32 || K > c->V) FAIL(c, LRCN_EINVAL, "beam width K=%d must be in [1, min(32, V=%d)]", K, c->V);
     if (N < 1 || (int64_t)N * K > c->maxB) FAIL(c, LRCN_EINVAL, "N*K = %d*%d must be in [1, max_B = %d]", N, K, c->maxB);
@@ -914,14 +971,29 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     const bool diverse = G != 0;
     if (diverse && K % G != 0) FAIL(c, LRCN_EINVAL, "groups G=%d must divide the beam width K=%d", G, K);
     if (diverse && (!std::isfinite(lambda) || lambda < 0.0f)) FAIL(c, LRCN_EINVAL, "lambda=%g must be finite and >= 0", (double)lambda);
-    const int R = N * K, Lh = nword + 2;
+    const int FC = forced ? forced->C : 0, FA = forced ? forced->A : 0, CA = FC * FA, per = K << FC;   // per: the rows of an image
+    if (forced && per > 32) FAIL(c, LRCN_EINVAL, "forced words: 2^C * K = %d * %d rows per image, at most 32", 1 << FC, K);
+    if (forced && (int64_t)N * per > c->maxB) FAIL(c, LRCN_EINVAL, "forced words: N * 2^C * K = %d*%d*%d exceeds max_B = %d", N, 1 << FC, K, c->maxB);
+    if (forced && nword < FC) FAIL(c, LRCN_EINVAL, "forced words: nword=%d is below the number of sets C=%d", nword, FC);
+    const int R = N * per, Lh = nword + 2;
     hipStream_t st = c->stream;
     int r;
     std::vector<uint32_t> bits;
-    if (cons && (r = constraints_check(c, cons, c->V, K, nword, nword, bits))) return r;
+    std::vector<int32_t> table;
+    const lrcn_constraints none{nullptr, 0, 0, 0};
+    if (forced && !cons) cons = &none;   // rule 4 and the moves ride on the constrained path
+    if (cons && (r = constraints_check(c, cons, c->V, K, nword + CA, nword, bits))) return r;
+    if (forced && (r = forced_check(c, forced->words, N, FC, FA, c->V, bits, table))) return r;
     if ((r = nbest_alloc(c))) return r;
-    if (diverse && !c->dv_done) DALLOC(c, c->dv_done, sizeof(int32_t) * (size_t)c->maxB);
-    if (cons && (r = constraints_upload(c, bits, 0, nullptr))) return r;
+    if ((diverse || forced) && !c->dv_done) DALLOC(c, c->dv_done, sizeof(int32_t) * (size_t)c->maxB);
+    if (forced && !c->fc_move) {
+        DALLOC(c, c->fc_move, sizeof(float) * (size_t)c->maxB * kForcedMaxWords);
+        DALLOC(c, c->fc_state, sizeof(int32_t) * (size_t)c->maxB);
+    }
+    float *behind = nullptr;   // the word table's place in the arena
+    if (cons && (r = constraints_upload(c, bits, sizeof(int32_t) * table.size(), &behind))) return r;
+    if (forced && (r = forced_upload(c, table, reinterpret_cast<int32_t *>(behind)))) return r;
+    const ForcedArgs fa{reinterpret_cast<const int32_t *>(behind), FC, FA, per};
     if (ens && !c->ens_mix) DALLOC(c, c->ens_mix, sizeof(float) * (size_t)c->maxB * c->ldV);
     ConstrainArgs ca{cons ? reinterpret_cast<const uint32_t *>(c->cn_arena) : nullptr, nullptr, Lh, 0, cons ? cons->min_len : 0,
                      cons ? cons->no_repeat_ngram : 0, LRCN_EOS};
@@ -936,9 +1008,9 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     EnsembleMixArgs mix{};
     mix.M = M;
     for (int m = 0; m < M; ++m) {
-        rt[m] = decode_route(mc[m], R, K);
+        rt[m] = decode_route(mc[m], R, per);
         if (f32_logits) rt[m].smax = false;
-        if ((r = decode_begin(mc[m], mp[m], feats, N, K, rt[m]))) return member_fail(c, mc[m], m, r);
+        if ((r = decode_begin(mc[m], mp[m], feats, N, per, rt[m]))) return member_fail(c, mc[m], m, r);
         mix.z[m] = mc[m]->st_logits;
         mix.ld[m] = mc[m]->ldV;
         mix.w[m] = ens ? ens->w[m] : 1.0f;
@@ -953,8 +1025,12 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
     ns.lp_max = (float)std::pow((double)(nword + 1), (double)alpha);
     ns.seq_in = c->bs_seq[0];
     ds.done = c->dv_done; ds.G = G; ds.lambda = lambda;
-    // histories = [bos], cum 0, next input = bos, one live slot (per group), empty pools
-    if (diverse) k_diverse_init(st, ds, N, LRCN_BOS);
+    ForcedState fs{};
+    fs.done = c->dv_done; fs.words = fa.words; fs.move = c->fc_move; fs.C = FC; fs.A = FA;
+    fs.nb = ns;
+    // histories = [bos], cum 0, next input = bos, one live slot (per group; of bank 0), empty pools
+    if (forced) k_forced_init(st, fs, N, LRCN_BOS);
+    else if (diverse) k_diverse_init(st, ds, N, LRCN_BOS);
     else k_nbest_init(st, ns, N, LRCN_BOS);
     for (int m = 1; m < M; ++m)   // the first step's input tokens of the other members
         HIPCHK(c, hipMemcpyAsync(mc[m]->bs_last, c->bs_last, sizeof(int32_t) * R, hipMemcpyDeviceToDevice, st));
@@ -972,13 +1048,16 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
         if (f32_logits) {
             ca.hist = c->bs_seq[cur];
             ca.current = current;
-            constrained_topk_rows(c, ens ? c->ens_mix : c->st_logits, c->ldV, R, c->V, K, ca, c->st_prob, c->st_topi, c->st_topv);
+            if (forced) forced_topk_rows(c, c->st_logits, c->ldV, R, c->V, K, ca, fa, c->st_prob, c->st_topi, c->st_topv, c->fc_move, c->fc_state);
+            else constrained_topk_rows(c, ens ? c->ens_mix : c->st_logits, c->ldV, R, c->V, K, ca, c->st_prob, c->st_topi, c->st_topv);
         }
         ns.seq_in = c->bs_seq[cur];
         ns.seq_out = c->bs_seq[cur ^ 1];
         ns.current = current;
         ns.lp_cur = (float)std::pow((double)current, (double)alpha);
-        if (diverse) k_diverse_update(st, c->st_topi, c->st_topv, ds, N);
+        fs.nb = ns;
+        if (forced) k_forced_update(st, c->st_topi, c->st_topv, fs, N);
+        else if (diverse) k_diverse_update(st, c->st_topi, c->st_topv, ds, N);
         else k_nbest_update(st, c->st_topi, c->st_topv, ns, N);
         cur ^= 1;
         for (int m = 0; m < M; ++m) {
@@ -992,7 +1071,8 @@ static int pool_beam_impl(lrcn_ctx *c, const float *const p[9], const float *fea
         if ((current & 3) == 0 && current <= nword && (r = decode_poll_done(c, N, done))) return r;
         if (done) break;
     }
-    KCHK(c, ens ? "beam_ensemble_batch" : cons ? "beam_constrained_batch" : diverse ? "beam_diverse_batch" : "beam_nbest_batch");
+    KCHK(c, forced ? "beam_forced_batch" : ens ? "beam_ensemble_batch" : cons ? "beam_constrained_batch" : diverse ? "beam_diverse_batch" : "beam_nbest_batch");
+    if (forced) return forced_results_to_host(c, N, K, per, Lh, out_tokens, out_len, out_logp, out_score);
     return decode_results_to_host(c, c->bs_res_tok, c->bs_res_len, c->bs_res_p, R, Lh, out_tokens, out_len, out_logp, c->nb_res_score, out_score);
 }
 
@@ -1110,6 +1190,51 @@ int lrcn_constrained_topk_logits(lrcn_ctx *c, const float *logits, int64_t ld, i
     const ConstrainArgs ca{reinterpret_cast<const uint32_t *>(c->cn_arena), hist, ld_hist, current, cons->min_len, cons->no_repeat_ngram, LRCN_EOS};
     constrained_topk_rows(c, logits, ld, R, V, K, ca, scratch, out_idx, out_logp);
     KCHK(c, "constrained_topk_logits");
+    return LRCN_OK;
+}
+
+// include/lrcn_forced.h.  No sets: the constrained call itself.
+int lrcn_beam_forced_batch(lrcn_ctx *c, const float *const p[9], const float *feats, int N, int K, int nword, float alpha,
+                           const lrcn_constraints *cons, const lrcn_forced *forced, int32_t *out_tokens, int *out_len, float *out_logp,
+                           float *out_score) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!forced || forced->C == 0) return lrcn_beam_constrained_batch(c, p, feats, N, K, 0, 0.0f, nword, alpha, cons, out_tokens, out_len, out_logp, out_score);
+    if (forced->C < 0 || forced->C > LRCN_FORCED_MAXSETS || forced->A < 1 || forced->A > LRCN_FORCED_MAXALT)
+        FAIL(c, LRCN_EINVAL, "forced words: C=%d outside [0, %d] or A=%d outside [1, %d]", forced->C, LRCN_FORCED_MAXSETS, forced->A, LRCN_FORCED_MAXALT);
+    if (!forced->words) FAIL(c, LRCN_EINVAL, "forced words: C=%d with a NULL table", forced->C);
+    return pool_beam_impl(c, p, feats, N, K, 0, 0.0f, nword, alpha, out_tokens, out_len, out_logp, out_score, cons, nullptr, forced);
+}
+
+int lrcn_forced_topk_logits(lrcn_ctx *c, const float *logits, int64_t ld, int R, int V, int K, const lrcn_constraints *cons, const int32_t *words,
+                            int C, int A, const int32_t *hist, int64_t ld_hist, int current, int32_t *out_idx, float *out_logp, float *out_move_logp,
+                            int32_t *out_state) {
+    if (!c) return LRCN_EINVAL;
+    DeviceGuard dg(c);
+    if (!logits || !hist || !out_idx || !out_logp || !out_state) FAIL(c, LRCN_EINVAL, "null argument");
+    if (C < 0 || C > LRCN_FORCED_MAXSETS || (C > 0 && (A < 1 || A > LRCN_FORCED_MAXALT)))
+        FAIL(c, LRCN_EINVAL, "forced words: C=%d outside [0, %d] or A=%d outside [1, %d]", C, LRCN_FORCED_MAXSETS, A, LRCN_FORCED_MAXALT);
+    if (C > 0 && (!words || !out_move_logp)) FAIL(c, LRCN_EINVAL, "forced words: C=%d with a NULL table or a NULL out_move_logp", C);
+    if (R < 1 || V < 1 || ld < V || (ld & 3)) FAIL(c, LRCN_EINVAL, "R=%d, V=%d must be >= 1, ld=%lld >= V and a multiple of 4", R, V, (long long)ld);
+    if (K < 1 || K > 32 || K > V) FAIL(c, LRCN_EINVAL, "K=%d must be in [1, min(32, V=%d)]", K, V);
+    if (current < 1 || current > ld_hist || current > LRCN_BEAM_MAXLEN - 1)
+        FAIL(c, LRCN_EINVAL, "current=%d outside [1, min(ld_hist=%lld, %d)]", current, (long long)ld_hist, LRCN_BEAM_MAXLEN - 1);
+    const lrcn_constraints none{nullptr, 0, 0, 0};
+    if (!cons) cons = &none;
+    const int FA = C > 0 ? A : 1, CA = C * FA;
+    std::vector<uint32_t> bits;
+    std::vector<int32_t> table;
+    int r = constraints_check(c, cons, V, K, current - 1 + CA, -1, bits);
+    if (r || (r = forced_check(c, words, R, C, FA, V, bits, table))) return r;
+    const bool general = V > 16384 || (reinterpret_cast<uintptr_t>(logits) & 15);
+    const size_t b_tab = (sizeof(int32_t) * table.size() + 255) & ~(size_t)255;
+    float *behind = nullptr;
+    if ((r = constraints_upload(c, bits, b_tab + (general ? sizeof(float) * (size_t)R * ld : 0), &behind))) return r;
+    if ((r = forced_upload(c, table, reinterpret_cast<int32_t *>(behind)))) return r;
+    const ConstrainArgs ca{reinterpret_cast<const uint32_t *>(c->cn_arena), hist, ld_hist, current, cons->min_len, cons->no_repeat_ngram, LRCN_EOS};
+    const ForcedArgs fa{reinterpret_cast<const int32_t *>(behind), C, FA, 1};
+    forced_topk_rows(c, logits, ld, R, V, K, ca, fa, behind + b_tab / sizeof(float), out_idx, out_logp, out_move_logp, out_state);
+    KCHK(c, "forced_topk_logits");
     return LRCN_OK;
 }
 

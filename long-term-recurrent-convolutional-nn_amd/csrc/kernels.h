@@ -410,3 +410,35 @@ struct DiverseState {
 void k_diverse_init(hipStream_t st, const DiverseState &s, int N, int bos);
 // one step for N images (one workgroup each) from this step's log-probability top-K topi / topv [N*K][K] (the full width); K <= 32
 void k_diverse_update(hipStream_t st, const int32_t *topi, const float *topv, const DiverseState &s, int N);
+
+// ---- forced words (include/lrcn_forced.h): the top-K of a row that knows its state (constrain.hip), the bank bookkeeping (forced.hip) ----
+constexpr int kForcedMaxSets = 3, kForcedMaxAlt = 4, kForcedMaxWords = kForcedMaxSets * kForcedMaxAlt;
+// The word table words [images][C*A] on the device (-1: no word); row r belongs to image r / rows_per_image.
+struct ForcedArgs {
+    const int32_t *words;
+    int C, A, rows_per_image;
+};
+// k_constrained_topk_rows with the forced-word rules: idx / val [R][K] the row's K best STAY columns (allowed by rules 1-4 and no word of a
+// present, unsatisfied set of the row), move [R][C*A] the logp of the row's move words (-inf: absent, satisfied set, or banned by rules
+// 1-3), state [R] the sets the row's history has met.  false: V too large for the register-resident form; then k_log_softmax_rows,
+// k_forced_mask_rows on its output and k_topk_rows.
+bool k_forced_topk_rows(hipStream_t st, const float *logits, int64_t ld, int R, int V, int K, const ConstrainArgs &a, const ForcedArgs &f,
+                        int32_t *idx, float *val, float *move, int32_t *state);
+// the general form's middle step, any V: lp [R][ld] is the rows' log-softmax; gathers move and state as above, then writes -inf over every
+// column that is no stay column
+void k_forced_mask_rows(hipStream_t st, float *lp, int64_t ld, int R, int V, const ConstrainArgs &a, const ForcedArgs &f, float *move,
+                        int32_t *state);
+// The n-best state with nb.K = the width of ONE bank: image n owns S * K rows (S = 2^C banks of K), bank b rows n*S*K + b*K ..; cum,
+// histories, parent and last are per row; img is [N*S] bank records {live slots (a prefix), -, -, -} with the image's pool count in bank
+// 0's .y; the pool, its 2K storage rows and the results use the first K rows of each image; done [N] marks the images whose results are
+// written.  move [N*S*K][C*A]: this step's move values from k_forced_topk_rows.
+struct ForcedState {
+    NbestState nb;
+    int32_t *done;
+    const int32_t *words;
+    const float *move;
+    int C, A;
+};
+void k_forced_init(hipStream_t st, const ForcedState &s, int N, int bos);
+// one step for N images (one workgroup each) from this step's stay proposals topi / topv [N*S*K][K] and s.move; S * K <= 32
+void k_forced_update(hipStream_t st, const int32_t *topi, const float *topv, const ForcedState &s, int N);

@@ -800,6 +800,98 @@ def constrained_topk_logits(ctx, logits, K, hist, current, banned=(), min_len=0,
     return idx.cpu().numpy(), lp.cpu().numpy()
 
 
+def _forced(forced, N):
+    """forced: one list of sets (each a list of alternative token ids) for all N images, or a list of N such lists (None or [] for an
+    image: no sets).  -> (lrcn_forced or None, the array it points to, the N lists of sets)"""
+    forced = list(forced) if forced is not None else []
+    first = next((f for f in forced if f is not None and len(f)), None)   # a set (its first entry an id) or an image's list of sets
+    if first is None or np.isscalar(first[0]):
+        forced = [[f for f in forced if f is not None and len(f)]] * N   # one list of sets for every image
+    elif len(forced) != N:
+        raise LrcnError("forced words: %d lists of sets for %d images" % (len(forced), N))
+    sets = [[[int(v) for v in alt] for alt in (img or [])] for img in forced]
+    Cn = max([len(img) for img in sets] + [0])
+    An = max([len(alt) for img in sets for alt in img] + [1])
+    if Cn == 0:
+        return None, None, sets
+    arr = (C.c_int32 * (N * Cn * An))(*([-1] * (N * Cn * An)))
+    for n, img in enumerate(sets):
+        for c, alt in enumerate(img):
+            for a, v in enumerate(alt):
+                arr[(n * Cn + c) * An + a] = v
+    return _lib.Forced(arr, Cn, An), arr, sets
+
+
+def meets(tokens, sets):
+    """Does a caption (token ids) hold a word of every non-empty set of `sets` (a list of lists of alternative ids)?"""
+    have = set(int(t) for t in tokens)
+    return all(any(int(v) in have for v in alt) for alt in sets if len(alt))
+
+
+def beam_forced_batch(ctx, param, feats, beam_width, nword, alpha=0.0, forced=(), banned=(), min_len=0, no_repeat_ngram=0):
+    """Forced-word beam search (lrcn_beam_forced_batch, include/lrcn_forced.h): the n-best beam under the constraints of
+    beam_constrained_batch whose every returned caption holds a word of each of its image's sets.  forced: one list of sets for all
+    images -- [[dog, dogs], [frisbee]]: "dog" or "dogs", and "frisbee" -- or a list of N such lists; at most 3 sets of at most 4 alternative
+    token ids in [1, V), disjoint within an image and not banned.  An image owns 2^sets * beam_width rows of the decode.  Returns what
+    beam_nbest_batch returns; an image whose sets could not be met within nword words has fewer than beam_width entries, possibly none.
+    With no sets it is beam_constrained_batch, bit for bit."""
+    N, K, L = feats.shape[0], beam_width, nword + 2
+    out = (C.c_int32 * (N * K * L))()
+    n = (C.c_int * (N * K))()
+    lp = (C.c_float * (N * K))()
+    sc = (C.c_float * (N * K))()
+    cons, keep = _constraints(banned, min_len, no_repeat_ngram)
+    fw, keep_words, _ = _forced(forced, N)
+    ctx._call("lrcn_beam_forced_batch", _p9(param), _ptr(feats), N, K, nword, float(alpha), C.byref(cons), C.byref(fw) if fw is not None else None,
+              out, n, lp, sc)
+    del keep, keep_words
+    toks = np.ctypeslib.as_array(out).reshape(N * K, L).tolist()
+    n, lp, sc = list(n), list(lp), list(sc)
+    return [[(toks[r][:n[r]], lp[r], sc[r]) for r in range(i * K, (i + 1) * K) if n[r] > 0] for i in range(N)]
+
+
+def forced_captions(ctx, param, feats, index_to_word, beam_width, nword, alpha=0.0, forced=(), banned=(), min_len=0, no_repeat_ngram=0,
+                    normalize=False):
+    """beam_forced_batch as caption text: as nbest_captions."""
+    if normalize:
+        f = from_jl(feats)
+        feats = to_jl(f / f.sum(axis=1, keepdims=True))  # input/sum(input) per image (lrcn.jl:597)
+    res = beam_forced_batch(ctx, param, feats, beam_width, nword, alpha, forced, banned, min_len, no_repeat_ngram)
+    return [[(_caption(toks, index_to_word), lp, sc) for toks, lp, sc in entries] for entries in res]
+
+
+def forced_topk_logits(ctx, logits, K, hist, current, words, banned=(), min_len=0, no_repeat_ngram=0):
+    """One step of the forced-word top-K on the caller's own logits (lrcn_forced_topk_logits, include/lrcn_forced.h): logits and hist as
+    constrained_topk_logits; words int [R][C][A] (one row per "image", -1: no word; C may be 0) -> numpy (stay columns [R][K] int32, their
+    logp [R][K] f32, move logp [R][C*A] f32, states [R] int32).  Independent of the context's model sizes."""
+    dev = "cuda:%d" % ctx.device
+    if isinstance(logits, torch.Tensor):
+        z = logits
+    else:
+        a = np.ascontiguousarray(logits, dtype=np.float32)
+        ld = (a.shape[1] + 3) // 4 * 4   # rows 16 bytes apart
+        z = torch.zeros((a.shape[0], ld), dtype=torch.float32, device=dev)[:, :a.shape[1]]
+        z.copy_(torch.from_numpy(a))
+    R, V = z.shape
+    w = np.ascontiguousarray(words, dtype=np.int32)
+    if w.ndim != 3 or w.shape[0] != R:
+        raise LrcnError("forced words: an int array [R][C][A]")
+    Cn, An = w.shape[1], w.shape[2]
+    h = torch.from_numpy(np.ascontiguousarray(hist, dtype=np.int32)).to(dev)
+    idx = torch.empty((R, K), dtype=torch.int32, device=z.device)
+    lp = torch.empty((R, K), dtype=torch.float32, device=z.device)
+    mv = torch.empty((R, max(Cn * An, 1)), dtype=torch.float32, device=z.device)
+    st = torch.empty(R, dtype=torch.int32, device=z.device)
+    cons, keep = _constraints(banned, min_len, no_repeat_ngram)
+    torch.cuda.synchronize(z.device)   # the uploads have landed whichever stream the context runs on
+    ctx._call("lrcn_forced_topk_logits", C.c_void_p(z.data_ptr()), z.stride(0), R, V, int(K), C.byref(cons),
+              w.ctypes.data_as(C.POINTER(C.c_int32)), Cn, An, C.c_void_p(h.data_ptr()), h.shape[1], int(current), C.c_void_p(idx.data_ptr()),
+              C.c_void_p(lp.data_ptr()), C.c_void_p(mv.data_ptr()), C.c_void_p(st.data_ptr()))
+    del keep
+    ctx.sync()
+    return idx.cpu().numpy(), lp.cpu().numpy(), mv.cpu().numpy()[:, :Cn * An], st.cpu().numpy()
+
+
 _ENSEMBLE_MODES = {"prob": 0, "logprob": 1}   # LRCN_ENSEMBLE_PROB / LRCN_ENSEMBLE_LOGPROB
 
 

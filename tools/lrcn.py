@@ -18,6 +18,8 @@ batch is split by rows over the ranks (same T everywhere, the global batch as no
 every `--ss_every` epochs up to `--ss_max`, drawn on the device from the model's own logits of the step before (include/lrcn_sched.h).
 `--generate N --nbest --loadfile m0.npz --ensemble m1.npz ...` decodes several checkpoints of one vocabulary as one model
 (include/lrcn_ensemble.h).
+`--generate N --nbest --force_words "dog|dogs,frisbee"` (or `--force_file F`, sets per image) returns only captions that hold a word of
+every set (include/lrcn_forced.h) and writes them to `forced`.
 `--label_smoothing E` scores every training step against (1 - E) onehot + E / V inside the loss kernels (include/lrcn_smooth.h); it combines
 with `--varlen`, `--ss_start`, `--scst` and `--gclip`, and the per-epoch loss line stays the plain NLL of average_loss.
 `--gpus N` starts the ranks itself from a parent that never touches the GPU; the torchrun form works too.  `--cnn --train --imagedir`
@@ -85,6 +87,11 @@ def build_parser():
                         "hold (their probability is not given to the others: logp stays the model's)")
     p.add_argument("--min_len", type=int, default=0, help="--nbest: a caption does not end before it has this many words (at most --generate)")
     p.add_argument("--no_repeat_ngram", type=int, default=0, help="--nbest: no caption holds the same N words in a row twice (0 = off; 1 = no word twice)")
+    p.add_argument("--force_words", default="",
+                   help="--nbest: forced-word beam search (include/lrcn_forced.h) -- every caption holds a word of each comma-separated set, a "
+                        "set being alternatives joined by '|' (\"dog|dogs,frisbee\"); at most 3 sets of 4 words, 2^sets * --beam_width <= 32; "
+                        "writes <out>/forced in place of nbest; composes with --ban_words / --min_len / --no_repeat_ngram")
+    p.add_argument("--force_file", default="", help="--force_words per image: lines \"IMAGE_ID set,set,...\"; an image without a line has no set")
     p.add_argument("--ensemble", nargs="+", default=[], metavar="CHECKPOINT",
                    help="--nbest: ensemble beam search (include/lrcn_ensemble.h) -- further checkpoints of the same vocabulary that decode "
                         "together with --loadfile, one context each, sized from the checkpoint; the files --nbest / --diverse_groups write")
@@ -159,6 +166,37 @@ def main(argv=None):
         parser.error("--ban_words / --min_len / --no_repeat_ngram constrain the n-best beam: give --generate N --nbest (without --sample)")
     if o.min_len < 0 or o.no_repeat_ngram < 0 or o.min_len > max(o.generate, 0):
         parser.error("--min_len must be in [0, --generate] and --no_repeat_ngram >= 0")
+    forcing = bool(o.force_words or o.force_file)
+    if forcing and not (o.nbest and o.generate > 0 and o.sample <= 0):
+        parser.error("--force_words / --force_file force words into the n-best beam: give --generate N --nbest (without --sample)")
+    if forcing and (o.diverse_groups > 0 or o.ensemble):
+        parser.error("--force_words / --force_file do not combine with --diverse_groups or --ensemble")
+    if o.force_words and o.force_file:
+        parser.error("give --force_words (the same sets for every image) or --force_file (sets per image), not both")
+    if o.force_file and o.cnn:
+        parser.error("--force_file names the images of a feature table: with --cnn --image give --force_words")
+
+    def parse_sets(text, where):   # "dog|dogs,frisbee" -> [["dog", "dogs"], ["frisbee"]]
+        sets = [[w for w in part.split("|") if w] for part in text.split(",")]
+        sets = [alt for alt in sets if alt]
+        if len(sets) > 3 or any(len(alt) > 4 for alt in sets):
+            parser.error("%s: at most 3 sets of at most 4 alternatives" % where)
+        if (o.beam_width << len(sets)) > 32:
+            parser.error("%s: 2^sets * --beam_width = %d rows per image, at most 32" % (where, o.beam_width << len(sets)))
+        if o.generate < len(sets):
+            parser.error("%s: %d sets do not fit into --generate %d words" % (where, len(sets), o.generate))
+        return sets
+    force_sets = parse_sets(o.force_words, "--force_words") if o.force_words else []
+    force_by_image = {}
+    if o.force_file:
+        with open(o.force_file) as fh:
+            for ln in fh:
+                if ln.strip():
+                    key, _, rest = ln.strip().partition(" ") if "\t" not in ln else ln.strip().partition("\t")
+                    try:
+                        force_by_image[int(key)] = parse_sets(rest.strip(), "--force_file, image %s" % key)
+                    except ValueError:
+                        parser.error("--force_file: %r is no image id" % key)
     ens_weights = None
     if o.ensemble and not (o.nbest and o.generate > 0 and o.sample <= 0 and o.loadfile):
         parser.error("--ensemble decodes several checkpoints with the n-best beam: give --loadfile m0 --generate N --nbest (without --sample)")
@@ -246,6 +284,24 @@ def main(argv=None):
             parser.error("--ban_words: %r %s" % (w, "ends a caption: use --min_len" if w in ("<eos>", cap.EOS_WORD) else "is not in the vocabulary"))
         if vocab[w] - 1 not in ban_ids:
             ban_ids.append(vocab[w] - 1)
+    def force_ids(sets, where):   # words -> 0-based ABI ids, as --ban_words
+        out, seen = [], set()
+        for alt in sets:
+            ids = []
+            for w in alt:
+                if w in ("<eos>", cap.EOS_WORD) or w not in vocab:
+                    parser.error("%s: %r %s" % (where, w, "ends a caption" if w in ("<eos>", cap.EOS_WORD) else "is not in the vocabulary"))
+                if vocab[w] - 1 in ban_ids:
+                    parser.error("%s: %r is in --ban_words" % (where, w))
+                if vocab[w] - 1 in seen:
+                    parser.error("%s: %r occurs twice" % (where, w))
+                seen.add(vocab[w] - 1)
+                ids.append(vocab[w] - 1)
+            out.append(ids)
+        return out
+    force_sets = force_ids(force_sets, "--force_words")
+    force_by_image = {i: force_ids(sets, "--force_file, image %d" % i) for i, sets in force_by_image.items()}
+    force_banks = max([len(force_sets)] + [len(sets) for sets in force_by_image.values()]) if forcing else 0
     if len(o.hidden) != 2 or o.hidden[1] % 2:
         raise SystemExit("--hidden takes two sizes, the second even (LRCN-2f, lrcn.jl:496-504)")
     H1, H2 = o.hidden
@@ -310,6 +366,10 @@ def main(argv=None):
         return L.beam_ensemble_batch(ens_ctxs, ens_params, f, o.beam_width, o.generate, o.length_norm, ens_weights, o.ensemble_mode, ban_ids,
                                      o.min_len, o.no_repeat_ngram, groups=groups, strength=o.diverse_strength)
 
+    def forced_lists(f, image_ids=None):   # --nbest --force_words / --force_file: per image its sets, under the same constraints
+        sets = [force_by_image.get(i, []) for i in image_ids] if o.force_file else [force_sets] * f.shape[0]
+        return L.beam_forced_batch(ctx, param, f, o.beam_width, o.generate, o.length_norm, sets, ban_ids, o.min_len, o.no_repeat_ngram), sets
+
     def nbest_lists(f):     # --nbest, under --ban_words / --min_len / --no_repeat_ngram the constrained beam
         if o.ensemble:
             return ensemble_lists(f, 0)
@@ -343,7 +403,7 @@ def main(argv=None):
                         print("%d\t%.6f\t%.6f\t%s" % (g, sc, lp, cap.caption_text(toks, idx2word)))
                 return 0
             if o.nbest:   # the n-best list, best score first: score<TAB>logp<TAB>caption
-                for toks, lp, sc in nbest_lists(f)[0]:
+                for toks, lp, sc in (forced_lists(f)[0] if forcing else nbest_lists(f))[0]:
                     print("%.6f\t%.6f\t%s" % (sc, lp, cap.caption_text(toks, idx2word)))
                 return 0
             toks, _ = L.beam_search(ctx, param, f, o.beam_width, o.generate)
@@ -365,10 +425,12 @@ def main(argv=None):
         gc.freeze()
         smp = open(os.path.join(o.out, "samples" + suffix), "w") if o.sample > 0 else None
         dvf = open(os.path.join(o.out, "diverse" + suffix), "w") if o.nbest and o.diverse_groups > 0 and o.sample <= 0 else None
-        nbf = open(os.path.join(o.out, "nbest" + suffix), "w") if o.nbest and o.sample <= 0 and dvf is None else None
+        nbf = open(os.path.join(o.out, ("forced" if forcing else "nbest") + suffix), "w") if o.nbest and o.sample <= 0 and dvf is None else None
+        chunk_n = gen_chunk >> force_banks   # a forced image owns 2^sets * beam_width rows of the decode
+        met = with_sets = 0
         with open(os.path.join(o.out, "candidates" + suffix), "w") as out, open(os.path.join(o.out, "candidate_ids" + suffix), "w") as ido:
-            for s0 in range(0, len(ids), gen_chunk):  # the reference decodes image by image; here gen_chunk images x beam_width rows per step
-                chunk = ids[s0:s0 + gen_chunk]
+            for s0 in range(0, len(ids), chunk_n):  # the reference decodes image by image; here gen_chunk images x beam_width rows per step
+                chunk = ids[s0:s0 + chunk_n]
                 if o.sample > 0:
                     # candidates / ids keep one line per image (the best log-likelihood of the S draws); `samples` holds all of them:
                     # "id<TAB>log-likelihood<TAB>caption", the image's draws in sample order.  The draws of an image depend on its index in the
@@ -393,6 +455,17 @@ def main(argv=None):
                             for toks, lp, sc in grp:
                                 dvf.write("%d\t%d\t%.6f\t%.6f\t%s\n" % (i, g, sc, lp, cap.caption_text(toks, idx2word)))
                     continue
+                if nbf is not None and forcing:
+                    # as `nbest` below; an image whose sets could not be met within --generate words has no entry and an empty caption
+                    res, sets = forced_lists(feature_rows(table, chunk), chunk)
+                    for i, entries, st in zip(chunk, res, sets):
+                        ido.write("%d\n" % i)
+                        out.write(cap.caption_text(entries[0][0] if entries else [lrcn_amd.BOS], idx2word) + "\n")
+                        for toks, lp, sc in entries:
+                            nbf.write("%d\t%.6f\t%.6f\t%s\n" % (i, sc, lp, cap.caption_text(toks, idx2word)))
+                        with_sets += bool(st)
+                        met += bool(st) and bool(entries)
+                    continue
                 if nbf is not None:
                     # candidates / ids keep each image's best entry; `nbest` holds the list: "id<TAB>score<TAB>logp<TAB>caption", best first
                     for i, entries in zip(chunk, nbest_lists(feature_rows(table, chunk))):
@@ -408,6 +481,8 @@ def main(argv=None):
             smp.close()
         if nbf is not None:
             nbf.close()
+        if forcing:
+            say("forced words: %d of %d images with sets met them" % (met, with_sets))
         if dvf is not None:
             dvf.close()
         return 0
