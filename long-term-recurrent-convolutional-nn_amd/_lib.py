@@ -29,6 +29,7 @@ SMOOTH_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_smoot
 GEMM_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_gemm_debug.h"))  # lrcn_debug_gemm (not in lrcn.h)
 CONV_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_conv_debug.h"))  # lrcn_debug_conv11 and the fp8 seams (not in lrcn.h)
 DECODE_DEBUG_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_decode_debug.h"))  # lrcn_debug_decode_steps (not in lrcn.h)
+CIDER_HEADER = os.path.normpath(os.path.join(HERE, "..", "include", "lrcn_cider.h"))  # lrcn_cider_* (not in lrcn.h)
 
 LRCN_F32, LRCN_BF16, LRCN_FP8 = 0, 1, 2
 LRCN_ABI_VERSION = 5   # include/lrcn.h: the revision this binding's struct layouts and signatures were written against
@@ -360,11 +361,29 @@ DECODE_DEBUG_SIGNATURES = {
     "lrcn_debug_decode_steps": (C.c_int, [C.c_void_p, C.POINTER(DecodeDebug)]),
 }
 
+class CiderStats(C.Structure):   # lrcn_cider_stats_t of include/lrcn_cider.h
+    _fields_ = [("images", C.c_int64), ("references", C.c_int64), ("ngrams", C.c_int64 * 4), ("slots", C.c_int64 * 4),
+                ("ref_entries", C.c_int64 * 4), ("device_bytes", C.c_int64)]
+
+
+# name -> (restype, argtypes); exactly the symbols include/lrcn_cider.h declares (bound by lib() as well)
+CIDER_SIGNATURES = {
+    "lrcn_cider_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int,
+                                    C.POINTER(C.c_void_p)]),
+    "lrcn_cider_destroy": (None, [C.c_void_p]),
+    "lrcn_cider_last_error": (C.c_char_p, [C.c_void_p]),
+    "lrcn_cider_set_stream": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "lrcn_cider_stats": (C.c_int, [C.c_void_p, C.POINTER(CiderStats)]),
+    "lrcn_cider_score": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                   C.POINTER(C.c_double)]),
+    "lrcn_cider_score_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+}
+
 
 def build(force=False):
     """hipcc --offload-arch=gfx950 -> csrc/liblrcn_hip.so (cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))] + [HEADER, SAMPLE_HEADER, NUCLEUS_HEADER, SCORE_HEADER, NBEST_HEADER, DIVERSE_HEADER, CONSTRAIN_HEADER, ENSEMBLE_HEADER, FORCED_HEADER,
-                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER, DECODE_DEBUG_HEADER]
+                                                                                                   ACTIVITY_HEADER, ACT_DROPOUT_HEADER, VARLEN_HEADER, CLIP_HEADER, WEIGHTED_HEADER, SCHED_HEADER, SMOOTH_HEADER, GEMM_DEBUG_HEADER, CONV_DEBUG_HEADER, DECODE_DEBUG_HEADER, CIDER_HEADER]
     stale = force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(s) for s in srcs)
     if stale:
         subprocess.check_call(["make", "-s", "-j4", "-C", CSRC, "-f", os.path.join(CSRC, "Makefile")])
@@ -386,7 +405,7 @@ def lib():
         L = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(SAMPLE_SIGNATURES.items()) + list(NUCLEUS_SIGNATURES.items()) + list(SCORE_SIGNATURES.items()) + list(NBEST_SIGNATURES.items()) + list(DIVERSE_SIGNATURES.items()) + list(CONSTRAIN_SIGNATURES.items()) + list(ENSEMBLE_SIGNATURES.items()) + list(FORCED_SIGNATURES.items()) + \
                 list(ACTIVITY_SIGNATURES.items()) + list(ACT_DROPOUT_SIGNATURES.items()) + list(VARLEN_SIGNATURES.items()) + list(CLIP_SIGNATURES.items()) + list(WEIGHTED_SIGNATURES.items()) + list(SCHED_SIGNATURES.items()) + list(SMOOTH_SIGNATURES.items()) + \
-                list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()) + list(DECODE_DEBUG_SIGNATURES.items()):
+                list(GEMM_DEBUG_SIGNATURES.items()) + list(CONV_DEBUG_SIGNATURES.items()) + list(DECODE_DEBUG_SIGNATURES.items()) + list(CIDER_SIGNATURES.items()):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -4,8 +4,10 @@ already has: the sampler draws captions on the device, a host metric (cider.Cide
 
     loss = -(1 / norm_tokens) * sum_r (r(sample_r) - b_r) * log p(sample_r | image_r).
 
-The reward runs on the host: it is a few hundred n-gram look-ups per caption on word strings, needs the whole sampled sentence, and the
-sampler hands its tokens to the host anyway.
+The reward runs on the host by default: it is a few hundred n-gram look-ups per caption on word strings, needs the whole sampled sentence,
+and the sampler hands its tokens to the host anyway.  A reward object with a score_batch method (cider_device.DeviceCiderD, the same
+metric over token ids as one HIP kernel call per batch) is scored in one call per batch instead; the sampler's tokens still pass through
+the host.
 
 The sampler's output (include/lrcn_sample.h, lrcn.sample_batch) and the training batch.  A sampled row is seq[0] = bos, then one token
 per step current = 1 .. nword + 1; it stops after the step that emits eos, or after step nword + 1 whatever that step emitted, and its
@@ -114,10 +116,14 @@ def beam_cider(ctx, param, cider, image_ids, feats_of, index_to_word, beam_width
     ids = list(dict.fromkeys(image_ids))
     chunk = chunk or max(1, ctx.max_B // max(1, beam_width))
     hyps = {}
+    batch = hasattr(cider, "score_batch")     # cider_device.DeviceCiderD: scores ids, every caption in one call
     for k in range(0, len(ids), chunk):
         part = ids[k:k + chunk]
         for i, (seq, _) in zip(part, L.beam_search_batch(ctx, param, feats_of(part), beam_width, nword)):
-            hyps[i] = [index_to_word[t] for t in sample_words(seq, len(seq))]
+            words = sample_words(seq, len(seq))
+            hyps[i] = words if batch else [index_to_word[t] for t in words]
+    if batch:
+        return float(np.mean(cider.score_batch(ids, [hyps[i] for i in ids]))) if ids else 0.0
     return cider.corpus(hyps)[0]
 
 
@@ -141,7 +147,9 @@ def train_epoch(trainer, image_ids, feats_of, reward, images_per_step, S, nword,
 
 def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_k=0, top_p=1.0, seed=0, baseline="greedy", label_smoothing=0.0):
     """One self-critical step of dp.DataParallelTrainer `trainer` on N images.  feats: N x 4096 (column-major device tensor, as every call
-    takes them); image_ids [N]; reward(image_id, word ids without bos / eos) -> float, on the host.
+    takes them); image_ids [N]; reward(image_id, word ids without bos / eos) -> float, on the host -- or an object with
+    score_batch(image ids [R], R lists of word ids) -> R floats (cider_device.DeviceCiderD): the N S samples are then scored in one call and
+    the N greedy captions in a second one, with no Python loop over the captions' rewards.
       1. lrcn.sample_batch draws S samples per image (temperature / top_k / top_p / seed as there);
       2. baseline "greedy": lrcn.beam_search_batch with K = 1 (= temperature 0, include/lrcn_sample.h) gives each image's baseline caption;
          "mean": the mean reward of the image's other samples, no second decode;
@@ -163,11 +171,19 @@ def scst_step(trainer, feats, image_ids, reward, S, nword, temperature=1.0, top_
         raise L.LrcnError("baseline is greedy, or mean with at least 2 samples per image")
     samples = L.sample_batch(ctx, trainer.param, feats, S, nword, temperature=temperature, top_k=top_k, seed=seed, top_p=top_p)
     tok, out_len = pack_samples(samples, nword)
-    r_sample = np.asarray([[reward(image_ids[i], sample_words(tok[i, s], out_len[i, s])) for s in range(S)] for i in range(N)], np.float64)
+    batch = hasattr(reward, "score_batch")
+    if batch:
+        r_sample = np.asarray(reward.score_batch([image_ids[i] for i in range(N) for _ in range(S)],
+                                                 [sample_words(tok[i, s], out_len[i, s]) for i in range(N) for s in range(S)]), np.float64).reshape(N, S)
+    else:
+        r_sample = np.asarray([[reward(image_ids[i], sample_words(tok[i, s], out_len[i, s])) for s in range(S)] for i in range(N)], np.float64)
     r_greedy = None
     if baseline == "greedy":
         greedy = L.beam_search_batch(ctx, trainer.param, feats, 1, nword)
-        r_greedy = np.asarray([reward(image_ids[i], sample_words(ids, len(ids))) for i, (ids, _) in enumerate(greedy)], np.float64)
+        if batch:
+            r_greedy = np.asarray(reward.score_batch(list(image_ids), [sample_words(ids, len(ids)) for ids, _ in greedy]), np.float64)
+        else:
+            r_greedy = np.asarray([reward(image_ids[i], sample_words(ids, len(ids))) for i, (ids, _) in enumerate(greedy)], np.float64)
     adv = advantages(r_sample, r_greedy, baseline)
     tokens, lens, weights, norm_tokens = build_batch(tok, out_len, adv)
     nonzero = int(np.count_nonzero(weights))

@@ -133,6 +133,8 @@ def build_parser():
     p.add_argument("--scst_baseline", default="greedy", choices=["greedy", "mean"],
                    help="--scst: the reward a sample is compared with -- the greedy caption's, or the mean of the image's other samples")
     p.add_argument("--scst_nword", type=int, default=20, help="--scst: sampled captions have at most this many words")
+    p.add_argument("--scst_reward", default=None, choices=["host", "device"],
+                   help="--scst: where CIDEr-D runs -- host (lrcn_amd/cider.py, the default) or device (include/lrcn_cider.h, one kernel call per batch)")
     p.add_argument("--no_normalize", action="store_true", help="--cnn --train: do not divide fc7 features by their sum (lrcn.jl:595-597 does)")
     return p
 
@@ -215,6 +217,8 @@ def main(argv=None):
         raise SystemExit("--varlen chooses the batches of the TRAINING job (--train)")
     if o.ss_start >= 0 and (not o.train or o.scst):
         raise SystemExit("--ss_start is a mode of the cross-entropy TRAINING job (--train without --scst)")
+    if o.scst_reward is not None and not o.scst:
+        raise SystemExit("--scst_reward is an option of self-critical TRAINING (--train --scst)")
     if o.scst and not o.train:
         raise SystemExit("--scst is a mode of the TRAINING job (--train)")
     if not 0.0 <= o.label_smoothing <= 1.0:
@@ -547,13 +551,19 @@ def main(argv=None):
             raise SystemExit("--scst: batchsize // scst_samples images per step (at least one per rank); the mean baseline needs 2 samples")
         tables = [feats[0], feats[min(1, len(feats) - 1)]]
         refs = scst.references_by_image(lists[0], vocab)
-        reward = scst.cider_reward(CiderD(refs), idx2word)
+        on_device = o.scst_reward == "device"
+        if on_device:
+            from lrcn_amd.cider_device import DeviceCiderD
+            word_ids = {w: i - 1 for w, i in vocab.items()}      # the C ABI's ids: what the sampler and the beam search write
+            reward = DeviceCiderD(refs, word_ids, word_ids[cap.UNK_WORD])
+        else:
+            reward = scst.cider_reward(CiderD(refs), idx2word)
         ids = [i for i in refs if i in tables[0]]
         mine = ids[rank::world][:len(ids) // world]       # the same count on every rank
         dev = None
         if len(lists) > 1:
             dev_refs = scst.references_by_image(lists[1], vocab)
-            dev = (CiderD(dev_refs), [i for i in dev_refs if i in tables[1]])
+            dev = (DeviceCiderD(dev_refs, word_ids, word_ids[cap.UNK_WORD]) if on_device else CiderD(dev_refs), [i for i in dev_refs if i in tables[1]])
         say("scst: %d images with references, %d per step on %d rank%s, %d samples each, baseline %s"
             % (len(ids), per_step * world, world, "" if world == 1 else "s", S, o.scst_baseline))
         optim = L.initparams(param)

@@ -9,7 +9,11 @@ V = 10640, bf16):
          (lengths from the same histogram), alternated in one process; the spread of the lrcn_train_step_var rounds is printed beside them.
 
 Prints one line per measurement and a JSON summary line.
-usage: python tools/scst_bench.py [--images 64] [--samples 4] [--nword 20] [--rounds 5] [--steps 30] [--out FILE]"""
+--reward device runs the split's rewards with cider_device.DeviceCiderD (include/lrcn_cider.h) instead; --reward both runs the host and the
+device reward in turn in every round on the same captions (one more row in the split) and reports the largest absolute difference between them.
+
+usage: python tools/scst_bench.py [--images 64] [--samples 4] [--nword 20] [--rounds 5] [--steps 30] [--reward host|device|both] [--split_only]
+                                  [--out FILE]"""
 import argparse
 import json
 import os
@@ -57,7 +61,7 @@ def timed(fn, n):
     return (time.perf_counter() - t0) / n * 1e3
 
 
-def step_split(N, S, nword, rounds, rng):
+def step_split(N, S, nword, rounds, rng, reward_mode="host"):
     ctx = L.Context(E, H, H, V, max_B=N * S, max_T=nword + 1, lstm_dtype=lrcn_amd.LRCN_BF16)
     param = L.initweights(ctx, seed=42)
     optim = L.initparams(param)
@@ -67,26 +71,59 @@ def step_split(N, S, nword, rounds, rng):
     refs = {i: [[words[w] for w in rng.integers(3, V, size=int(n))] for n in hist_lengths(5, rng, nword)] for i in ids}
     cider = CiderD(refs)
     reward = scst.cider_reward(cider, words)
+    dev, t_build = None, None
+    if reward_mode != "host":
+        from lrcn_amd.cider_device import DeviceCiderD
+        t0 = time.perf_counter()
+        dev = DeviceCiderD(refs, {w: k for k, w in enumerate(words)}, L.UNK)
+        t_build = (time.perf_counter() - t0) * 1e3      # the one-time table build and upload for this corpus
+    image_rows = [i for i in ids for _ in range(S)] + ids     # the N S samples' images, then the N greedy captions'
     feats = L.to_jl((rng.standard_normal((N, 4096)) * 0.01).astype(np.float32))
     rows = L.to_jl(feats.repeat_interleave(S, dim=0))
     out = {"N": N, "S": S, "nword": nword, "rows": N * S, "rounds": []}
     for r in range(rounds + 1):     # round 0 warms every shape up and is not reported
         t_s, samples = wall(lambda: L.sample_batch(ctx, param, feats, S, nword, seed=100 + r))
         t_g, greedy = wall(lambda: L.beam_search_batch(ctx, param, feats, 1, nword))
-        t0 = time.perf_counter()
+        t_r = t_d = t_hs = diff = None
         tok, n = scst.pack_samples(samples, nword)
-        r_s = [[reward(i, scst.sample_words(tok[i, s], n[i, s])) for s in range(S)] for i in ids]
-        r_g = [reward(i, scst.sample_words(seq, len(seq))) for i, (seq, _) in zip(ids, greedy)]
-        tokens, lens, w, nt = scst.build_batch(tok, n, scst.advantages(r_s, r_g))
-        t_r = (time.perf_counter() - t0) * 1e3
+        if reward_mode != "device":
+            t0 = time.perf_counter()
+            tok, n = scst.pack_samples(samples, nword)
+            r_s = [[reward(i, scst.sample_words(tok[i, s], n[i, s])) for s in range(S)] for i in ids]
+            r_g = [reward(i, scst.sample_words(seq, len(seq))) for i, (seq, _) in zip(ids, greedy)]
+            t_hs = (time.perf_counter() - t0) * 1e3     # CiderD.score over all captions plus the Python that feeds it
+            tokens, lens, w, nt = scst.build_batch(tok, n, scst.advantages(r_s, r_g))
+            t_r = (time.perf_counter() - t0) * 1e3
+        if dev is not None:
+            # the sampler's arrays as they are, the greedy rows behind them: one score_ids call to the float64 result (copies and the wait inside)
+            gt, gn = scst.pack_samples([[g] for g in greedy], nword)
+            all_tok = np.concatenate([tok.reshape(N * S, -1), gt.reshape(N, -1)])
+            all_len = np.concatenate([n.reshape(-1), gn.reshape(-1)])
+            t_d, r_dev = wall(lambda: dev.score_ids(image_rows, all_tok, all_len))
+            if reward_mode == "both":
+                diff = float(np.abs(r_dev - np.concatenate([np.asarray(r_s, np.float64).reshape(-1), np.asarray(r_g, np.float64)])).max())
+            else:
+                tokens, lens, w, nt = scst.build_batch(tok, n, scst.advantages(r_dev[:N * S].reshape(N, S), r_dev[N * S:]))
         if not np.count_nonzero(w):
             w[:] = 1.0               # (every reward 0 against random references: time the step all the same)
         t_t, _ = wall(lambda: tr.step(None, tokens, feats=rows, lens=lens, norm_tokens=nt, row_weights=w))
         if r:
             out["rounds"].append({"sample_ms": t_s, "greedy_ms": t_g, "host_reward_ms": t_r, "train_step_ms": t_t, "T": int(tokens.shape[0]),
                                   "mean_words": float(lens.mean()), "zero_weight_share": 1.0 - np.count_nonzero(w) / float(N * S)})
-    for k in ("sample_ms", "greedy_ms", "host_reward_ms", "train_step_ms"):
-        out[k + "_median"] = float(np.median([x[k] for x in out["rounds"]]))
+            if t_hs is not None:
+                out["rounds"][-1]["host_score_ms"] = t_hs
+            if t_d is not None:
+                out["rounds"][-1]["device_reward_ms"] = t_d
+            if diff is not None:
+                out["rounds"][-1]["reward_max_abs_diff"] = diff
+    for k in ("sample_ms", "greedy_ms", "host_reward_ms", "host_score_ms", "device_reward_ms", "train_step_ms"):
+        if out["rounds"] and out["rounds"][0].get(k) is not None:
+            out[k + "_median"] = float(np.median([x[k] for x in out["rounds"]]))
+    if dev is not None:
+        out["device_table_build_ms"], out["device_stats"] = t_build, dev.stats()
+        if reward_mode == "both":
+            out["reward_max_abs_diff"] = max(x["reward_max_abs_diff"] for x in out["rounds"])
+        dev.close()
     tr.close()
     ctx.close()
     torch.cuda.empty_cache()
@@ -135,16 +172,26 @@ def main():
     ap.add_argument("--nword", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--reward", default="host", choices=["host", "device", "both"],
+                    help="where the split's CIDEr-D runs: host (cider.CiderD), device (cider_device.DeviceCiderD), or both in turn in every round")
+    ap.add_argument("--split_only", action="store_true", help="skip the train-step comparison")
     ap.add_argument("--out")
     o = ap.parse_args()
     rng = np.random.default_rng(0)
-    sp = step_split(o.images, o.samples, o.nword, o.rounds, rng)
-    print("scst step, %d images x %d samples (%d rows), at most %d words, medians of %d rounds: sample %.2f ms | greedy %.2f ms | host reward %.2f ms | "
-          "weighted train step %.2f ms   (T = %d, %.1f words per sample)"
-          % (sp["N"], sp["S"], sp["rows"], sp["nword"], len(sp["rounds"]), sp["sample_ms_median"], sp["greedy_ms_median"], sp["host_reward_ms_median"],
-             sp["train_step_ms_median"], sp["rounds"][-1]["T"], sp["rounds"][-1]["mean_words"]), flush=True)
+    sp = step_split(o.images, o.samples, o.nword, o.rounds, rng, o.reward)
+    ms = lambda k: "%.2f ms" % sp[k + "_median"] if k + "_median" in sp else "not run"   # noqa: E731
+    print("scst step, %d images x %d samples (%d rows), at most %d words, medians of %d rounds: sample %s | greedy %s | host reward %s | "
+          "weighted train step %s   (T = %d, %.1f words per sample)"
+          % (sp["N"], sp["S"], sp["rows"], sp["nword"], len(sp["rounds"]), ms("sample_ms"), ms("greedy_ms"), ms("host_reward_ms"),
+             ms("train_step_ms"), sp["rounds"][-1]["T"], sp["rounds"][-1]["mean_words"]), flush=True)
+    if o.reward != "host":
+        print("device reward (one score_ids call over the %d samples and %d greedy captions): %s, rounds %s | host scores alone %s, rounds %s | "
+              "table build %.1f ms | largest |device - host| %s | %s"
+              % (sp["rows"], sp["N"], ms("device_reward_ms"), " ".join("%.3f" % x["device_reward_ms"] for x in sp["rounds"]), ms("host_score_ms"),
+                 " ".join("%.3f" % x["host_score_ms"] for x in sp["rounds"] if "host_score_ms" in x), sp["device_table_build_ms"],
+                 "%.3g" % sp["reward_max_abs_diff"] if "reward_max_abs_diff" in sp else "not run", sp["device_stats"]), flush=True)
     steps = []
-    for B in (256, 32):
+    for B in (() if o.split_only else (256, 32)):
         r = step_times(B, 20, o.rounds, o.steps, rng)
         steps.append(r)
         print("train step B=%3d T=20 (mean length %.1f): lrcn_train_step_var %.3f ms (rounds %s, spread %.2f %%) | lrcn_train_step_w, weights 1: %.3f ms "
